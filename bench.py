@@ -4,7 +4,11 @@
   python bench.py --gpus 1 --steps K --warmup W           (N>1: launched by torch.distributed.run, one rank / GPU)
 
 A "step" is one env.step() of ALL envs of the shard: one launch of the fused HIP kernel (action term -> 4 physics
-sub-steps -> terminations -> rewards -> resets -> pushes -> 14-dim observation).  Workload (config.workload): drift
+sub-steps -> terminations -> rewards -> resets -> pushes -> 14-dim observation).  W warm-up steps and one untimed
+block of K steps are followed by ONE timed block of exactly K steps; `ms_per_step` is that block's wall time / K (the
+secondary figures -- events, kernel-only duration, other tasks -- are measured after it).  `--dump-outputs DIR` writes what the
+last timed step returned (observation, reward, terminated, truncated) as float32 .npy files; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.  Workload (config.workload): drift
 task, 4096 envs per GPU, flat terrain, synthetic U(-1,1) actions pre-staged in HBM, outputs written into a
 [128, n, ...] rollout storage exactly as an on-policy runner would keep them (modified_rsl_rl_runner.py:70-73).
 Env shards are independent (weak scaling); the only collective is the episode-metric all-reduce (RCCL) once per
@@ -28,7 +32,7 @@ import torch  # noqa: E402
 
 ENVS_PER_GPU = 4096
 ROLLOUT = 128            # num_steps_per_env of the reference's PPO config
-REPEATS = 11             # timed blocks of --steps steps each; the headline is their median
+DUMP_BYTES = 64 << 20    # --dump-outputs budget over all ranks: larger batches are written as a seeded sample of envs
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s achievable)
 
 # algorithmic HBM bytes per env-step of the fused drift kernel:
@@ -402,6 +406,24 @@ def write_detail(detail, path=None):
         return None
 
 
+def dump_outputs(out_dir, arrays, suffix="", budget=DUMP_BYTES):
+    """arrays: name -> [n, ...] tensor (one row per env) -> out_dir/<name><suffix>.npy in float32.  Should they exceed `budget`
+    bytes, the same seeded, sorted sample of envs is taken from each, and its env indices go to env_index<suffix>.npy (float64)."""
+    import numpy as np
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values())
+    if n * row_bytes > budget:
+        m = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        sel = torch.from_numpy(idx).to(next(iter(arrays.values())).device)
+        arrays = {k: t.index_select(0, sel) for k, t in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, t in arrays.items():
+        a = t if isinstance(t, np.ndarray) else t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
+
+
 _ROOF_KEYS = ("bound", "regime", "achieved", "peak", "unit", "frac", "traffic", "frac_launch", "frac_profile", "frac_counters", "frac_survey",
               "wasted_traffic", "valu_frac", "kernel", "launch_us", "profile_us", "bytes_per_env_step", "bytes_per_env_step_survey",
               "envs_per_launch", "frac_is")
@@ -484,7 +506,11 @@ def main():
     ap.add_argument("--headline-only", action="store_true", help="only the timed headline workload: no secondary sections, no CPU baseline")
     ap.add_argument("--detail-out", default=None, help="side file for everything measured (default gpurun_out/bench_detail.json)")
     ap.add_argument("--print-detail", action="store_true", help="also print the full detail as an earlier stdout line prefixed `[bench detail] `")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB; per rank: <name>_rank<r>.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.sweep_child:
         assert torch.cuda.is_available(), "bench.py needs a GPU (the product has no CPU path)"
         d0 = torch.device("cuda", 0)
@@ -554,7 +580,8 @@ def main():
         cadence["reductions"] += 1
 
     def run(k_steps):
-        done = 0
+        """k_steps env.step()s; returns the storage row the last one wrote"""
+        done = k = 0
         while done < k_steps:
             k = min(every - cadence["since"], k_steps - done)
             env.rollout(actions[:k], obs_buf, rew_buf, term_buf, trunc_buf)
@@ -562,6 +589,7 @@ def main():
             cadence["since"] += k
             if cadence["since"] >= every:
                 reduce_metrics()
+        return k - 1
 
     def drain():
         if cadence["since"] > 0:
@@ -587,36 +615,36 @@ def main():
             dist.destroy_process_group()
             sys.exit(3)
     run(args.warmup)
-    # EXACTLY --steps steps per timed block, bracketed by barrier + synchronize, max over ranks -- and REPEATS such blocks:
-    # at the driver's K = 20 one block is 0.15 ms, a single sample of which is launch-queue noise (round 1 reported
-    # 10.9 us / step where the steady state was 7.2); the headline is the median block
-    walls, gpu = [], []
+    # the timed block's shape (K launches queued back to back) once untimed: after a short warm-up alone the first K-step block
+    # measured 8.2 us / step where the steady state was 7.0 (K = 20)
+    run(args.steps)
+    # ONE timed block of EXACTLY --steps steps, bracketed by barrier + synchronize, max over ranks: --steps is the number of
+    # timed steps, and a caller sizes later runs from ms_per_step.  No timing event is recorded before it: with two event
+    # records around it the same 20-step block measured 7.8 - 9.4 us / step instead of 7.1.
     cadence["reductions"] = 0
-    for _ in range(REPEATS):
-        barrier()
-        t0 = time.perf_counter()
-        run(args.steps)
-        barrier()
-        w = time.perf_counter() - t0
-        t = torch.tensor([w], device=dev, dtype=torch.float64)
-        if dist is not None:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        walls.append(float(t.item()))
+    barrier()
+    t0 = time.perf_counter()
+    last = run(args.steps)
+    barrier()
+    t = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+    if dist is not None:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    wall = float(t.item())
     reductions_in_timed_blocks = cadence["reductions"]
-    # the same block between two events on the launch stream (secondary figure; NOT inside the wall-timed blocks above:
-    # two event records are 8 us of host work, 6 % of a 20-step block)
-    for _ in range(5):
-        barrier()
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        run(args.steps)
-        ev1.record()
-        barrier()
-        gpu.append(ev0.elapsed_time(ev1))
-    wall = sorted(walls)[len(walls) // 2]
-    wall_mean = sum(walls) / len(walls)
-    gpu_ms = sorted(gpu)[len(gpu) // 2]
-    drain()   # what the timed blocks left in the accumulators (outside the timing: short runs report their metrics too)
+    if args.dump_outputs:
+        # what env.step() returned in the last timed step, before anything below reuses the storage rows
+        dump_outputs(args.dump_outputs, {"obs": obs_buf[last], "reward": rew_buf[last], "terminated": term_buf[last],
+                                         "truncated": trunc_buf[last]},
+                     "" if world == 1 else f"_rank{rank}", DUMP_BYTES // world)
+    # secondary figure: a block of the same shape between two events on the launch stream
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    barrier()
+    ev0.record()
+    run(args.steps)
+    ev1.record()
+    barrier()
+    gpu_ms = ev0.elapsed_time(ev1)
+    drain()   # what the blocks left in the accumulators (outside the timing: short runs report their metrics too)
 
     # kernel-only duration: K back-to-back launches of the fused step between two events on the launch stream
     env.rollout(actions, obs_buf, rew_buf, term_buf, trunc_buf)
@@ -1002,10 +1030,8 @@ def main():
                        "envs_per_gpu": n, "total_envs": total_envs, "decimation": 4, "sim_dt": 0.005,
                        "parallelism": f"env-shard x{world}, metric all-reduce / {every} steps"},
             "gpu_event_ms_per_step": gpu_ms / args.steps,
-            "timing": {"repeats": REPEATS, "statistic": "median of the per-block max-over-ranks wall time",
-                       "block_ms": [round(w * 1e3, 4) for w in walls],
-                       # every block counted, incl. the ones the metric all-reduce falls into (the median skips them at K < 128)
-                       "mean_value": total_envs * args.steps / wall_mean, "mean_ms_per_step": wall_mean * 1e3 / args.steps,
+            "timing": {"repeats": 1, "statistic": "max-over-ranks wall time of the one timed block of --steps steps",
+                       "block_ms": [round(wall * 1e3, 4)],
                        "metric_reductions_in_timed_blocks": reductions_in_timed_blocks, "allreduce_every": every},
             "rccl": rccl,
             # `bound` names the roofline `peak` belongs to (the contract: "hbm" | "mfma"); `regime` says what actually limits the
@@ -1022,7 +1048,7 @@ def main():
                          "valu_frac": sq.get("valu_pipe_frac") if sq else None, "sq_counters": sq,
                          "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
                          "kernel": "drift_step_kernel<FlatGround>", "launch_us": launch_us,
-                         "frac_uses": "ms_per_step (wall clock of the timed blocks); frac_launch: launch_us (HIP events on the launch stream)",
+                         "frac_uses": "ms_per_step (wall clock of the timed block); frac_launch: launch_us (HIP events on the launch stream)",
                          "rocprof_kernel_stats": prof, "frac_profile": frac_profile, "frac_counters": frac_counters,
                          "wasted_traffic": traffic / (BYTES_PER_ENV_STEP * n) if traffic else None,
                          "bytes_per_env_step": BYTES_PER_ENV_STEP, "envs_per_launch": n},

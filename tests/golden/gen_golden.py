@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by IMPORTING the reference's own mdp functions.
 
-Runs only in the authoring container (it reads /root/reference, which does not exist on the GPU box).
-Nothing here is imported by the product or by the tests; the tests only read the ``.npz`` files this
-script writes.  No reference source text is copied: the reference modules are imported in place, fed
-seeded inputs, and only (inputs, outputs) arrays are stored.
+Needs a checkout of the reference: WL_REFERENCE_SRC names its ``source/`` directory.  Nothing here is
+imported by the product or by the tests; the tests only read the ``.npz`` files this script writes.
+No reference source text is copied: the reference modules are imported in place, fed seeded inputs,
+and only (inputs, outputs) arrays are stored.
 
 How the import works: the reference is a plugin layer on IsaacLab 2.0.2, which is
 not installed here.  We inject a stub ``isaaclab`` namespace whose *state accessors* are one-liners over a
@@ -14,8 +14,8 @@ therefore "parity unpinned" -- see DESIGN.md).  Every arithmetic line that the r
 (reward / termination / observation / action-term / reset / curriculum / traversability functions) is
 executed from the reference's files.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py      (WL_GOLDEN_OUT=<dir> writes there instead;
-tests/test_oracle_golden_drift.py::test_committed_vectors_regenerate_from_the_reference does that and compares)
+Usage:  WL_REFERENCE_SRC=<reference>/source PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py
+        (WL_GOLDEN_OUT=<dir> writes there instead; WL_GOLDEN_SEED_OFFSET=1000 made tests/golden_seed1000/, 2024 tests/golden/seed2024/)
 """
 import sys
 
@@ -30,9 +30,9 @@ import types
 import numpy as np
 import torch
 
-REF = "/root/reference/source"
+REF = os.environ.get("WL_REFERENCE_SRC", "")   # the reference checkout's source/ directory
 OUT = os.environ.get("WL_GOLDEN_OUT") or os.path.dirname(os.path.abspath(__file__))   # WL_GOLDEN_OUT: regenerate elsewhere
-# WL_GOLDEN_SEED_OFFSET shifts every INPUT seed (states, actions, query points, reset draws): fresh vectors for
+# WL_GOLDEN_SEED_OFFSET shifts every INPUT seed (states, actions, query points, reset draws): the fresh-seed vectors of
 # tests/test_oracle_golden_drift.py::test_oracle_matches_the_reference_on_fresh_seeds (the map-generation seeds stay: the
 # tests regenerate those maps from the same numpy seeds)
 SEED_OFFSET = int(os.environ.get("WL_GOLDEN_SEED_OFFSET", "0"))
@@ -813,4 +813,6 @@ def main():
 
 
 if __name__ == "__main__":
+    if not os.path.isdir(os.path.join(REF, "wheeledlab_tasks")):
+        sys.exit("gen_golden.py: set WL_REFERENCE_SRC to the reference checkout's source/ directory")
     main()

