@@ -3,7 +3,10 @@
 (source/wheeledlab_rl/scripts/play_policy.py:128-165: torch.save({'observations': [T,N,D], 'actions': [T,N,2]})).
 
     python scripts/play_policy.py --task Isaac-MushrDriftRL-v0 --checkpoint logs/drift/models/model_99.pt --steps 200 \\
-        --save_data logs/drift/playback/run-rollouts.pt"""
+        --save_data logs/drift/playback/run-rollouts.pt --video
+
+--video records one --steps long clip of the viewer camera into the playback folder (the --save_data file's, else
+<checkpoint's run>/playback), as the reference's play_policy.py:103-114."""
 import argparse
 import os
 import sys
@@ -20,6 +23,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--save_data", default=None)
+    ap.add_argument("--video", action="store_true", help="record a clip of the playback (viewer camera)")
+    ap.add_argument("--video_folder", default=None, help="where the clip goes (default: the playback folder)")
     args = ap.parse_args()
 
     import torch
@@ -31,8 +36,17 @@ def main():
 
     env_cfg = registry.parse_env_cfg(args.task, device=args.device, num_envs=args.num_envs, play=True)
     agent_cfg = registry.load_cfg_from_registry(args.task, "rsl_rl_cfg_entry_point")
-    env = registry.make(args.task, cfg=env_cfg)
+    env = registry.make(args.task, cfg=env_cfg, render_mode="rgb_array" if args.video else None)
     env.action_space.low, env.action_space.high = -1.0, 1.0
+    recorder = None
+    if args.video:
+        from wheeledlab_amd.video import RecordVideo
+        folder = args.video_folder or (os.path.dirname(os.path.abspath(args.save_data)) if args.save_data else
+                                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(args.checkpoint))), "playback"))
+        start = env.common_step_counter
+        recorder = RecordVideo(env, video_folder=folder, step_trigger=lambda step: step == start, video_length=args.steps,
+                               name_prefix="rl-video", disable_logger=False)
+        print(f"[INFO] Recording video of playback to: {folder}")
     env = RslRlVecEnvWrapper(ClipAction(env))
     runner = OnPolicyRunner(env, agent_cfg, device=args.device)
     runner.load(args.checkpoint, load_optimizer=False)
@@ -57,6 +71,8 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.save_data)), exist_ok=True)
         torch.save({k: torch.stack(v, 0) for k, v in data.items()}, args.save_data)
         print("[INFO] Saved episode data to:", args.save_data)
+    if recorder is not None:
+        recorder.close()
     env.close()
 
 

@@ -77,8 +77,18 @@ def main():
             yaml.safe_dump(json.loads(json.dumps(run_cfg.to_dict(), default=str)), f)
 
     torch.manual_seed(train_cfg.seed)
-    env = registry.make(env_setup.task_name, cfg=env_cfg)
+    record = bool(log_cfg.video) and rank == 0 and log_dir is not None
+    env = registry.make(env_setup.task_name, cfg=env_cfg, render_mode="rgb_array" if record else None)
     env.action_space.low, env.action_space.high = -1.0, 1.0
+    recorder = None
+    if record:      # train_rl.py:78-90: clips of video_length steps every video_interval steps, global rank 0 only
+        from wheeledlab_amd.video import RecordVideo
+        interval = int(log_cfg.video_interval)
+        recorder = RecordVideo(env, video_folder=os.path.join(log_cfg.run_log_dir, "videos"), step_trigger=lambda step: step % interval == 0,
+                               video_length=int(log_cfg.video_length), video_resolution=tuple(log_cfg.video_resolution),
+                               disable_logger=bool(args.quiet))
+        if not args.quiet:
+            print(f"[INFO] Recording videos during training into {recorder.video_folder}")
     env = RslRlVecEnvWrapper(ClipAction(env))
     if not log_cfg.no_checkpoints:
         agent_cfg.save_interval = min(agent_cfg.save_interval, log_cfg.checkpoint_every)
@@ -116,6 +126,8 @@ def main():
                           "mean_step_reward_first": first["mean_step_reward"], "mean_step_reward_last": last["mean_step_reward"],
                           "mean_reward_last": last["mean_reward"], "mean_episode_length_last": last["mean_episode_length"],
                           "n_gpus": world, "ranks_in_sync": in_sync, "fps_last": last["fps"], "collection_fps_last": last["collection_fps"], "log_dir": log_dir}))
+    if recorder is not None:
+        recorder.close()
     env.close()
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -252,6 +252,29 @@ SIGNATURES = {
     "wl_visual_depth_observe": (C.c_int, [_P(WlVisualParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, C.c_float, _vp, _vp]),
 }
 
+# include/wheeledlab_amd_viewer.h: the viewer camera -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)
+WL_VIEWER_VERSION = 1
+VIEWER_PLANE, VIEWER_HEIGHTFIELD = 0, 1
+VIEWER_TILE = 16
+
+
+class WlViewerParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("cam_pos", C.c_float * 3), ("cam_quat", C.c_float * 4),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("far_clip", C.c_float),
+                ("ground", C.c_int32), ("plane_z", C.c_float), ("checker", C.c_float), ("sun", C.c_float * 3), ("ambient", C.c_float),
+                ("box_center", C.c_float * 3), ("box_half", C.c_float * 3), ("half_wheelbase_f", C.c_float),
+                ("half_wheelbase_r", C.c_float), ("half_track", C.c_float), ("wheel_z", C.c_float), ("wheel_radius", C.c_float),
+                ("env_index", C.c_int32), ("id_offset", C.c_int32)]
+
+
+# every symbol include/wheeledlab_amd_viewer.h declares
+VIEWER_SIGNATURES = {
+    "wl_viewer_version": (C.c_int, []),
+    "wl_viewer_scratch_bytes": (C.c_int64, [_i32, _i32, _i32]),
+    "wl_viewer_render": (C.c_int, [_P(WlViewerParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _P(WlTravMap), _vp, _i64, _vp, _vp, _vp,
+                                   _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -274,7 +297,7 @@ def load(path: str | None = None):
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -283,6 +306,8 @@ def load(path: str | None = None):
     v = lib.wl_version()
     if v != WL_ABI_VERSION:
         raise HipExtensionMissing(f"{path} has ABI version {v}, python expects {WL_ABI_VERSION}: rebuild")
+    if lib.wl_viewer_version() != WL_VIEWER_VERSION:
+        raise HipExtensionMissing(f"{path} has viewer version {lib.wl_viewer_version()}, python expects {WL_VIEWER_VERSION}: rebuild")
     _lib = lib
     return lib
 

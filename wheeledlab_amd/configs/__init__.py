@@ -13,13 +13,16 @@ WHEELEDLAB_LOGS_DIR = os.environ.get("WHEELEDLAB_LOGS_DIR", os.path.join(os.getc
 
 @configclass
 class LogConfig:
-    """logging during training (common_cfg.py:12-45); video / wandb switches are accepted and ignored (no renderer)"""
+    """logging during training (common_cfg.py:12-45).  video: clips of video_length steps every video_interval steps from the
+    viewer camera into run_log_dir/videos (scripts/train_rl.py; off by default here, on in the reference); wandb switches are
+    accepted and ignored"""
     logs_dir: str = WHEELEDLAB_LOGS_DIR
     no_log: bool = False
     log_every: int = 10
     video: bool = False
     video_length: int = 500
     video_interval: int = 5000
+    video_resolution: tuple = (1280, 720)
     no_checkpoints: bool = False
     checkpoint_every: int = 1000
     no_wandb: bool = True

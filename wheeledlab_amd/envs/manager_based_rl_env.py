@@ -14,6 +14,7 @@ import os
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from .. import _abi as A
@@ -210,7 +211,7 @@ class EpisodeLog(dict):
 
 
 class ManagerBasedRLEnv:
-    metadata = {"render_modes": [None]}
+    metadata = {"render_modes": [None, "rgb_array"], "render_fps": None}
     is_vector_env = True
 
     def __init__(self, cfg, render_mode=None, **kwargs):
@@ -250,6 +251,9 @@ class ManagerBasedRLEnv:
         self.physics_dt = cfg.sim.dt
         self.max_episode_length_s = cfg.episode_length_s
         self.max_episode_length = math.ceil(cfg.episode_length_s / self.step_dt)
+        self.metadata = dict(type(self).metadata, render_fps=1.0 / self.step_dt)
+        self._viewers = {}          # resolution -> viewer.Viewer, made on the first frame
+        self._frame_hooks = []      # called wherever common_step_counter advances by one step (video.RecordVideo)
         self.action_manager = ActionManager(self)
         self.command_manager = CommandManager(self)
         self.observation_manager = ObservationManager(self)
@@ -345,6 +349,7 @@ class ManagerBasedRLEnv:
         obs, rew, terminated, truncated = b.step(action)
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
+        self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
         # curriculum: evaluated inside _reset_idx in IsaacLab, i.e. on steps where >= 1 env resets; every built-in
@@ -380,6 +385,7 @@ class ManagerBasedRLEnv:
             self.action_manager.prev_action = a
             self.common_step_counter += 1
             self._sim_step_counter += self.cfg.decimation
+            self._run_frame_hooks()
             if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
                 if bool(storage.dones[k].any()):
                     for name, term in self._flat.curriculum:
@@ -397,6 +403,7 @@ class ManagerBasedRLEnv:
                   storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
+        self._run_frame_hooks()
         if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
             if bool(storage.dones[k].any()):
                 for name, term in self._flat.curriculum:
@@ -584,7 +591,56 @@ class ManagerBasedRLEnv:
         return m
 
     def render(self):
-        return None
+        """render_mode "rgb_array": the viewer camera's frame of the current state, np.uint8 [H, W, 3] (cfg.viewer: eye -> lookat
+        at `resolution`); None for render_mode None or "human" (no GUI), as IsaacLab without one.  Reads the state only."""
+        if self.render_mode != "rgb_array":
+            return None
+        return self.render_frame().cpu().numpy()
+
+    def render_frame(self, resolution=None, out=None) -> torch.Tensor:
+        """the viewer camera's frame as a device tensor uint8 [H, W, 3], whatever the render mode"""
+        from ..viewer import Viewer
+        v = self.cfg.viewer
+        res = tuple(int(x) for x in (resolution or v.resolution))
+        vw = self._viewers.get(res)
+        if vw is None:
+            vw = self._viewers[res] = Viewer(self.device, res)
+        eye, lookat = self.viewer_pose()
+        return vw.render(self._batch, eye, lookat, env_index=int(v.env_index), out=out)
+
+    def viewer_pose(self):
+        """(eye, lookat) of cfg.viewer in the world frame"""
+        v = self.cfg.viewer
+        eye, lookat = np.asarray(v.eye, np.float64), np.asarray(v.lookat, np.float64)
+        if v.origin_type == "asset_root":
+            if v.asset_name != "robot":
+                raise ValueError(f"viewer asset '{v.asset_name}': the scene has one articulation, 'robot'")
+            k = int(v.env_index)
+            if not 0 <= k < self.num_envs:
+                raise ValueError(f"viewer env_index {k} outside 0 .. {self.num_envs - 1}")
+            root = self._batch.state[A.S_PX:A.S_PZ + 1, k].double().cpu().numpy()
+            eye, lookat = eye + root, lookat + root
+        elif v.origin_type not in ("world", "env"):
+            raise ValueError(f"viewer origin_type '{v.origin_type}': one of 'world', 'env', 'asset_root'")
+        return eye, lookat
+
+    # ---- frame hooks (video recording) ----------------------------------------------------------------------------
+    def add_frame_hook(self, hook):
+        """hook(env) is called after every step that advances common_step_counter by one (step() and collect_step()); a hook
+        with `wants_frames(counter, n_steps)` also steers the runner off the fused K-step collectors while it wants frames"""
+        self._frame_hooks.append(hook)
+
+    def remove_frame_hook(self, hook):
+        if hook in self._frame_hooks:
+            self._frame_hooks.remove(hook)
+
+    def _run_frame_hooks(self):
+        for h in list(self._frame_hooks):
+            h(self)
+
+    def frames_due(self, n_steps: int) -> bool:
+        """does any frame hook want a frame of the next n_steps steps (counter values common_step_counter + 1 .. + n_steps)?"""
+        return any(getattr(h, "wants_frames", lambda c, n: True)(self.common_step_counter, int(n_steps)) for h in self._frame_hooks)
 
     def close(self):
         self._batch = None

@@ -168,8 +168,15 @@ class SimulationCfg:
 
 @configclass
 class ViewerCfg:
+    """isaaclab.envs.ViewerCfg: the world camera env.render() draws (wheeledlab_amd/viewer.py).  origin_type "world" and "env" are
+    the same here (every env origin is 0); with "asset_root" eye and lookat are offsets from the root position of env `env_index`
+    (translation only, as IsaacLab's viewport camera controller).  env_index is also drawn in the highlight colour."""
     eye: list = [7.5, 7.5, 7.5]
     lookat: list = [0.0, 0.0, 0.0]
+    resolution: tuple = (1280, 720)
+    origin_type: str = "world"
+    env_index: int = 0
+    asset_name: str = "robot"
 
 
 @configclass

@@ -328,12 +328,14 @@ class OnPolicyRunner:
         self.rank = torch.distributed.get_rank() if self.world > 1 else 0
         self.tot_timesteps, self.tot_time = 0, 0.0
         self.history: list[dict] = []
+        self.collection_paths: list[str] = []      # per iteration: "fused" or "stepwise"
 
     # ---- collection --------------------------------------------------------------------------------------
     def _collect_fused(self):
         self.env.unwrapped.rollout_policy(self.actor_critic.fused(), self.storage)
 
-    def _collect_stepwise(self, obs):
+    def _collect_stepwise(self, obs, frames: bool = False):
+        """frames: a frame hook wants frames of this rollout -- take a collector that advances the env one step at a time"""
         st, ac = self.storage, self.actor_critic
         # the policy step as one launch for any observation width (elevation 689, visual 3208): actor, sampling, log-prob
         # and the critic's value straight into the storage rows
@@ -343,7 +345,7 @@ class OnPolicyRunner:
             view.global_rows = st.n_envs * torch.distributed.get_world_size()   # kernel form as for the one-process batch
         base = self.env.unwrapped
         batch = getattr(base, "_batch", None)
-        if one_launch and hasattr(base, "can_collect_rollout") and base.can_collect_rollout():
+        if one_launch and not frames and hasattr(base, "can_collect_rollout") and base.can_collect_rollout():
             # the whole loop as one launch per curriculum segment, then every row's value in one batched pass (the critic is
             # not needed to step)
             with torch.inference_mode():
@@ -425,10 +427,17 @@ class OnPolicyRunner:
         start_iter = self.current_learning_iteration
         for it in range(start_iter, start_iter + num_learning_iterations):
             t0 = time.time()
-            if self.fused:
+            # a video recorder on the env (video.RecordVideo) that wants frames of this rollout: the per-step collector, whose
+            # every step runs the env's frame hooks; otherwise the path is chosen as without a recorder
+            base = env.unwrapped
+            frames = bool(getattr(base, "_frame_hooks", None)) and base.frames_due(self.num_steps_per_env)
+            if self.fused and not frames:
                 self._collect_fused()
             else:
-                obs = self._collect_stepwise(obs)
+                if self.fused:
+                    obs, _ = env.get_observations()      # the fused collector keeps the env's observation, not this loop's
+                obs = self._collect_stepwise(obs, frames)
+            self.collection_paths.append("stepwise" if (frames or not self.fused) else "fused")
             st = self.storage
             # book keeping of finished episodes (runner :88-98 does it per step with a host sync each): here the whole
             # rollout at once with cumulative sums, one device->host copy of the finished episodes' returns / lengths
