@@ -35,7 +35,7 @@ def _render(viewer, batch, eye, lookat, env_index=0):
     return rgb.cpu().numpy(), depth.cpu().numpy(), ids.cpu().numpy()
 
 
-def _reference(viewer, batch, eye, lookat, env_index=0):
+def _reference(viewer, batch, eye, lookat, env_index=0, explain=False):
     p = viewer.params(batch, eye, lookat, env_index)
     pos, quat = _poses(batch)
     hf = None
@@ -44,7 +44,7 @@ def _reference(viewer, batch, eye, lookat, env_index=0):
     trav = None
     if getattr(batch, "_map", None) is not None:
         trav = (batch.trav_map.cpu().numpy(), float(batch._map.row_spacing), float(batch._map.col_spacing))
-    return VR.render(p, pos, quat, hf, trav)
+    return VR.acceptable(p, pos, quat, hf, trav) if explain else VR.render(p, pos, quat, hf, trav)
 
 
 def _check(got, want, what, min_ids=0.995, max_bad=2e-3):
@@ -53,6 +53,13 @@ def _check(got, want, what, min_ids=0.995, max_bad=2e-3):
     assert c["id_match"] >= min_ids, (what, c)
     assert c["depth_bad"] <= max_bad * c["n"] and c["colour_bad"] <= max_bad * c["n"], (what, c)
     return c
+
+
+def _check_explained(got, viewer, batch, eye, lookat, what, env_index=0):
+    """the bounds of _check, and every pixel explained by the float64 reference's own state (viewer_reference.check_explained)"""
+    acc = _reference(viewer, batch, eye, lookat, env_index, explain=True)
+    _check(got, acc["nominal"], what)
+    return VR.check_explained(got, acc, what)
 
 
 def _elev(n, field=None):
@@ -82,7 +89,7 @@ def test_terrain_depth_matches_depth_oracle_at_full_resolution():
     bad, err = DC.mismatch(depth, want, p.far_clip)
     print(f"viewer terrain depth: grazing {int(bad.sum())} of {bad.size}, p99.9 err {np.quantile(err, 0.999):.2e}")
     assert bad.mean() < 1e-4 and np.quantile(err, 0.999) < 1e-4
-    _check((rgb, depth, ids), _reference(v, b, eye, lookat), "terrain")
+    _check_explained((rgb, depth, ids), v, b, eye, lookat, "terrain")
 
 
 @pytest.mark.parametrize("mapped", [False, True])
@@ -94,7 +101,7 @@ def test_plane_matches_reference(mapped):
     v = Viewer(DEV, (640, 360))
     eye, lookat = ((40.0, 0.0, 45.0), (0.0, 0.0, -3.0)) if mapped else ((4.0, -4.0, 4.0), (0.0, 0.0, 0.0))
     got = _render(v, b, eye, lookat)
-    _check(got, _reference(v, b, eye, lookat), f"plane mapped={mapped}")
+    _check_explained(got, v, b, eye, lookat, f"plane mapped={mapped}")
     assert (got[2] >= 0).any() and (got[2] == -1).any()      # cars and ground both in the frame
 
 
@@ -106,7 +113,7 @@ def test_cars_on_terrain_match_reference(eye):
     _set_poses(b, pos, quat)
     v = Viewer(DEV, (320, 180))
     got = _render(v, b, eye, (0.0, 0.0, 0.0))
-    _check(got, _reference(v, b, eye, (0.0, 0.0, 0.0)), f"cars {eye}")
+    _check_explained(got, v, b, eye, (0.0, 0.0, 0.0), f"cars {eye}")
     assert (got[2] >= 0).sum() > 100
 
 
@@ -119,7 +126,7 @@ def test_cars_after_physics_match_reference():
     v = Viewer(DEV, (320, 180))
     for eye in ((20.0, -20.0, 20.0), (8.0, -8.0, 6.0)):
         got = _render(v, b, eye, (0.0, 0.0, 0.0))
-        _check(got, _reference(v, b, eye, (0.0, 0.0, 0.0)), f"after physics {eye}")
+        _check_explained(got, v, b, eye, (0.0, 0.0, 0.0), f"after physics {eye}")
 
 
 def test_crowded_tiles_and_near_cars_are_complete():
@@ -140,7 +147,7 @@ def test_crowded_tiles_and_near_cars_are_complete():
     v = Viewer(DEV, (320, 180))
     for eye, lookat in (((25.0, -25.0, 20.0), (0.0, 0.0, 0.0)), ((1.2, -1.2, 0.8), (0.0, 0.0, 0.0))):
         got = _render(v, b, eye, lookat)
-        _check(got, _reference(v, b, eye, lookat), f"crowded {eye}")
+        _check_explained(got, v, b, eye, lookat, f"crowded {eye}")
         assert len(np.unique(got[2][got[2] >= 0])) > 20
 
 
