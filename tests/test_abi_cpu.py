@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads, exports every symbol include/wheeledlab_amd.h
 declares, the ctypes structs match the header's layout, and the product's default parameters equal the oracle's."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -109,6 +110,8 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert dep(C.byref(vp), C.byref(good_b), C.byref(A.WlHeightField(base, 1, 16, 0.0, 0.0, 0.5, 0.0, 2.0 ** -13)), base, 10.0, base, None) == -1
     assert dep(C.byref(vp), C.byref(good_b), C.byref(A.WlHeightField(base, 16, 16, 0.0, 0.0, 0.0, 0.0, 2.0 ** -13)), base, 10.0, base, None) == -1   # cell 0
     assert dep(C.byref(vp), C.byref(good_b), C.byref(A.WlHeightField(base, 16, 16, 0.0, 0.0, 0.5, 0.0, 0.0)), base, 10.0, base, None) == -1   # z_scale 0
+    assert dep(C.byref(vp), C.byref(good_b), C.byref(A.WlHeightField(base, 16, 16, 0.0, 0.0, math.inf, 0.0, 2.0 ** -13)), base, 10.0, base, None) == -1   # cell inf
+    assert lib.wl_heightfield_build_pyramid(C.byref(A.WlHeightField(base, 16, 16, 0.0, 0.0, math.inf, 0.0, 2.0 ** -13)), base, None) == -1
     assert lib.wl_heightfield_build_pyramid(C.byref(A.WlHeightField(None, 16, 16, 0.0, 0.0, 0.5, 0.0, 2.0 ** -13)), base, None) == -1
     assert lib.wl_heightfield_build_pyramid(C.byref(hf), None, None) == -1
 
@@ -149,6 +152,8 @@ def test_layout_of_task_structs_and_misuse_codes(tmp_path):
     assert lib.wl_elev_step(C.byref(ep), C.byref(good), None, base, C.byref(out), 0, 0, None) == -1      # no heightfield
     no_scale = A.WlHeightField(base, 8, 8, 0.0, 0.0, 1.0, 0.0, 0.0)
     assert lib.wl_elev_step(C.byref(ep), C.byref(good), C.byref(no_scale), base, C.byref(out), 0, 0, None) == -1      # z_scale 0
+    inf_cell = A.WlHeightField(base, 8, 8, 0.0, 0.0, math.inf, 0.0, 2.0 ** -13, base)
+    assert lib.wl_elev_step(C.byref(ep), C.byref(good), C.byref(inf_cell), base, C.byref(out), 0, 0, None) == -1      # cell inf
     # persistent elevation collector: observation rows k + 1 must be where the policy of step k + 1 reads them; quad form only
     hfb = A.WlHeightField(base, 8, 8, 0.0, 0.0, 1.0, 0.0, 2.0 ** -13)
     net = lambda o: A.WlMlp(base, base, base, base, base, base, A.ELEV_OBS_DIM, o, 64, A.ACT_ELU)
@@ -171,6 +176,18 @@ def test_layout_of_task_structs_and_misuse_codes(tmp_path):
     assert vr(C.byref(vp), C.byref(good), C.byref(tm), base, C.byref(out), 0, 0, 2, 0, 0, None) == -1
     ring = A.WlEnvBuffers(stride=128, n_envs=100, env_offset=0, metrics_slots=2, **ok_bufs)
     assert vr(C.byref(vp), C.byref(ring), C.byref(tm), base, C.byref(out), 100 * A.VIS_OBS_DIM, 100, 4, 0, 0, None) == -1   # ring slot aliasing
+    # maps the camera cannot index (24-bit multiplies, a 32-bit buffer resource): refused by every visual entry point
+    for big in (A.WlTravMap(base, base, 1 << 23, 2, 10, 0.5, 0.5), A.WlTravMap(base, base, 50000, 50000, 10, 0.5, 0.5)):
+        assert lib.wl_visual_step(C.byref(vp), C.byref(good), C.byref(big), base, C.byref(out), 0, 0, None) == -1
+        assert vr(C.byref(vp), C.byref(good), C.byref(big), base, C.byref(out), 100 * A.VIS_OBS_DIM, 100, 2, 0, 0, None) == -1
+    # the visual-depth task's contact sampler reads the row-pair table: it must be there, 4-byte aligned, and indexable
+    hf_args = lambda nx, ny, cell, pair: A.WlHeightField(base, nx, ny, 0.0, 0.0, cell, 0.0, 2.0 ** -13, pair)
+    for hfx, rc in ((hf_args(8, 8, 1.0, None), -1), (hf_args(8, 8, 1.0, base + 2), -3), (hf_args(1 << 23, 2, 1.0, base), -1),
+                    (hf_args(30000, 30000, 1.0, base), -1), (hf_args(8, 8, math.inf, base), -1)):
+        assert lib.wl_visual_step_hf(C.byref(vp), C.byref(good), C.byref(tm), C.byref(hfx), base, C.byref(out), 0, 0, None) == rc
+        assert lib.wl_visual_reset_hf(C.byref(vp), C.byref(good), C.byref(tm), C.byref(hfx), None, 0, 0, None) == rc
+    for hfx, rc in ((hf_args(8, 8, 1.0, base + 2), -3), (hf_args(1 << 23, 2, 1.0, base), -1), (hf_args(30000, 30000, 1.0, base), -1)):
+        assert lib.wl_elev_step(C.byref(ep), C.byref(good), C.byref(hfx), base, C.byref(out), 0, 0, None) == rc
 
 
 def test_missing_library_fails_loudly(tmp_path):

@@ -1,5 +1,5 @@
 """Round 6: in the fused elevation launch and in the quad-form visual step on a heightfield the block's RESET draws are made by an
-otherwise idle wavefront while the physics runs (wl_elev.hip FusedHooks::reset, wl_visual.hip HelperReset) and handed over through
+otherwise idle wavefront while the physics runs (wl_implicit_task.h ResetHelper, in wl_elev.hip and wl_visual.hip) and handed over through
 LDS.  The lane-form kernels draw the same values on the spot.  A reset pose does not depend on the physics, so with episodes of three
 steps -- a third of the batch resetting in every step -- the poses the two forms write for the resetting envs must agree bit for bit."""
 import pytest

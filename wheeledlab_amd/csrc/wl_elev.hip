@@ -39,10 +39,8 @@ __device__ unsigned long long wl_timeline[2048][16];
 #include "../../include/wheeledlab_amd.h"
 #include "wl_kernel_common.h"
 #include "wl_actor_dev.h"
-#include "wl_drift_terms.h"   // process_action / joint_targets (shared action term)
 #include "wl_rng.h"
-#include "wl_vehicle.h"
-#include "wl_heightfield.h"
+#include "wl_implicit_task.h"
 
 namespace {
 
@@ -221,7 +219,7 @@ WL_DEV ScanRay scan_request(const ScanFrame& f, const WlHeightField& hf, const S
     r.fu = c.fu, r.fv = c.fv, r.inside = c.inside;
     // a ray outside the field asks for whatever address its cell index wraps to: inside the buffer it reads a value nobody uses
     // (the ray is a miss), outside it the resource's bounds check returns 0 -- four clamps per ray saved.  24-bit multiply (full
-    // rate; v_mul_lo_u32 is a quarter-rate instruction): exact for every ray inside the field (check_elev: nx, ny < 2^23)
+    // rate; v_mul_lo_u32 is a quarter-rate instruction): exact for every ray inside the field (heightfield_args_ok: nx, ny < 2^23)
     const wl_u2 w = __builtin_amdgcn_raw_buffer_load_b64(sf.rsrc, (__mul24(c.j, hf.nx) + c.i) * 4, 0, 0);
     r.lo = w.x, r.hi = w.y;
     return r;
@@ -288,35 +286,7 @@ WL_DEV void scan_quad_store(float* __restrict__ row_map /* obs row + 13 */, int 
     else *dst = v;
 }
 
-// the dynamic rows of an env as the step needs them at its start (requested in one go, ahead of the parameter block)
-template <int LANES>
-struct ElevRows {
-    float mass, mu_s, mu_d, damp;
-    V3 pos, v, ww;
-    Quat q;
-    float wheel[LANES == 1 ? 4 : 1];
-    float th, om;
-};
-template <int LANES>
-WL_DEV ElevRows<LANES> load_elev_rows(const Rows& S, int e, int wid) {
-    ElevRows<LANES> r;
-    r.mass = S.ld(WL_S_MASS, e), r.mu_s = S.ld(WL_S_MU_S, e), r.mu_d = S.ld(WL_S_MU_D, e), r.damp = S.ld(WL_S_DAMP, e);
-    r.pos = ld3(S, WL_S_PX, e);
-    r.q = Quat{S.ld(WL_S_QW, e), S.ld(WL_S_QX, e), S.ld(WL_S_QY, e), S.ld(WL_S_QZ, e)};
-    r.v = ld3(S, WL_S_VX, e);
-    r.ww = ld3(S, WL_S_WX, e);
-    if constexpr (LANES == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r.wheel[i] = S.ld(WL_S_WHEEL_BL + i, e);
-    } else {
-        r.wheel[0] = S.ld(WL_S_WHEEL_BL + wid, e);
-    }
-    r.th = S.ld(WL_S_STEER_POS, e);
-    r.om = S.ld(WL_S_STEER_VEL, e);
-    return r;
-}
-
-// the bookkeeping rows of an env (episode length, goal command, episode sums) + the last action: with ElevRows everything a
+// the bookkeeping rows of an env (episode length, goal command, episode sums) + the last action: with VehRows everything a
 // persistent rollout carries in registers from step to step
 struct ElevBook {
     int ep_len;
@@ -325,29 +295,9 @@ struct ElevBook {
 };
 template <int LANES>
 WL_DEV void store_elev_state(const WlElevParams& p, const WlEnvBuffers& b, const Rows& S, int e, int wid, bool lead,
-                             const ElevRows<LANES>& r, const ElevBook& k) {
-    if constexpr (LANES == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) S.st(WL_S_WHEEL_BL + i, e, r.wheel[i]);
-    } else {
-        S.st(WL_S_WHEEL_BL + wid, e, r.wheel[0]);
-    }
+                             const VehRows<LANES>& r, const ElevBook& k) {
+    store_veh_rows<LANES>(S, e, wid, lead, r, k.act[0], k.act[1], p.log_episode_sums != 0, k.epsum);
     if (lead) {
-        st3(S, WL_S_PX, e, r.pos);
-        S.st(WL_S_QW, e, r.q.w);
-        S.st(WL_S_QX, e, r.q.x);
-        S.st(WL_S_QY, e, r.q.y);
-        S.st(WL_S_QZ, e, r.q.z);
-        st3(S, WL_S_VX, e, r.v);
-        st3(S, WL_S_WX, e, r.ww);
-        S.st(WL_S_STEER_POS, e, r.th);
-        S.st(WL_S_STEER_VEL, e, r.om);
-        S.st(WL_S_ACT0, e, k.act[0]);
-        S.st(WL_S_ACT1, e, k.act[1]);
-        if (p.log_episode_sums) {
-#pragma unroll
-            for (int i = 0; i < WL_ER_NTERMS; ++i) S.st(WL_S_EPSUM0 + i, e, k.epsum[i]);
-        }
         S.st(WL_S_CMD_BX, e, k.cb[0]);
         S.st(WL_S_CMD_BY, e, k.cb[1]);
         S.st(WL_S_TGT_X, e, k.tgt[0]);
@@ -376,47 +326,24 @@ WL_DEV ElevBook load_elev_book(const WlElevParams& p, const WlEnvBuffers& b, con
 // one env.step() of env `e` (all LANES lanes of the env take part): the body of the step kernels below.
 // PERSIST: the env's rows and bookkeeping live in `rows` / `*carry` across calls (persistent rollout): nothing is loaded
 // from or stored to the state matrix here, both are updated in place.
-// HOOKS (round 6): how the fused launch takes the step apart.  `pose(pos, q)` is called with the env's pose as the step leaves it
-// (AFTER a reset, if the env resets) as soon as that pose is known -- before the rewards are weighted, the outputs, the metrics and the
-// state rows are written -- so that the launch can hand the height scan its lattice frames and let the other wavefronts start while
-// this one finishes its bookkeeping.  `reset(...)` supplies a resetting env's draw: by default drawn here; the fused launch has an idle
-// wavefront draw all 16 envs' resets while the physics runs (the draw depends on (seed, env, step) and the terrain only) -- with a
-// reset somewhere in nearly every launch, the draw's ~0.9 us (two Philox blocks, a terrain sample's round trip, sin / cos) was on the
-// launch's critical path.
-struct NoStepHooks {
-    WL_DEV ElevReset reset(const WlElevParams& p, const HeightFieldGround& g, uint32_t gid, uint64_t step, uint64_t seed, int) const {
-        return draw_elev_reset(p, g, gid, step, seed);
-    }
-    WL_DEV void pose(const V3&, const Quat&) const {}
+// How the fused launch takes the step apart (round 6): `pose(pos, q)` is called with the env's pose as the step leaves it (AFTER a
+// reset, if the env resets) as soon as that pose is known -- before the rewards are weighted, the outputs, the metrics and the state
+// rows are written -- so that the launch can hand the height scan its lattice frames and let the other wavefronts start while this one
+// finishes its bookkeeping.  `reset_src` supplies a resetting env's draw (wl_implicit_task.h): drawn here by default, by the fused
+// launch's helper wavefront there.
+struct NoPose {
+    WL_DEV void operator()(const V3&, const Quat&) const {}
 };
-template <int LANES, bool PERSIST = false, class HOOKS = NoStepHooks>
+template <int LANES, bool PERSIST = false, class RESET = InlineReset, class POSE = NoPose>
 WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const WlEnvBuffers& b, const HeightFieldGround& ground,
-                              const float2 action, ElevRows<LANES>& rows, const WlStepOut& out, const uint64_t seed,
+                              const float2 action, VehRows<LANES>& rows, const WlStepOut& out, const uint64_t seed,
                               const uint64_t step, const Rows& S, const int e, const int wid, const bool lead, float* blk_metrics,
-                              ElevBook* carry = nullptr, float* prop2 = nullptr, const HOOKS& hooks = HOOKS()) {
+                              ElevBook* carry = nullptr, float* prop2 = nullptr, const RESET& reset_src = RESET(), const POSE& pose = POSE()) {
     const WlVehicleParams& vp = p.vehicle;
     const uint32_t gid = (uint32_t)(b.env_offset + e);
     float2 a = action;
-    float v_t, delta;
-    process_action(p.action, a.x, a.y, v_t, delta);
-    EnvConst ec;
-    joint_targets(p.action, v_t, delta, ec.steer_target, ec.wheel_target);
-    env_const_rows(ec, vp, vd, rows.mass, rows.mu_s, rows.mu_d, rows.damp);
-    if constexpr (LANES == 4) env_const_lane(ec, vp, vd, wid);
-    VehState s;
-    V3 pos = rows.pos;
-    s.q = rows.q;
-    s.v = rows.v;
-    V3 ww = rows.ww;
-#pragma unroll
-    for (int i = 0; i < (LANES == 1 ? 4 : 1); ++i) s.wheel[i] = rows.wheel[i];
-    s.th = rows.th;
-    s.om = rows.om;
-    {
-        const Mat3 R = mat_from_quat(s.q);
-        s.x = pos + vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
-        s.wb = mul_t(R, ww);
-    }
+    const EnvConst ec = veh_env_const<LANES>(p.action, vp, vd, a, rows, wid);
+    VehState s = veh_state<LANES>(vp, rows);
     // Bookkeeping rows (episode length, goal command, episode sums): the lane form fetches them after the physics loop --
     // it runs several wavefronts per SIMD and the registers are worth more than the latency; the quad form is one wavefront
     // per SIMD with registers to spare, so it requests them BEFORE the loop and finds them landed behind it.
@@ -446,86 +373,42 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
         tgt_in[2] = S.ld(WL_S_TGT_H, e);
         tgt_in[3] = S.ld(WL_S_CMD_TIMER, e);
     };
-    if constexpr (LANES == 4) fetch_bookkeeping();
-#ifndef WL_WHEEL_CORNER_CACHE
-#define WL_WHEEL_CORNER_CACHE 1
-#endif
-    if constexpr (LANES == 1 && WL_WHEEL_CORNER_CACHE) {      // lane form: each wheel's cell corners stay in registers between sub-steps
-        const HeightFieldGroundCached cached(ground);
-        vehicle_integrate<LANES, HeightFieldGroundCached, true, -1, true>(vp, vd, ec, s, cached, wid);
-    } else {
-        if constexpr (LANES == 4) WL_TL(1);
-        vehicle_integrate<LANES, HeightFieldGround, true, -1, true>(vp, vd, ec, s, ground, wid);
-        if constexpr (LANES == 4) WL_TL(2);
+    if constexpr (LANES == 4) {
+        fetch_bookkeeping();
+        WL_TL(1);
     }
+    veh_integrate<LANES>(vp, vd, ec, s, ground, wid);
+    if constexpr (LANES == 4) WL_TL(2);
     if constexpr (LANES != 4) {
         asm volatile("" ::: "memory");
         fetch_bookkeeping();
     }
-    const Mat3 R = mat_from_quat(s.q);
-    ww = mul(R, s.wb);
-    pos = s.x - vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
+    VehPost v = veh_post<LANES>(vp, s);
     int ep_len = ep_len_in + 1;
     const bool truncated = ep_len >= p.max_episode_length;
-    float wheel_sum;
-    if constexpr (LANES == 1) wheel_sum = s.wheel[0] + s.wheel[1] + s.wheel[2] + s.wheel[3];
-    else wheel_sum = quad_sum(s.wheel[0]);
-    const float chk = pos.x + pos.y + pos.z + s.q.w + s.q.x + s.q.y + s.q.z + s.v.x + s.v.y + s.v.z + ww.x + ww.y +
-                      ww.z + wheel_sum + s.th + s.om;
-    const bool finite = __builtin_isfinite(chk);
-    const V3 vb = mul_t(R, s.v);
     // terminations / rewards use the command as the PREVIOUS step's command update left it (IsaacLab step order)
     float cbx = cb_in[0], cby = cb_in[1];
-    const ElevTerms tm = elev_terms(p, pos, R.r2.z, vb, s.v, wheel_sum, cbx, cby, truncated);
-    const bool terminated = !finite || tm.flag[0] || tm.flag[1] || tm.flag[2] || tm.flag[3];
-    // the pose the step leaves behind first (a reset replaces it): whoever waits for it (hooks.pose) is served before the bookkeeping
+    const ElevTerms tm = elev_terms(p, v.pos, v.R.r2.z, v.vb, s.v, v.wheel_sum, cbx, cby, truncated);
+    const bool terminated = !v.finite || tm.flag[0] || tm.flag[1] || tm.flag[2] || tm.flag[3];
+    // the pose the step leaves behind first (a reset replaces it): whoever waits for it is served before the bookkeeping.  `pose` is
+    // called exactly once on every path -- unconditionally, with nothing above it that returns -- because the fused launch's holds the
+    // block's one s_barrier: keep it that way.
     const bool reset_now = terminated || truncated;
     ElevReset rd{};
     if (reset_now) {
-        rd = hooks.reset(p, ground, gid, step, seed, e);
-        pos = rd.pos;
+        rd = reset_src(e, [&] { return draw_elev_reset(p, ground, gid, step, seed); });
+        v.pos = rd.pos;
     }
-    hooks.pose(pos, reset_now ? rd.q : s.q);
+    pose(v.pos, reset_now ? rd.q : s.q);
     const float step_dt = p.sim_dt * (float)p.decimation;
-    float reward = 0.f;
     float epsum[WL_ER_NTERMS];
-#pragma unroll
-    for (int i = 0; i < WL_ER_NTERMS; ++i) {
-        const float w = p.weight[i];
-        const float c = (w != 0.f && finite) ? tm.t[i] * w * step_dt : 0.f;
-        reward += c;
-        epsum[i] = p.log_episode_sums ? epsum_in[i] + c : 0.f;
-    }
-    if (lead) {
-        out.reward[e] = reward;
-        out.terminated[e] = terminated ? 1 : 0;
-        out.truncated[e] = truncated ? 1 : 0;
-        if (out.dones) out.dones[e] = reset_now ? 1 : 0;
-    }
+    const float reward = weigh_rewards(p.weight, tm.t, v.finite, step_dt, p.log_episode_sums != 0, epsum_in, epsum);
+    if (lead) write_step_flags(out, e, reward, terminated, truncated);
     float a0 = a.x, a1 = a.y;
     float tgt_x = tgt_in[0], tgt_y = tgt_in[1], tgt_h = tgt_in[2], cmd_timer = tgt_in[3];
     if (reset_now) {
-        if (lead) {
-#pragma unroll
-        for (int i = 0; i < WL_ER_NTERMS; ++i) atomicAdd(&blk_metrics[WL_M_EPSUM0 + i], epsum[i]);
-        atomicAdd(&blk_metrics[WL_M_RESETS], 1.f);
-        if (truncated) atomicAdd(&blk_metrics[WL_M_TIMEOUTS], 1.f);
-#pragma unroll
-        for (int k = 0; k < WL_ET_NTERMS; ++k)
-            if (finite && tm.flag[k]) atomicAdd(&blk_metrics[WL_M_TERM0 + k], 1.f);
-        if (!finite) atomicAdd(&blk_metrics[WL_M_NONFINITE], 1.f);
-        atomicAdd(&blk_metrics[WL_M_EPLEN], (float)ep_len);
-        }
-#pragma unroll
-        for (int i = 0; i < WL_ER_NTERMS; ++i) epsum[i] = 0.f;
-        if (!finite) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s.wheel[i] = 0.f;
-            s.th = s.om = 0.f;
-        }
-        s.q = rd.q;
-        s.v = v3(rd.vx, rd.vy, 0.f);
-        ww = v3(0.f, 0.f, 0.f);
+        if (lead) episode_end_metrics(blk_metrics, epsum, truncated, v.finite, tm.flag, ep_len);
+        veh_reset(s, v, epsum, rd.pos, rd.q, v3(rd.vx, rd.vy, 0.f));
         tgt_x = rd.tgt_x;
         tgt_y = rd.tgt_y;
         tgt_h = rd.tgt_h;
@@ -545,14 +428,12 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
     {
         float c, sn;
         yaw_cs(s.q, c, sn);
-        const float dx = tgt_x - pos.x, dy = tgt_y - pos.y;
+        const float dx = tgt_x - v.pos.x, dy = tgt_y - v.pos.y;
         cbx = fmaf(c, dx, sn * dy);
         cby = fmaf(-sn, dx, c * dy);
     }
     {   // the env's new rows: kept (persistent rollout) or written back
-        rows.pos = pos, rows.q = s.q, rows.v = s.v, rows.ww = ww, rows.th = s.th, rows.om = s.om;
-#pragma unroll
-        for (int i = 0; i < (LANES == 1 ? 4 : 1); ++i) rows.wheel[i] = s.wheel[i];
+        veh_rows_from(rows, s, v);
         ElevBook k;
         k.ep_len = ep_len;
         k.cb[0] = cbx, k.cb[1] = cby;
@@ -565,11 +446,11 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
     }
     // proprioceptive part of the observation, from the post-reset state (all lanes of a quad take part)
     const Mat3 R2 = mat_from_quat(s.q);
-    write_elev_prop<LANES>(p, out.obs + (int64_t)e * WL_ELEV_OBS_DIM, pos, s.q, mul_t(R2, s.v), mul_t(R2, ww), cbx, cby, a0, a1,
+    write_elev_prop<LANES>(p, out.obs + (int64_t)e * WL_ELEV_OBS_DIM, v.pos, s.q, mul_t(R2, s.v), mul_t(R2, v.ww), cbx, cby, a0, a1,
                            wid, lead, prop2);
     float yc, ys;
     yaw_cs(s.q, yc, ys);
-    return ScanPose{pos.x, pos.y, pos.z, yc, ys};
+    return ScanPose{v.pos.x, v.pos.y, v.pos.z, yc, ys};
 }
 
 // (lane form: 110 VGPRs = 4 wavefronts per SIMD.  Squeezed to 96 / 80 registers for 5 / 6 wavefronts the kernel spills 60 / 128 bytes
@@ -599,7 +480,7 @@ __global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) e
     __syncthreads();
     const Rows S = make_rows(b.state, b.stride);
     if (e < b.n_envs) {
-        ElevRows<LANES> rows = load_elev_rows<LANES>(S, e, wid);
+        VehRows<LANES> rows = load_veh_rows<LANES>(S, e, wid);
         (void)elev_env_step<LANES>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics);
     }
     __syncthreads();
@@ -837,11 +718,10 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
     __shared__ ScanFrame frame[kFusedEnvs];
     __shared__ __attribute__((aligned(16))) float hbuf[POLICY ? 2 * 3 * kMlpTiles * 64 * 4 : 4];   // partial accumulators [net][share - 1][tile][lane][4]
     __shared__ float2 act_lds[kFusedEnvs];
-    __shared__ ElevReset reset_lds[kFusedEnvs];     // the block's 16 reset draws, by wavefront 1 while wavefront 0 integrates (!POLICY)
-    __shared__ int reset_ready;
+    __shared__ ResetHelper<ElevReset, kFusedEnvs> resets;     // the block's 16 reset draws, by wavefront 1 while wavefront 0 integrates (!POLICY)
     const int tid = threadIdx.x;
     if (tid < 64) WL_TL(0);
-    if (tid == 0) reset_ready = 0;
+    resets.init();
     if (tid < WL_M_COUNT) blk_metrics[tid] = 0.f;
     const int m_slot = b.metrics_slots > 1 ? (int)(step % (uint64_t)b.metrics_slots) : 0;
     if (b.metrics_slots > 1) clear_metric_slot(b, (m_slot + 1) % b.metrics_slots);
@@ -964,7 +844,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
                 a.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ar, e * 8, 4, 0));
             }
             const Rows S = make_rows(b.state, b.stride);
-            ElevRows<4> rows = load_elev_rows<4>(S, e, wid);
+            VehRows<4> rows = load_veh_rows<4>(S, e, wid);
             WlElevParams p;
             VehDerived vd;
             kernarg_vector_copy2(0, p, vd);
@@ -977,46 +857,34 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
                 // known (after a reset's draw) the lattice frames go to LDS and the other seven wavefronts start casting rays, while
                 // this one weights its rewards, writes outputs, metrics and state rows and then joins them for a smaller share
                 // (fused_scan_share).  Round 6, tools/fused_timeline.py: the bookkeeping was 1.1 us of every launch with seven
-                // wavefronts waiting behind it.  (Every block has an env, so wavefront 0 always gets here: one s_barrier per wavefront.)
-                struct FusedHooks {
-                    const WlElevParams& p;
-                    const HeightFieldGround& ground;
-                    ScanFrame* frame;
-                    const ElevReset* reset_lds;
-                    int* reset_ready;
-                    int tid, wid, e0;
-                    WL_DEV ElevReset reset(const WlElevParams& pp, const HeightFieldGround& g, uint32_t gid, uint64_t st, uint64_t sd, int e) const {
-                        if constexpr (POLICY) return draw_elev_reset(pp, g, gid, st, sd);      // (the collector's other wavefronts are busy with the nets)
-                        // wavefront 1 set the flag long ago (its draws take ~1.5 us, this is ~9 us into the launch): the loop is the guarantee
-                        while (__hip_atomic_load(reset_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
-                        return reset_lds[e - e0];
-                    }
-                    WL_DEV void pose(const V3& pos_out, const Quat& q_out) const {
-                        float yc, ys;
-                        yaw_cs(q_out, yc, ys);
-                        if (wid == 0) frame[tid >> 2] = scan_frame(p, ground, ScanPose{pos_out.x, pos_out.y, pos_out.z, yc, ys});
-                        WL_TL(3);
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    }
+                // wavefronts waiting behind it.  (Every block has an env, so wavefront 0 always gets here, and elev_env_step calls
+                // `pose` exactly once on every path: one s_barrier per wavefront.)
+                auto pose = [&](const V3& pos_out, const Quat& q_out) {
+                    float yc, ys;
+                    yaw_cs(q_out, yc, ys);
+                    if (wid == 0) frame[tid >> 2] = scan_frame(p, ground, ScanPose{pos_out.x, pos_out.y, pos_out.z, yc, ys});
+                    WL_TL(3);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 };
-                const FusedHooks hooks{p, ground, frame, reset_lds, &reset_ready, tid, wid, e0};
-                (void)elev_env_step<4, false, FusedHooks>(p, vd, b, ground, a, rows, out, seed, step, S, e, wid, wid == 0, blk_metrics, nullptr, nullptr, hooks);
+                // (the collector's other wavefronts are busy with the nets: it draws its resets inline)
+                const HelperReset<ElevReset, kFusedEnvs> reset_src{&resets, e0, !POLICY};
+                (void)elev_env_step<4>(p, vd, b, ground, a, rows, out, seed, step, S, e, wid, wid == 0, blk_metrics, nullptr, nullptr, reset_src, pose);
             }
         }
         WL_TL(4);
+        static_assert(WL_M_COUNT <= 64, "wavefront 0 flushes the block's metrics alone");
         if (tid < WL_M_COUNT) {
             const float m = blk_metrics[tid];
             if (m != 0.f) atomicAdd(metric_shard(b, m_slot) + tid, m);
         }
     } else {
         if constexpr (!POLICY) {
-            if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics (FusedHooks::reset)
+            if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics
                 const int j = tid - 64;
-                if (j < kFusedEnvs && e0 + j < b.n_envs) reset_lds[j] = draw_elev_reset(p_arg, ground, (uint32_t)(b.env_offset + e0 + j), step, seed);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (j == 0) __hip_atomic_store(&reset_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs,
+                               [&] { return draw_elev_reset(p_arg, ground, (uint32_t)(b.env_offset + e0 + j), step, seed); });
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1076,7 +944,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
 
 // K env.step()s in ONE launch with pre-staged actions [K][n][2] (open-loop rollouts: sampling-based planners, system
 // identification, the bench; quad form, n <= 32 768).  Block = 16 envs.  Wavefront 0 keeps their rows and bookkeeping in
-// registers across the K steps (ElevRows / ElevBook: no state round trip, no launch boundary per step) and leaves each
+// registers across the K steps (VehRows / ElevBook: no state round trip, no launch boundary per step) and leaves each
 // step's poses in one of two LDS buffers; wavefronts 1..7 cast the height rays of step k WHILE wavefront 0 already
 // integrates step k + 1 -- with actions that do not depend on the observations the scan is off the critical path.  One
 // s_barrier per step and wavefront: at barrier k wavefront 0 has finished step k, the others the scan of step k - 1.
@@ -1099,12 +967,12 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
         const int wid = tid & 3, e = e0 + (tid >> 2);
         const bool valid = e < b.n_envs;
         const Rows S = make_rows(b.state, b.stride);
-        ElevRows<4> rows;
+        VehRows<4> rows;
         ElevBook book;
         WlElevParams p;
         VehDerived vd;
         if (valid) {
-            rows = load_elev_rows<4>(S, e, wid);
+            rows = load_veh_rows<4>(S, e, wid);
             kernarg_vector_copy2(0, p, vd);
             keep_scalar_common(p, p_arg);
             vd.n_sub = vd_arg.n_sub;
@@ -1112,12 +980,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
         }
         for (int k = 0; k < n_steps; ++k) {
             if (valid) {
-                WlStepOut o = out;
-                o.obs += k * obs_step_stride;
-                o.reward += k * vec_step_stride;
-                o.terminated += k * vec_step_stride;
-                o.truncated += k * vec_step_stride;
-                if (o.dones) o.dones += k * vec_step_stride;
+                const WlStepOut o = step_out_at(out, k, obs_step_stride, vec_step_stride);
                 const float2 a = actions[(int64_t)k * b.n_envs + e];
                 const ScanPose sp = elev_env_step<4, true>(p, vd, b, ground, a, rows, o, seed, step0 + (uint64_t)k, S, e, wid, wid == 0,
                                                            blk_metrics, &book);
@@ -1221,7 +1084,7 @@ WL_DEV void tail_io(float* base, int lane, MlpTail& W) {
     for (int i = 0; i < kMlpHidSteps; ++i) col_io<PUT>(c, W.w3[i]);
 }
 template <bool PUT>
-WL_DEV void carry_io(float* base, int lane, ElevRows<4>& r, ElevBook& k) {
+WL_DEV void carry_io(float* base, int lane, VehRows<4>& r, ElevBook& k) {
     LdsColumn c{base, lane, 0};
     col_io<PUT>(c, r.mass), col_io<PUT>(c, r.mu_s), col_io<PUT>(c, r.mu_d), col_io<PUT>(c, r.damp);
     col_io<PUT>(c, r.pos.x), col_io<PUT>(c, r.pos.y), col_io<PUT>(c, r.pos.z);
@@ -1246,7 +1109,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
     float* obs_tile = col_lds;                                   // [16][kTilePitch]
     float* part_a = obs_tile + kFusedEnvs * kTilePitch;          // [8][4][64][4]
     float* tail_a = part_a + kPartFloats;                        // the actor's MlpTail, [85][64]
-    float* carry = tail_a + kTailFloats;                         // wavefront 0's ElevRows + ElevBook between steps, [words][64]
+    float* carry = tail_a + kTailFloats;                         // wavefront 0's VehRows + ElevBook between steps, [words][64]
     float* prop = carry + kCarryWords * 64;                      // [16][13]
     ScanFrame* frame = reinterpret_cast<ScanFrame*>(prop + kFusedEnvs * 13);   // [16] (7 floats each, 8 reserved)
     float2* act_lds = reinterpret_cast<float2*>(prop + kFusedEnvs * 13 + kFusedEnvs * 8);
@@ -1283,7 +1146,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
         load_tail(pio.actor, lane, Wa);
         tail_io<true>(tail_a, lane, Wa);
         if (phys) {
-            ElevRows<4> rows = load_elev_rows<4>(S, e, wid);
+            VehRows<4> rows = load_veh_rows<4>(S, e, wid);
             ElevBook book = load_elev_book<4>(p, b, S, e);
             carry_io<true>(carry, lane, rows, book);
         }
@@ -1346,14 +1209,9 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // act_lds: written by lanes 0..15, read by all 64 below
             __builtin_amdgcn_wave_barrier();
             if (phys) {
-                WlStepOut o = out;
-                o.obs += kn * D;
-                o.reward += kn;
-                o.terminated += kn;
-                o.truncated += kn;
-                if (o.dones) o.dones += kn;
+                const WlStepOut o = step_out_at(out, k, (int64_t)n * D, n);
                 const float2 a = act_lds[tid >> 2];
-                ElevRows<4> rows;
+                VehRows<4> rows;
                 ElevBook book;
                 carry_io<false>(carry, lane, rows, book);
                 const ScanPose sp = elev_env_step<4, true>(p, vd, b, ground, a, rows, o, seed, step, S, e, wid, wid == 0, blk_metrics, &book,
@@ -1404,7 +1262,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
     }
     if (wave == 0) {
         if (phys) {
-            ElevRows<4> rows;
+            VehRows<4> rows;
             ElevBook book;
             carry_io<false>(carry, lane, rows, book);
             store_elev_state<4>(p, b, S, e, wid, wid == 0, rows, book);
@@ -1489,17 +1347,8 @@ __global__ void __launch_bounds__(kBlock) elev_mdp_kernel(const WlElevParams p, 
 }
 
 int check_elev(const WlElevParams* p, const WlEnvBuffers* b, const WlHeightField* hf) {
-    if (!p || !b || !hf || !b->state || !b->episode_len || !b->metrics || !hf->height) return WL_EINVAL;
-    if (b->n_envs <= 0 || b->stride < b->n_envs || b->metrics_slots < 1) return WL_EINVAL;
-    if (b->stride % 64 != 0 || ((uintptr_t)b->state & 15u)) return WL_EALIGN;
-    if (b->stride * 4 * WL_S_COUNT > 0x7fffffffLL || (b->lanes != 0 && b->lanes != 1 && b->lanes != 4)) return WL_EINVAL;
-    if (!flags_ok(b)) return WL_EINVAL;
-    if (p->decimation <= 0 || p->vehicle.substeps <= 0 || !(p->sim_dt > 0.f)) return WL_EINVAL;
-    if (p->vehicle.implicit != 1 || !(p->vehicle.susp_fmax > 0.f)) return WL_EINVAL;   // these kernels step the linearly implicit integrator (wl_vehicle.h)
-    if (hf->nx < 2 || hf->ny < 2 || !(hf->cell > 0.f) || !(hf->z_scale > 0.f && hf->z_scale < INFINITY)) return WL_EINVAL;
-    if (!hf->pair || (int64_t)hf->nx * hf->ny * 4 > 0x7fffffffLL || hf->nx >= (1 << 23) || hf->ny >= (1 << 23)) return WL_EINVAL;   // wl_heightfield_pairs
-    if ((uintptr_t)hf->pair & 3u) return WL_EALIGN;
-    return WL_OK;
+    const int rc = check_implicit_env(p, b);
+    return rc != WL_OK ? rc : heightfield_args_ok(hf, HF_PAIRS);
 }
 
 // pair[j][i] = code[j][i] | code[min(j + 1, ny - 1)][i] << 16
@@ -1548,12 +1397,7 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
     const bool quad = use_quad(b) && (b->lanes == 4 || b->n_envs <= WL_ELEV_FUSED_MAX_ENVS);
     clear_error();
     for (int k = 0; k < n_steps; ++k) {
-        WlStepOut o = *out;
-        o.obs += k * obs_step_stride;
-        o.reward += k * vec_step_stride;
-        o.terminated += k * vec_step_stride;
-        o.truncated += k * vec_step_stride;
-        if (o.dones) o.dones += k * vec_step_stride;
+        const WlStepOut o = step_out_at(*out, k, obs_step_stride, vec_step_stride);
         const float2* a = (const float2*)(actions + (int64_t)k * b->n_envs * 2);
         if (quad) {   // step + scan in one launch
             elev_step_scan_kernel<false><<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k, PolicyIo{});

@@ -165,4 +165,18 @@ struct HeightFieldGroundCached {
 // hf_look_ahead_scan_stagers.jsonl.)
 inline HeightFieldGround make_ground(const WlHeightField* hf) { return HeightFieldGround{*hf, 1.f / hf->cell}; }
 
+// The host-side check of a heightfield argument: WL_OK or the code to refuse the call with.  Every user: the codes, at least 2 x 2
+// of them, finite positive cell and z_scale, and nx * ny * 4 bytes within a buffer resource's 32-bit range.  HF_PAIRS (the contact
+// samplers and the height scan): the row-pair table, 4-byte aligned, nx, ny < 2^23 (24-bit index multiplies).  HF_PYRAMID (the
+// depth / viewer walks over the bound pyramid): nx, ny <= 16385 (what the pyramid is laid out for).
+enum HfUse { HF_PAIRS, HF_PYRAMID };
+inline int heightfield_args_ok(const WlHeightField* hf, HfUse use) {
+    if (!hf || !hf->height || hf->nx < 2 || hf->ny < 2) return WL_EINVAL;
+    if (!(hf->cell > 0.f && hf->cell < INFINITY) || !(hf->z_scale > 0.f && hf->z_scale < INFINITY)) return WL_EINVAL;
+    if ((int64_t)hf->nx * hf->ny * 4 > 0x7fffffffLL) return WL_EINVAL;
+    if (use == HF_PYRAMID) return hf->nx <= 16385 && hf->ny <= 16385 ? WL_OK : WL_EINVAL;
+    if (!hf->pair || hf->nx >= (1 << 23) || hf->ny >= (1 << 23)) return WL_EINVAL;   // wl_heightfield_pairs
+    return ((uintptr_t)hf->pair & 3u) ? WL_EALIGN : WL_OK;
+}
+
 }  // namespace

@@ -240,9 +240,7 @@ int wl_viewer_render(const WlViewerParams* p, const WlEnvBuffers* b, const WlHei
         if (!finite_pos(p->box_half[k])) return WL_EINVAL;
     if (!finite_pos(p->wheel_radius) || !(p->ambient >= 0.f && p->ambient <= 1.f)) return WL_EINVAL;
     if (p->ground == WL_VIEWER_HEIGHTFIELD) {
-        if (!hf || !pyramid || !hf->height || hf->nx < 2 || hf->ny < 2 || hf->nx > 16385 || hf->ny > 16385 || !finite_pos(hf->cell) ||
-            !finite_pos(hf->z_scale))
-            return WL_EINVAL;
+        if (!pyramid || heightfield_args_ok(hf, HF_PYRAMID) != WL_OK) return WL_EINVAL;
     } else if (p->ground != WL_VIEWER_PLANE || hf || pyramid || !(p->plane_z == p->plane_z)) {
         return WL_EINVAL;
     }

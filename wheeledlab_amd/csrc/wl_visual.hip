@@ -11,10 +11,8 @@
 
 #include "../../include/wheeledlab_amd.h"
 #include "wl_kernel_common.h"
-#include "wl_drift_terms.h"
 #include "wl_rng.h"
-#include "wl_vehicle.h"
-#include "wl_heightfield.h"
+#include "wl_implicit_task.h"
 
 namespace {
 
@@ -83,10 +81,6 @@ struct CamPose {
     float px, py, pz, qw, qx, qy, qz, vx, vy, vz, wx, wy, wz, a0, a1;
 };
 
-// one env.step() of env e (lane form: one lane; quad form: the four lanes of a quad, wid = wheel).  Ground: the flat plane of the
-// reference's task, or a heightfield (the visual-depth extension task, BASELINE config 5: wheel contacts by bilinear gathers as in
-// the elevation task, reset poses lifted onto the terrain; `prop`: the env's 8 proprioceptive observation values are written
-// there -- the depth image next to them comes from wl_depth.hip)
 // a resetting env's new pose: the draw + (on a heightfield) the lift onto the terrain under the spawn cell
 template <class Ground>
 WL_DEV VisReset visual_reset_pose(const WlVisualParams& p, const WlTravMap& m, const Ground& ground, uint32_t gid, uint64_t step, uint64_t seed) {
@@ -99,168 +93,78 @@ WL_DEV VisReset visual_reset_pose(const WlVisualParams& p, const WlTravMap& m, c
     }
     return rd;
 }
-// RESET_SRC: where a resetting env's pose comes from.  By default drawn on the spot; the quad-form step kernel of the small batches has
-// a helper wavefront draw the block's resets while the physics runs (round 6): the draw is two or three DEPENDENT memory round trips
-// (Philox -> the spawn-cell table -> on a heightfield the terrain under the cell) behind the last sub-step, with mean episodes of ~50
-// steps every other block of 32 envs has one per step, and the launch is as long as its slowest block.
-struct InlineVisualReset {
-    template <class Ground>
-    WL_DEV VisReset operator()(const WlVisualParams& p, const WlTravMap& m, const Ground& ground, uint32_t gid, uint64_t step, uint64_t seed, int) const {
-        return visual_reset_pose(p, m, ground, gid, step, seed);
-    }
-};
-template <int LANES, class Ground = FlatGround, class RESET_SRC = InlineVisualReset>
+// one env.step() of env e (lane form: one lane; quad form: the four lanes of a quad, wid = wheel).  Ground: the flat plane of the
+// reference's task, or a heightfield (the visual-depth extension task, BASELINE config 5: wheel contacts by bilinear gathers as in
+// the elevation task, reset poses lifted onto the terrain; `prop`: the env's 8 proprioceptive observation values are written
+// there -- the depth image next to them comes from wl_depth.hip).  `rows` are the env's rows as loaded; they leave as stored.
+// RESET_SRC: where a resetting env's pose comes from (wl_implicit_task.h).  By default drawn on the spot; the quad-form step kernel of
+// the small batches on a heightfield has a helper wavefront draw the block's resets while the physics runs (round 6): the draw is two
+// or three DEPENDENT memory round trips (Philox -> the spawn-cell table -> on a heightfield the terrain under the cell) behind the last
+// sub-step, with mean episodes of ~50 steps every other block of 32 envs has one per step, and the launch is as long as its slowest block.
+template <int LANES, class Ground = FlatGround, class RESET_SRC = InlineReset>
 WL_DEV CamPose visual_env_step(const WlVisualParams& p, const VehDerived& vd, const WlEnvBuffers& b, const WlTravMap& m, float2 a,
-                               const WlStepOut& out, const uint64_t seed, const uint64_t step, const Rows& S, const int e, const int wid,
-                               const bool lead, float* blk_metrics, const Ground ground = Ground{}, float* __restrict__ prop = nullptr,
-                               const RESET_SRC& reset_src = RESET_SRC()) {
+                               VehRows<LANES>& rows, const WlStepOut& out, const uint64_t seed, const uint64_t step, const Rows& S,
+                               const int e, const int wid, const bool lead, float* blk_metrics, const Ground ground = Ground{},
+                               float* __restrict__ prop = nullptr, const RESET_SRC& reset_src = RESET_SRC()) {
     const WlVehicleParams& vp = p.vehicle;
-    {
-        const uint32_t gid = (uint32_t)(b.env_offset + e);
-        float v_t, delta;
-        process_action(p.action, a.x, a.y, v_t, delta);
-        EnvConst ec;
-        joint_targets(p.action, v_t, delta, ec.steer_target, ec.wheel_target);
-        env_const_rows(ec, vp, vd, S.ld(WL_S_MASS, e), S.ld(WL_S_MU_S, e), S.ld(WL_S_MU_D, e), S.ld(WL_S_DAMP, e));
-        if constexpr (LANES == 4) env_const_lane(ec, vp, vd, wid);
-        VehState s;
-        V3 pos = ld3(S, WL_S_PX, e);
-        s.q = Quat{S.ld(WL_S_QW, e), S.ld(WL_S_QX, e), S.ld(WL_S_QY, e), S.ld(WL_S_QZ, e)};
-        s.v = ld3(S, WL_S_VX, e);
-        V3 ww = ld3(S, WL_S_WX, e);
-        if constexpr (LANES == 1) {
+    const uint32_t gid = (uint32_t)(b.env_offset + e);
+    const EnvConst ec = veh_env_const<LANES>(p.action, vp, vd, a, rows, wid);
+    VehState s = veh_state<LANES>(vp, rows);
+    // bookkeeping rows: the quad form (one wavefront per SIMD, registers to spare) requests them BEFORE the physics loop
+    // and finds them landed behind it; the lane form fetches them after it (registers are worth more there)
+    int ep_len_in = 0;
+    float epsum_in[WL_VR_NTERMS];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) s.wheel[i] = S.ld(WL_S_WHEEL_BL + i, e);
-        } else {
-            s.wheel[0] = S.ld(WL_S_WHEEL_BL + wid, e);
-        }
-        s.th = S.ld(WL_S_STEER_POS, e);
-        s.om = S.ld(WL_S_STEER_VEL, e);
-        {
-            const Mat3 R = mat_from_quat(s.q);
-            s.x = pos + vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
-            s.wb = mul_t(R, ww);
-        }
-        // bookkeeping rows: the quad form (one wavefront per SIMD, registers to spare) requests them BEFORE the physics loop
-        // and finds them landed behind it; the lane form fetches them after it (registers are worth more there)
-        int ep_len_in = 0;
-        float epsum_in[WL_VR_NTERMS];
+    for (int i = 0; i < WL_VR_NTERMS; ++i) epsum_in[i] = 0.f;
+    auto fetch_bookkeeping = [&]() {
+        ep_len_in = b.episode_len[e];
+        if (p.log_episode_sums) {
 #pragma unroll
-        for (int i = 0; i < WL_VR_NTERMS; ++i) epsum_in[i] = 0.f;
-        auto fetch_bookkeeping = [&]() {
-            ep_len_in = b.episode_len[e];
-            if (p.log_episode_sums) {
-#pragma unroll
-                for (int i = 0; i < WL_VR_NTERMS; ++i) epsum_in[i] = S.ld(WL_S_EPSUM0 + i, e);
-            }
-        };
-        if constexpr (LANES == 4) fetch_bookkeeping();
-#ifndef WL_WHEEL_CORNER_CACHE
-#define WL_WHEEL_CORNER_CACHE 1
-#endif
-        if constexpr (LANES == 1 && !Ground::kFlat && WL_WHEEL_CORNER_CACHE) {   // lane form on a heightfield: see HeightFieldGroundCached
-            const HeightFieldGroundCached cached(ground);
-            vehicle_integrate<LANES, HeightFieldGroundCached, true, -1, true>(vp, vd, ec, s, cached, wid);
-        } else {
-            vehicle_integrate<LANES, Ground, true, -1, true>(vp, vd, ec, s, ground, wid);
+            for (int i = 0; i < WL_VR_NTERMS; ++i) epsum_in[i] = S.ld(WL_S_EPSUM0 + i, e);
         }
-        if constexpr (LANES != 4) {
-            asm volatile("" ::: "memory");
-            fetch_bookkeeping();
-        }
-        const Mat3 R = mat_from_quat(s.q);
-        ww = mul(R, s.wb);
-        pos = s.x - vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
-        int ep_len = ep_len_in + 1;
-        const bool truncated = ep_len >= p.max_episode_length;
-        float wheel_sum;
-        if constexpr (LANES == 1) wheel_sum = s.wheel[0] + s.wheel[1] + s.wheel[2] + s.wheel[3];
-        else wheel_sum = quad_sum(s.wheel[0]);
-        const float chk = pos.x + pos.y + pos.z + s.q.w + s.q.x + s.q.y + s.q.z + s.v.x + s.v.y + s.v.z + ww.x + ww.y +
-                          ww.z + wheel_sum + s.th + s.om;
-        const bool finite = __builtin_isfinite(chk);
-        const bool oom = finite && out_of_map(m, pos.x, pos.y);
-        const bool terminated = !finite || oom;
-        const V3 vb = mul_t(R, s.v);
-        float t[WL_VR_NTERMS];
-        t[WL_VR_TRAVERSABLE] = finite ? (traversable(m, pos.x, pos.y) ? 1.f : -1.f) : 0.f;   // :309-312
-        t[WL_VR_FORWARD_VEL] = vb.x;                                                          // :370-371
-        const float step_dt = p.sim_dt * (float)p.decimation;
-        float reward = 0.f;
-        float epsum[WL_VR_NTERMS];
-#pragma unroll
-        for (int i = 0; i < WL_VR_NTERMS; ++i) {
-            const float w = p.weight[i];
-            const float c = (w != 0.f && finite) ? t[i] * w * step_dt : 0.f;
-            reward += c;
-            epsum[i] = p.log_episode_sums ? epsum_in[i] + c : 0.f;
-        }
-        if (lead) {
-            out.reward[e] = reward;
-            out.terminated[e] = terminated ? 1 : 0;
-            out.truncated[e] = truncated ? 1 : 0;
-            if (out.dones) out.dones[e] = (terminated || truncated) ? 1 : 0;
-        }
-        float a0 = a.x, a1 = a.y;
-        if (terminated || truncated) {
-            if (lead) {
-#pragma unroll
-            for (int i = 0; i < WL_VR_NTERMS; ++i) atomicAdd(&blk_metrics[WL_M_EPSUM0 + i], epsum[i]);
-            atomicAdd(&blk_metrics[WL_M_RESETS], 1.f);
-            if (truncated) atomicAdd(&blk_metrics[WL_M_TIMEOUTS], 1.f);
-            if (oom) atomicAdd(&blk_metrics[WL_M_TERM0], 1.f);
-            if (!finite) atomicAdd(&blk_metrics[WL_M_NONFINITE], 1.f);
-            atomicAdd(&blk_metrics[WL_M_EPLEN], (float)ep_len);
-            }
-#pragma unroll
-            for (int i = 0; i < WL_VR_NTERMS; ++i) epsum[i] = 0.f;
-            if (!finite) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) s.wheel[i] = 0.f;
-                s.th = s.om = 0.f;
-            }
-            const VisReset rd = reset_src(p, m, ground, gid, step, seed, e);
-            pos = rd.pos;
-            s.q = rd.q;
-            s.v = v3(0.f, 0.f, 0.f);
-            ww = v3(0.f, 0.f, 0.f);
-            ep_len = 0;
-            a0 = a1 = 0.f;
-        }
-        if constexpr (LANES == 1) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) S.st(WL_S_WHEEL_BL + i, e, s.wheel[i]);
-        } else {
-            S.st(WL_S_WHEEL_BL + wid, e, s.wheel[0]);
-        }
-        if (lead) {
-            st3(S, WL_S_PX, e, pos);
-            S.st(WL_S_QW, e, s.q.w);
-            S.st(WL_S_QX, e, s.q.x);
-            S.st(WL_S_QY, e, s.q.y);
-            S.st(WL_S_QZ, e, s.q.z);
-            st3(S, WL_S_VX, e, s.v);
-            st3(S, WL_S_WX, e, ww);
-            S.st(WL_S_STEER_POS, e, s.th);
-            S.st(WL_S_STEER_VEL, e, s.om);
-            S.st(WL_S_ACT0, e, a0);
-            S.st(WL_S_ACT1, e, a1);
-            if (p.log_episode_sums) {
-    #pragma unroll
-                for (int i = 0; i < WL_VR_NTERMS; ++i) S.st(WL_S_EPSUM0 + i, e, epsum[i]);
-            }
-            b.episode_len[e] = ep_len;
-            if (prop) {     // base_lin_vel | base_ang_vel | last_action (clipped) of the post-reset state
-                const Mat3 R2 = mat_from_quat(s.q);
-                const V3 vb2 = mul_t(R2, s.v), wb2 = mul_t(R2, ww);
-                prop[0] = vb2.x, prop[1] = vb2.y, prop[2] = vb2.z, prop[3] = wb2.x, prop[4] = wb2.y, prop[5] = wb2.z;
-                prop[6] = clampf(a0, -1.f, 1.f), prop[7] = clampf(a1, -1.f, 1.f);
-            }
-        }
-        return CamPose{pos.x, pos.y, pos.z, s.q.w, s.q.x, s.q.y, s.q.z, s.v.x, s.v.y, s.v.z, ww.x, ww.y, ww.z, a0, a1};
+    };
+    if constexpr (LANES == 4) fetch_bookkeeping();
+    veh_integrate<LANES>(vp, vd, ec, s, ground, wid);
+    if constexpr (LANES != 4) {
+        asm volatile("" ::: "memory");
+        fetch_bookkeeping();
     }
+    VehPost v = veh_post<LANES>(vp, s);
+    int ep_len = ep_len_in + 1;
+    const bool truncated = ep_len >= p.max_episode_length;
+    const bool oom[1] = {v.finite && out_of_map(m, v.pos.x, v.pos.y)};
+    const bool terminated = !v.finite || oom[0];
+    float t[WL_VR_NTERMS];
+    t[WL_VR_TRAVERSABLE] = v.finite ? (traversable(m, v.pos.x, v.pos.y) ? 1.f : -1.f) : 0.f;   // :309-312
+    t[WL_VR_FORWARD_VEL] = v.vb.x;                                                              // :370-371
+    float epsum[WL_VR_NTERMS];
+    const float reward = weigh_rewards(p.weight, t, v.finite, p.sim_dt * (float)p.decimation, p.log_episode_sums != 0, epsum_in, epsum);
+    if (lead) write_step_flags(out, e, reward, terminated, truncated);
+    float a0 = a.x, a1 = a.y;
+    if (terminated || truncated) {
+        if (lead) episode_end_metrics(blk_metrics, epsum, truncated, v.finite, oom, ep_len);
+        const VisReset rd = reset_src(e, [&] { return visual_reset_pose(p, m, ground, gid, step, seed); });
+        veh_reset(s, v, epsum, rd.pos, rd.q, v3(0.f, 0.f, 0.f));
+        ep_len = 0;
+        a0 = a1 = 0.f;
+    }
+    veh_rows_from(rows, s, v);
+    store_veh_rows<LANES>(S, e, wid, lead, rows, a0, a1, p.log_episode_sums != 0, epsum);
+    if (lead) {
+        b.episode_len[e] = ep_len;
+        if (prop) {     // base_lin_vel | base_ang_vel | last_action (clipped) of the post-reset state
+            const Mat3 R2 = mat_from_quat(s.q);
+            const V3 vb2 = mul_t(R2, s.v), wb2 = mul_t(R2, v.ww);
+            prop[0] = vb2.x, prop[1] = vb2.y, prop[2] = vb2.z, prop[3] = wb2.x, prop[4] = wb2.y, prop[5] = wb2.z;
+            prop[6] = clampf(a0, -1.f, 1.f), prop[7] = clampf(a1, -1.f, 1.f);
+        }
+    }
+    return CamPose{v.pos.x, v.pos.y, v.pos.z, s.q.w, s.q.x, s.q.y, s.q.z, s.v.x, s.v.y, s.v.z, v.ww.x, v.ww.y, v.ww.z, a0, a1};
 }
 
+// The visual-depth step's quad form at <= 8192 envs: QB = 128 physics threads + a helper wavefront that draws the block's resets
+// (on the plane the draw is one round trip shorter and the helper bought nothing: visual env.step 35.4 against 35.2 us, same box).
+constexpr int kHelperQB = 128, kHelperThreads = kHelperQB + 64;
 template <int LANES, int QB = kBlock /* quad form: threads per block (see drift_step_kernel) */, class Ground = FlatGround>
 __global__ void __launch_bounds__(kBlock) visual_step_kernel(const WlVisualParams p_arg, const VehDerived vd_arg, const WlEnvBuffers b,
                                                              const WlTravMap m, const float2* __restrict__ actions,
@@ -275,45 +179,32 @@ __global__ void __launch_bounds__(kBlock) visual_step_kernel(const WlVisualParam
         vd.n_sub = vd_arg.n_sub;
     }
     constexpr int kEnvs = (LANES == 4 ? QB : kBlock) / LANES;
-    // heightfield ground only: launched with QB + 64 threads, the last wavefront draws the block's resets (on the plane the draw is one
-    // round trip shorter and the helper bought nothing: visual env.step 35.4 against 35.2 us, same box)
-    constexpr bool kHelper = LANES == 4 && QB == 128 && !Ground::kFlat;
-    __shared__ VisReset reset_lds[kHelper ? kEnvs : 1];
-    __shared__ int reset_ready;
+    constexpr bool kHelper = LANES == 4 && QB == kHelperQB && !Ground::kFlat;
+    __shared__ ResetHelper<VisReset, kHelper ? kEnvs : 1> resets;
     const int wid = LANES == 1 ? 0 : (threadIdx.x & 3);
     const bool lead = LANES == 1 || wid == 0;
     const int e = blockIdx.x * kEnvs + threadIdx.x / LANES;
     if (threadIdx.x < WL_M_COUNT) blk_metrics[threadIdx.x] = 0.f;
-    if (threadIdx.x == 0) reset_ready = 0;
+    if constexpr (kHelper) resets.init();
     const int m_slot = b.metrics_slots > 1 ? (int)(step % (uint64_t)b.metrics_slots) : 0;
     if (b.metrics_slots > 1) clear_metric_slot(b, (m_slot + 1) % b.metrics_slots);
     __syncthreads();
     const Rows S = make_rows(b.state, b.stride);
+    // the helper's part: the wavefront behind the physics threads -- or, in a launch without it (block-uniform test), wavefront 0
+    // ahead of its physics: the same draws, and no second copy of them in the kernel
     if constexpr (kHelper) {
-        if (threadIdx.x >= QB) {
-            const int j = (int)threadIdx.x - QB, ej = blockIdx.x * kEnvs + j;
-            if (j < kEnvs && ej < b.n_envs) reset_lds[j] = visual_reset_pose(p_arg, m, ground, (uint32_t)(b.env_offset + ej), step, seed);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (j == 0) __hip_atomic_store(&reset_ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else if (e < b.n_envs) {
-            struct HelperReset {
-                const VisReset* reset_lds;
-                int* reset_ready;
-                int e0;
-                WL_DEV VisReset operator()(const WlVisualParams&, const WlTravMap&, const Ground&, uint32_t, uint64_t, uint64_t, int e) const {
-                    // set ~1 us into the launch, read ~8 us into it: the loop is the guarantee
-                    while (__hip_atomic_load(reset_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
-                    return reset_lds[e - e0];
-                }
-            };
-            const HelperReset hr{reset_lds, &reset_ready, (int)(blockIdx.x * kEnvs)};
-            visual_env_step<LANES, Ground, HelperReset>(p, vd, b, m, actions[e], out, seed, step, S, e, wid, lead, blk_metrics, ground,
-                                                        prop_stride > 0 ? out.obs + (int64_t)e * prop_stride + prop_offset : nullptr, hr);
+        const int helper0 = blockDim.x >= kHelperThreads ? QB : 0;
+        if ((unsigned)((int)threadIdx.x - helper0) < 64u) {
+            const int j = (int)threadIdx.x - helper0, ej = blockIdx.x * kEnvs + j;
+            resets.publish(j, j < kEnvs && ej < b.n_envs,
+                           [&] { return visual_reset_pose(p_arg, m, ground, (uint32_t)(b.env_offset + ej), step, seed); });
         }
-    } else {
-        if (e < b.n_envs)
-            visual_env_step<LANES, Ground>(p, vd, b, m, actions[e], out, seed, step, S, e, wid, lead, blk_metrics, ground,
-                                           prop_stride > 0 ? out.obs + (int64_t)e * prop_stride + prop_offset : nullptr);
+    }
+    if ((!kHelper || threadIdx.x < QB) && e < b.n_envs) {
+        VehRows<LANES> rows = load_veh_rows<LANES>(S, e, wid);
+        const HelperReset<VisReset, kHelper ? kEnvs : 1> reset_src{&resets, (int)(blockIdx.x * kEnvs), kHelper};
+        visual_env_step<LANES, Ground>(p, vd, b, m, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics, ground,
+                                       prop_stride > 0 ? out.obs + (int64_t)e * prop_stride + prop_offset : nullptr, reset_src);
     }
     __syncthreads();
     if (threadIdx.x < WL_M_COUNT) {
@@ -637,14 +528,10 @@ __global__ void __launch_bounds__(kPersistThreads) visual_rollout_persistent_ker
 #pragma unroll 1
         for (int k = 0; k < n_steps; ++k) {
             if (valid) {
-                WlStepOut o = out;
-                o.obs += k * obs_step_stride;
-                o.reward += k * vec_step_stride;
-                o.terminated += k * vec_step_stride;
-                o.truncated += k * vec_step_stride;
-                if (o.dones) o.dones += k * vec_step_stride;
+                const WlStepOut o = step_out_at(out, k, obs_step_stride, vec_step_stride);
                 const float2 a = actions[(int64_t)k * b.n_envs + e];
-                const CamPose cp = visual_env_step<4>(p, vd, b, m, a, o, seed, step0 + (uint64_t)k, S, e, wid, wid == 0, blk_metrics);
+                VehRows<4> rows = load_veh_rows<4>(S, e, wid);
+                const CamPose cp = visual_env_step<4>(p, vd, b, m, a, rows, o, seed, step0 + (uint64_t)k, S, e, wid, wid == 0, blk_metrics);
                 if (wid == 0) pose[k & 1][tid >> 2] = cp;
             }
             __syncthreads();   // barrier k: the poses of step k are published
@@ -692,13 +579,7 @@ __global__ void __launch_bounds__(kBlock) visual_reset_kernel(const WlVisualPara
     if (e >= b.n_envs) return;
     if (mask && !mask[e]) return;
     const Rows S = make_rows(b.state, b.stride);
-    VisReset rd = draw_visual_reset(p, m, (uint32_t)(b.env_offset + e), step, seed);
-    if constexpr (!Ground::kFlat) {
-        float zt;
-        V3 nt;
-        ground.sample(rd.pos.x, rd.pos.y, zt, nt);
-        rd.pos.z += zt;
-    }
+    const VisReset rd = visual_reset_pose(p, m, ground, (uint32_t)(b.env_offset + e), step, seed);
     st3(S, WL_S_PX, e, rd.pos);
     S.st(WL_S_QW, e, rd.q.w);
     S.st(WL_S_QX, e, rd.q.x);
@@ -730,13 +611,11 @@ __global__ void __launch_bounds__(kBlock) visual_mdp_kernel(const WlVisualParams
 }
 
 int check_visual(const WlVisualParams* p, const WlEnvBuffers* b, const WlTravMap* m) {
-    if (!p || !b || !m || !b->state || !b->episode_len || !b->metrics || !m->map || !m->cells) return WL_EINVAL;
-    if (b->n_envs <= 0 || b->stride < b->n_envs || b->metrics_slots < 1 || m->n_cells <= 0) return WL_EINVAL;
-    if (b->stride % 64 != 0 || ((uintptr_t)b->state & 15u)) return WL_EALIGN;
-    if (b->stride * 4 * WL_S_COUNT > 0x7fffffffLL || (b->lanes != 0 && b->lanes != 1 && b->lanes != 4)) return WL_EINVAL;
-    if (!flags_ok(b)) return WL_EINVAL;
-    if (p->decimation <= 0 || p->vehicle.substeps <= 0 || !(p->sim_dt > 0.f) || m->rows <= 0 || m->cols <= 0) return WL_EINVAL;
-    if (p->vehicle.implicit != 1 || !(p->vehicle.susp_fmax > 0.f)) return WL_EINVAL;   // these kernels step the linearly implicit integrator (wl_vehicle.h)
+    const int rc = check_implicit_env(p, b);
+    if (rc != WL_OK) return rc;
+    if (!m || !m->map || !m->cells || m->n_cells <= 0 || m->rows <= 0 || m->cols <= 0) return WL_EINVAL;
+    // the camera indexes the map by 24-bit multiplies and reads it through a buffer resource of rows * cols bytes
+    if (m->rows >= (1 << 23) || m->cols >= (1 << 23) || (int64_t)m->rows * m->cols > 0x7fffffffLL) return WL_EINVAL;
     return WL_OK;
 }
 
@@ -759,12 +638,7 @@ int wl_visual_rollout(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
     const bool quad = use_quad(b);
     clear_error();
     for (int k = 0; k < n_steps; ++k) {
-        WlStepOut o = *out;
-        o.obs += k * obs_step_stride;
-        o.reward += k * vec_step_stride;
-        o.terminated += k * vec_step_stride;
-        o.truncated += k * vec_step_stride;
-        if (o.dones) o.dones += k * vec_step_stride;
+        const WlStepOut o = step_out_at(*out, k, obs_step_stride, vec_step_stride);
         const float2* a = (const float2*)(actions + (int64_t)k * b->n_envs * 2);
         const uint64_t st = step0 + (uint64_t)k;
         const hipStream_t hs = (hipStream_t)stream;
@@ -834,8 +708,8 @@ int wl_visual_observe(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
 int wl_visual_step_hf(const WlVisualParams* p, const WlEnvBuffers* b, const WlTravMap* m, const WlHeightField* hf, const float* actions,
                       const WlStepOut* out, uint64_t seed, uint64_t step, void* stream) {
     int rc = check_visual(p, b, m);
+    if (rc == WL_OK) rc = heightfield_args_ok(hf, HF_PAIRS);   // pair: the contact sampler's table (wl_heightfield_pairs)
     if (rc != WL_OK) return rc;
-    if (!hf || !hf->height || !hf->pair || hf->nx < 2 || hf->ny < 2 || !(hf->cell > 0.f) || !(hf->z_scale > 0.f && hf->z_scale < INFINITY)) return WL_EINVAL;   // pair: the contact sampler's table (wl_heightfield_pairs)
     if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated) return WL_EINVAL;
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     const HeightFieldGround g = make_ground(hf);
@@ -845,7 +719,7 @@ int wl_visual_step_hf(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
     clear_error();
     if (use_quad(b)) {
         const int lanes = n * 4;
-        if (n <= 8192) visual_step_kernel<4, 128, HeightFieldGround><<<(lanes + 127) / 128, 128 + 64, 0, hs>>>(*p, vd, *b, *m, a, *out, seed, step, g, WL_VISDEPTH_OBS_DIM, WL_VISDEPTH_NPIX);   // + the helper wavefront
+        if (n <= 8192) visual_step_kernel<4, kHelperQB, HeightFieldGround><<<(lanes + kHelperQB - 1) / kHelperQB, kHelperThreads, 0, hs>>>(*p, vd, *b, *m, a, *out, seed, step, g, WL_VISDEPTH_OBS_DIM, WL_VISDEPTH_NPIX);
         else visual_step_kernel<4, kBlock, HeightFieldGround><<<grid_for(lanes), kBlock, 0, hs>>>(*p, vd, *b, *m, a, *out, seed, step, g, WL_VISDEPTH_OBS_DIM, WL_VISDEPTH_NPIX);
     } else {
         visual_step_kernel<1, kBlock, HeightFieldGround><<<grid_for(n), kBlock, 0, hs>>>(*p, vd, *b, *m, a, *out, seed, step, g, WL_VISDEPTH_OBS_DIM, WL_VISDEPTH_NPIX);
@@ -856,8 +730,8 @@ int wl_visual_step_hf(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
 int wl_visual_reset_hf(const WlVisualParams* p, const WlEnvBuffers* b, const WlTravMap* m, const WlHeightField* hf, const uint8_t* mask,
                        uint64_t seed, uint64_t step, void* stream) {
     int rc = check_visual(p, b, m);
+    if (rc == WL_OK) rc = heightfield_args_ok(hf, HF_PAIRS);   // pair: the contact sampler's table (wl_heightfield_pairs)
     if (rc != WL_OK) return rc;
-    if (!hf || !hf->height || !hf->pair || hf->nx < 2 || hf->ny < 2 || !(hf->cell > 0.f) || !(hf->z_scale > 0.f && hf->z_scale < INFINITY)) return WL_EINVAL;   // pair: the contact sampler's table (wl_heightfield_pairs)
     clear_error();
     visual_reset_kernel<HeightFieldGround><<<grid_for(b->n_envs), kBlock, 0, (hipStream_t)stream>>>(*p, *b, *m, mask, seed, step, make_ground(hf));
     return launch_status();
