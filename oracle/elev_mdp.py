@@ -50,7 +50,8 @@ def stuck(v_b, throttle_joint_vel, min_vel=0.02, wheel_spin_thr=5.0):
 def upright_penalty(quat, thresh_deg):
     """:217-222"""
     up = matrix_from_quat(quat)[:, 2, 2]
-    ang = np.rad2deg(np.arccos(np.clip(up, -1, 1))).astype(F)
+    # torch.rad2deg is one fp32 product by 180 / pi (numpy's rounds otherwise): at R33 = 0.5 the tilt is 60.000004, not 60
+    ang = (np.arccos(np.clip(up, -1, 1)).astype(F) * F(180.0 / np.pi)).astype(F)
     return np.where(ang > F(thresh_deg), ang - F(thresh_deg), F(0)).astype(F)
 
 
@@ -61,8 +62,15 @@ def upright_bool(quat, thresh_deg=60.0):
 
 def close_to_goal(pos, cmd, dist=0.5):
     """:268-273"""
-    d = f32(cmd)[:, :2] - f32(pos)[:, :2]
-    return np.sqrt((d * d).sum(-1)) < F(dist)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return _norm2(f32(cmd)[:, :2] - f32(pos)[:, :2]) < F(dist)
+
+
+def _norm2(d):
+    d = d.astype(np.float64)
+    # torch.norm of a 2-vector: fp32 fma(y, y, x * x), correctly rounded sqrt (float64 holds y * y exactly)
+    sq = (d[:, 1] * d[:, 1] + (d[:, 0] * d[:, 0]).astype(F)).astype(F)
+    return np.sqrt(sq.astype(np.float64)).astype(F)
 
 
 def root_height_below_minimum(pos, minimum_height=0.15):

@@ -163,7 +163,7 @@ def step(p, state, episode_len, hf, actions, seed, step_count, metrics=None, env
     t_low = E.root_height_below_minimum(pos, p.min_height)
     t_stuck = np.logical_and(np.minimum(v_b[:, 0], F(p.stuck_vel_cap)) < F(p.stuck_min_vel),
                              wheel.sum(-1) > F(p.stuck_wheel_spin))
-    t_roll = R[:, 2, 2] < F(p.upright_cos)
+    t_roll = R[:, 2, 2] <= F(p.upright_cos)   # the fp32 tie at cos 60 deg is rolled over (elev_mdp.upright_penalty)
     t_goal = E.close_to_goal(pos, cmd, p.goal_dist)
     terminated = t_low | t_stuck | t_roll | t_goal | ~finite
     with np.errstate(invalid="ignore", divide="ignore"):

@@ -86,9 +86,9 @@ def get_traversability(trav, xy, **kw):
 
 # ---- mdp terms (mushr_visual_env_cfg.py) ----
 
-def traversable_reward(trav, pos):
-    """:309-312"""
-    return np.where(get_traversability(trav, f32(pos)[:, :2]), F(1), F(-1)).astype(F)
+def traversable_reward(trav, pos, **kw):
+    """:309-312 (kw: the map geometry of get_map_id)"""
+    return np.where(get_traversability(trav, f32(pos)[:, :2], **kw), F(1), F(-1)).astype(F)
 
 
 def forward_vel(v_b):

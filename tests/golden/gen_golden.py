@@ -15,7 +15,8 @@ therefore "parity unpinned" -- see DESIGN.md).  Every arithmetic line that the r
 executed from the reference's files.
 
 Usage:  WL_REFERENCE_SRC=<reference>/source PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py
-        (WL_GOLDEN_OUT=<dir> writes there instead; WL_GOLDEN_SEED_OFFSET=1000 made tests/golden_seed1000/, 2024 tests/golden/seed2024/)
+        (WL_GOLDEN_OUT=<dir> writes there instead; WL_GOLDEN_SEED_OFFSET=1000 made tests/golden_seed1000/, 2024 tests/golden/seed2024/;
+         the *_edges files of offset 1000 other than drift's live in tests/golden/seed1000/: binary vectors stay under tests/golden/)
 """
 import sys
 
@@ -790,6 +791,260 @@ def gen_visual_unwired(V, st, env):
     np.savez_compressed(os.path.join(OUT, "visual_unwired.npz"), **out)
 
 
+# --------------------------------------------------------------------------------------------------
+# 4. edge sets: every threshold of the elevation and visual terms, hit exactly and straddled
+# --------------------------------------------------------------------------------------------------
+
+
+def around(t):
+    """the fp32 values at and next to a threshold t: t, 1 and 2 ulps either side, t (1 +- 1e-6), t +- 1e-4"""
+    t32 = np.float32(t)
+    up1 = np.nextafter(t32, np.float32(np.inf))
+    dn1 = np.nextafter(t32, np.float32(-np.inf))
+    vals = [t32, up1, np.nextafter(up1, np.float32(np.inf)), dn1, np.nextafter(dn1, np.float32(-np.inf)),
+            np.float32(t * (1 + 1e-6)), np.float32(t * (1 - 1e-6)), np.float32(t + 1e-4), np.float32(t - 1e-4)]
+    return np.array(vals, np.float32)
+
+
+def _quat_for_r33(target, axis):
+    """a unit-ish fp32 quaternion about x (axis 1) or y (axis 2) whose R33 under matrix_from_quat is `target` exactly when one
+    exists a few ulps from the float64 rotation (else the closest found)"""
+    th = math.acos(min(max(float(target), -1.0), 1.0))
+    q0 = np.zeros(4, np.float32)
+    q0[0], q0[axis] = np.float32(math.cos(th / 2)), np.float32(math.sin(th / 2))
+    best, best_d = q0, None
+    for dw in range(-3, 4):
+        for dx in range(-48, 49):
+            q = q0.copy()
+            q[0] = q0[0] + np.float32(dw) * np.spacing(q0[0])
+            q[axis] = q0[axis] + np.float32(dx) * np.spacing(q0[axis])
+            r = float(matrix_from_quat(torch.from_numpy(q[None].copy()))[0, 2, 2])
+            d = abs(r - float(target))
+            if best_d is None or d < best_d:
+                best, best_d = q, d
+            if d == 0:
+                return q
+    return best
+
+
+def elevation_edge_state():
+    """one row per edge input (the rest of the row clear of every threshold); random filler follows the seed offset"""
+    rows = []   # (field overrides)
+
+    def add(**kw):
+        rows.append(kw)
+
+    for z in around(0.15):                                           # root_height_below_minimum
+        add(z=z)
+    for v in around(0.02):                                           # stuck: forward speed under min_vel, wheels spinning
+        add(vx=v, wheels=(2.0, 2.0, 2.0, 2.0))
+    for v in around(1.2):                                            # forward_vel's cap
+        add(vx=v, wheels=(2.0, 2.0, 2.0, 2.0))
+    for s in around(5.0):                                            # stuck: wheel sum over wheel_spin_thr
+        add(vx=0.0, wheels=(s, 0.0, 0.0, 0.0))
+        add(vx=0.0, wheels=(0.5 * s, 0.0, 0.0, 0.5 * s))
+    e = 2.0 ** -22                                                   # half an ulp of 5: sums that depend on the order
+    for w in ((5.0, e, e, 0.0), (e, e, 5.0, 0.0), (5.0, 0.0, e, e), (1e8, 5.0, -1e8, 0.0), (3.0, 1e8, 2.0, -1e8),
+              (2.5, 2.5, 1e-7, -1e-7), (4.0, 1.0, e, e), (1e8, -1e8, 5.0, 1e-7), (5.0, 3e-7, -3e-7, 0.0)):
+        add(vx=0.0, wheels=w)
+    for s in around(200.0):                                          # forward_wheel_spin's cap (unwired set)
+        add(vx=0.5, wheels=(0.25 * s, 0.25 * s, 0.25 * s, 0.25 * s))
+    for t in around(0.5):                                            # R33 at cos 60 deg
+        add(quat=_quat_for_r33(t, 1))
+        add(quat=_quat_for_r33(t, 2))
+    w = np.float32(math.sqrt(0.75))                                  # w * w rounds to 0.75: norm 1, R33 = 0.5 in every formula
+    for q in ((w, 0.5, 0, 0), (w, 0, -0.5, 0), (0.5, w, 0, 0)):
+        add(quat=np.array(q, np.float32))
+    for k in (-2, -1, 1, 2):                                         # x = 0.5 +- k ulp: R33 straddles 0.5 with the norm ~1
+        add(quat=np.array([w, np.float32(0.5) + np.float32(k) * np.float32(2.0 ** -24), 0, 0], np.float32))
+    ulp = np.float32(2.0 ** -23)
+    for k in (-4, -2, -1, 1, 2, 4):                                  # R33 near +-1 from quaternions of norm 1 +- k ulp
+        s = np.float32(1) + np.float32(k) * ulp
+        add(quat=np.array([s, 0, 0, 0], np.float32))
+        add(quat=np.array([0, s, 0, 0], np.float32))
+        add(quat=np.array([0, 0, s, 0], np.float32))
+        add(quat=np.array([0, 0.6 * s, 0.8 * s, 0], np.float32))
+        add(quat=np.array([0.8 * s, 0.6 * s, 0, 0], np.float32))
+        add(quat=np.array([s, 1e-4, 0, 0], np.float32))
+    for d in around(0.5):                                            # at_goal: along the axes, the diagonal, exact triples
+        for g in ((d, 0), (0, d), (-d, 0), (0, -d), (d * np.float32(math.sqrt(0.5)), d * np.float32(math.sqrt(0.5))),
+                  (np.float32(0.6) * d, np.float32(0.8) * d), (np.float32(-0.8) * d, np.float32(0.6) * d)):
+            add(pxy=(0.0, 0.0), goal=g)
+    for g in ((0.3, 0.4), (0.4, -0.3), (0.5, 0.0), (0.0, -0.5), (0.14, 0.48)):
+        add(pxy=(0.0, 0.0), goal=g)
+        add(pxy=(3.75, -12.5), goal=(3.75 + g[0], -12.5 + g[1]))     # dyadic positions: the subtraction is exact
+    for g in ((0.0, 0.0), (1e-20, 0.0), (1e-20, 1e-20), (3e-20, -4e-20), (1e20, 0.0), (1e20, 1e20), (-3e38, 3e38),
+              (np.nan, 0.0), (0.0, np.nan), (np.inf, 0.0), (-np.inf, 0.0), (0.0, np.inf), (np.inf, np.inf)):
+        add(pxy=(0.0, 0.0), goal=g)                                  # goal_progress_rate: 0/0, tiny, huge, non-finite
+    z0 = np.float32(0.19)
+    for t in around(0.1):                                            # higher_elevation: z - 0.19 at 0.1 (z = 0.29, exact subtraction)
+        add(z=np.float32(z0 + t), vx=0.5)
+    for k in range(-3, 4):
+        z = np.float32(0.29)
+        for _ in range(abs(k)):
+            z = np.nextafter(z, np.float32(np.sign(k) * np.inf))
+        add(z=z, vx=0.5)
+    for v in around(0.1):                                            # higher_elevation: forward speed over 0.1
+        add(z=0.5, vx=v)
+    for t in around(1.0):                                            # higher_elevation: the clip at 1
+        add(z=np.float32(z0 + t), vx=0.5)
+    for v in around(0.10):                                           # is_falling_penalty: vb.z over 0.10
+        add(vz=v)
+    n = len(rows) + 16                                               # + 16 random rows
+    st = make_state(n, 13)
+    rng = np.random.RandomState(14 + SEED_OFFSET)
+    st["pos"][:, 0] = rng.uniform(-19, 19, n)
+    st["pos"][:, 1] = rng.uniform(-19, 19, n)
+    st["pos"][:, 2] = rng.uniform(0.4, 0.9, n)
+    st["lin_vel_b"][:, 0] = rng.uniform(0.3, 1.0, n)
+    st["lin_vel_b"][:, 2] = rng.uniform(-0.05, 0.05, n)
+    yaw = rng.uniform(-3.14, 3.14, n)
+    st["quat"] = npy(quat_from_euler_xyz(torch.zeros(n), torch.zeros(n), torch.tensor(yaw, dtype=torch.float32)))
+    st["joint_vel"][:, 2:6] = rng.uniform(0.0, 1.0, (n, 4))
+    cmd = np.concatenate([rng.uniform(-19, 19, (n, 2)), np.zeros((n, 1)), rng.uniform(-3.14, 3.14, (n, 1))], -1).astype(np.float32)
+    cmd[:, :2] = np.where(np.hypot(cmd[:, 0] - st["pos"][:, 0], cmd[:, 1] - st["pos"][:, 1])[:, None] < 2.0, cmd[:, :2] + 5.0, cmd[:, :2])
+    for i, r in enumerate(rows):
+        if "z" in r:
+            st["pos"][i, 2] = r["z"]
+        if "vx" in r:
+            st["lin_vel_b"][i, 0] = r["vx"]
+        if "vz" in r:
+            st["lin_vel_b"][i, 2] = r["vz"]
+        if "wheels" in r:
+            st["joint_vel"][i, 2:6] = np.array(r["wheels"], np.float32)
+        if "quat" in r:
+            st["quat"][i] = r["quat"]
+        if "pxy" in r:
+            st["pos"][i, :2] = r["pxy"]
+        if "goal" in r:
+            cmd[i, :2] = r["goal"]
+    timed_out = rng.rand(n) < 0.5
+    timed_out[: len(rows)] = np.arange(len(rows)) % 2 == 0              # every edge family meets both
+    return st, cmd, timed_out
+
+
+def gen_elevation_edges(El):
+    st, cmd, timed_out = elevation_edge_state()
+    n = st["pos"].shape[0]
+    rng = np.random.RandomState(15 + SEED_OFFSET)
+    NH = 8                                                           # rows with a full ray grid: +-inf / nan hits among them
+    hits_z = (np.round(rng.uniform(-0.2, 1.5, (n, 676)) * 256) / 256).astype(np.float32)
+    hits_z[:NH, 0:8] = [np.inf, -np.inf, np.nan, 0.0, 20.0, -20.0, 1e30, -1e30]
+    hits_z[NH:] = hits_z[NH:, :1]
+    env = env_from_state(st)
+    env.commands["goal_pose"] = torch.tensor(cmd, dtype=torch.float32)
+    sensor = types.SimpleNamespace(data=types.SimpleNamespace(
+        pos_w=torch.tensor(np.concatenate([st["pos"][:, :2], st["pos"][:, 2:3] + 20.0], -1), dtype=torch.float32),
+        ray_hits_w=torch.tensor(np.concatenate([np.zeros((n, 676, 2), np.float32), hits_z[..., None]], -1), dtype=torch.float32)))
+    env.scene.sensors["height_scanner"] = sensor
+    res = dict(st)
+    res["command"] = cmd
+    res["timed_out"] = timed_out
+    res["sensor_pos_w"] = npy(sensor.data.pos_w)
+    res["ray_hits_z"] = hits_z
+    O = El.ElevationObsCfg.ConcatObs
+    T = El.ElevationTerminationsCfg
+    with np.errstate(all="ignore"):
+        res["world_height_map"] = npy(El.world_height_map(env, **O.elevation_map.params))
+        res["goal_relative_xyz"] = npy(El.goal_relative_xyz(env))
+        res["goal_progress_rate"] = npy(El.goal_progress_rate(env))
+    res["higher_elevation"] = npy(El.higher_elevation(env))
+    res["is_falling_penalty"] = npy(El.is_falling_penalty(env))
+    res["forward_vel"] = npy(El.forward_vel(env))
+    res["stuck"] = npy(El.stuck(env, **T.stuck.params))
+    res["upright_penalty"] = npy(El.upright_penalty(env, 60.0))
+    res["upright_tilt"] = npy(El.upright_penalty(env, 0.0))         # the reference's own arccos in degrees (0 where it is 0 or nan)
+    res["upright_r33"] = npy(matrix_from_quat(torch.from_numpy(st["quat"].copy()))[:, 2, 2])
+    res["upright_bool"] = npy(El.upright_bool(env, **T.rollover.params))
+    res["close_to_goal"] = npy(El.close_to_goal(env, **T.at_goal.params))
+    # isaaclab's root_height_below_minimum is not the reference's (stubbed): its published rule, pos.z < minimum_height
+    res["below_min_height"] = st["pos"][:, 2] < np.float32(T.cart_out_of_bounds.params["minimum_height"])
+    np.savez_compressed(os.path.join(OUT, "elevation_mdp_edges.npz"), **res)
+    out = dict(pos=st["pos"], quat=st["quat"], lin_vel_b=st["lin_vel_b"], ang_vel_b=st["ang_vel_b"], lin_vel_w=st["lin_vel_w"],
+               joint_vel=st["joint_vel"])
+    out["forward_wheel_spin"] = npy(El.forward_wheel_spin(env))
+    out["change_in_elevation"] = npy(El.change_in_elevation(env))
+    out["steep_penalty"] = npy(El.steep_penalty(env, 0.2))
+    out["yaw_change_onElev"] = npy(El.yaw_change_onElev(env, 0.5, 0.1))
+    out["roll_on_elev"] = npy(El.roll_on_elev(env, 0.1, 0.1))
+    out["ascending"] = npy(El.ascending(env))
+    out["low_vel_penalty"] = npy(El.low_vel_penalty(env, 0.1))
+    out["upright_penalty_30"] = npy(El.upright_penalty(env, 30.0))
+    np.savez_compressed(os.path.join(OUT, "elevation_unwired_edges.npz"), **out)
+
+
+# map geometries (rows, cols, row_spacing, col_spacing): the task's own, the spacing of the reference's create_geometry example,
+# unequal spacings, an odd size, and a non-square map (looked up only where the reference can index it)
+VIS_GEOMS = ((500, 500, 0.5, 0.5), (100, 100, 0.3, 0.3), (100, 100, 0.3, 0.5), (101, 101, 0.45, 0.45), (60, 90, 0.5, 0.25))
+
+
+def visual_edge_points(rows, cols, rs, cs, rng):
+    """points on and next to out_of_map's edges and the lookup's cell lines, in x and in y, plus the far field and non-finite"""
+    hw, hh = rows * rs / 2.0, cols * cs / 2.0
+    pts = []
+    for a in around(hw):                                             # x edges (y inside), y edges (x inside), corners
+        for sx in (-1, 1):
+            pts.append((sx * a, rng.uniform(-hh, hh) * 0.9))
+            pts.append((rng.uniform(-hw, hw) * 0.9, sx * np.float32(hh)))
+    for a in around(hh):
+        for sy in (-1, 1):
+            pts.append((rng.uniform(-hw, hw) * 0.9, sy * a))
+            pts.append((sy * np.float32(hw), sy * a))
+            pts.append((-sy * a * np.float32(hw / hh), sy * a))
+    # cell lines: (x + w/2 + rs/2) / rs integer  <=>  x = k rs - w/2 - rs/2
+    for k in (1, 2, rows // 2, rows // 2 + 1, rows - 1, rows):
+        for v in around(k * rs - hw - rs / 2):
+            pts.append((v, rng.uniform(-hh, hh)))
+    for k in (1, 2, cols // 2, cols // 2 + 1, cols - 1, cols):
+        for v in around(k * cs - hh - cs / 2):
+            pts.append((rng.uniform(-hw, hw), v))
+    for c in (0.0, rs / 4, -rs / 4):                                 # first and last cell
+        pts += [(-hw + c, -hh + c), (hw - c, hh - c), (-hw + c, hh - c), (hw - c, -hh + c)]
+    for far in (1e3, 1e9, 3e38):
+        pts += [(far, 0.0), (-far, 0.0), (0.0, far), (0.0, -far), (far, -far)]
+    for bad in (np.nan, np.inf, -np.inf):
+        pts += [(bad, 0.0), (0.0, bad), (bad, bad)]
+    pts += [tuple(p) for p in rng.uniform([-hw * 1.05, -hh * 1.05], [hw * 1.05, hh * 1.05], (64, 2))]
+    return np.array(pts, np.float32)
+
+
+def gen_visual_edges(VU, TU):
+    V = importlib.import_module("wheeledlab_tasks.visual.mushr_visual_env_cfg")
+    util = TU.TraversabilityHashmapUtil()
+    trav, mdp_out = {}, {}
+    for gi, (rows, cols, rs, cs) in enumerate(VIS_GEOMS):
+        if gi == 0:   # the task's map, drawn as gen_visual draws it (tests unpack it from visual_trav.npz)
+            np.random.seed(0)
+            m = VU.generated_colored_plane((500, 500), (0.5, 0.5), (100, 100), (50, 50), 1, False)[4]
+        else:         # lookups do not care how the map was made: a fixed random map, neighbouring cells differ half the time
+            m = np.random.RandomState(100 + gi).rand(rows, cols) < 0.5
+        m = np.asarray(m, bool)
+        rng = np.random.RandomState(20 + gi + SEED_OFFSET)
+        xy = visual_edge_points(rows, cols, rs, cs, rng)
+        util.set_traversability_hashmap(m.tolist(), (rows, cols), (rs, cs))
+        xi, yi = util.get_map_id(torch.from_numpy(xy[:, 0].copy()), torch.from_numpy(xy[:, 1].copy()))
+        ok = (npy(yi) < m.shape[0]) & (npy(xi) < m.shape[1])      # what the reference can index (all of it on a square map)
+        xy = xy[ok]
+        t = util.get_traversability(torch.from_numpy(xy.copy()))
+        xi, yi = util.get_map_id(torch.from_numpy(xy[:, 0].copy()), torch.from_numpy(xy[:, 1].copy()))
+        p = f"g{gi}_"
+        if gi > 0:
+            trav[p + "map_packed"] = np.packbits(m)
+        trav.update({p + "xy": xy, p + "trav": npy(t), p + "x_idx": npy(xi), p + "y_idx": npy(yi)})
+        # the reward / termination terms on the same points as car positions
+        n = xy.shape[0]
+        st = make_state(n, 30 + gi)
+        st["pos"][:, :2] = xy
+        env = env_from_state(st)
+        env.scene["terrain"] = types.SimpleNamespace(cfg=types.SimpleNamespace(width=rows * rs, height=cols * cs))   # the cfg's width / height
+        mdp_out.update({p + "pos": st["pos"], p + "lin_vel_b": st["lin_vel_b"],
+                        p + "traversable_reward": npy(V.traversable_reward(env)), p + "forward_vel": npy(V.forward_vel(env)),
+                        p + "out_of_map": npy(V.out_of_map(env))})
+    geoms = np.array(VIS_GEOMS, np.float64)
+    np.savez_compressed(os.path.join(OUT, "visual_trav_edges.npz"), geoms=geoms, **trav)
+    np.savez_compressed(os.path.join(OUT, "visual_mdp_edges.npz"), geoms=geoms, **mdp_out)
+
+
 def main():
     install_stubs()
     A = importlib.import_module("wheeledlab.envs.mdp.actions")
@@ -807,6 +1062,8 @@ def main():
     gen_elevation(El)
     gen_visual(VU, TU)
     gen_visual_terms()
+    gen_elevation_edges(El)
+    gen_visual_edges(VU, TU)
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))

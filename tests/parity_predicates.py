@@ -7,7 +7,10 @@ land on different sides of:
     within CELL_EPS cells of a line at some sub-step.
 Both margins are recorded by the oracle (oracle/vehicle.py::substep `probe`, oracle/elev_step.py::ground_fn `probe`).  The thresholds are
 ~100 x what rounding can move a wheel (1e-6 m, 1e-4 N) and far below what the dynamics do in a sub-step."""
+import os
+
 import numpy as np
+import pytest
 
 FZ_EPS = 0.02        # N     (static load per wheel: 8.3 N)
 CELL_EPS = 2e-3      # cells (0.1 mm at the 5 cm grid)
@@ -55,3 +58,63 @@ def check_state(got, want, probe, n, ok, rows=21, tight=5e-4, loose=400.0, where
                              f"{float(np.asarray(probe['fz_margin'])[e]):.4f} N, cell_margin {float(np.asarray(probe.get('cell_margin', [np.inf] * n))[e]):.5f}")
     assert err[:, touchy].max(initial=0) < loose, (where, float(err[:, touchy].max()))
     return ok & ~touchy, int(touchy.sum())
+
+
+# ---- edge goldens (tests/golden/{,seed1000/,seed2024/}elevation_mdp_edges.npz, visual_*_edges.npz): the inputs a kernel may answer otherwise, each
+# decided from the inputs and the reference's own values ------------------------------------------------------------------------
+
+def rollover_norm_excused(quat, ref_r33, tie=0.5):
+    """rows where the quaternion's norm error alone moves R33 across cos 60 deg: the reference divides by |q|^2
+    (matrix_from_quat), the kernels and the oracle use the unit-quaternion form 1 - 2 (x^2 + y^2)"""
+    q = np.asarray(quat, np.float64)
+    unnorm = 1.0 - 2.0 * (q[:, 1] ** 2 + q[:, 2] ** 2)
+    return (np.asarray(ref_r33) <= tie) != (unnorm <= tie)
+
+
+def map_index_excused(coord, cells, spacing):
+    """one axis of get_map_id: (coord + cells * spacing / 2 + spacing / 2) / spacing, judged in float64 from the fp32 input.
+    Excused: a quotient that is not finite or beyond 2^63, where torch's float -> int64 `.long()` has no defined value (x86 gives
+    INT64_MIN, which clamps to cell 0); and, on geometries whose half extent cells * spacing / 2 is not the same fp32 number when
+    formed from the fp32 spacing (the kernels) as from the float64 one (the reference), a quotient within (cells + |q|) 2^-21 of an
+    integer (a cell line)"""
+    c = np.asarray(coord, np.float64)
+    half64 = np.float32(cells * spacing / 2.0)
+    half32 = np.float32(0.5) * np.float32(np.float32(cells) * np.float32(spacing))
+    with np.errstate(all="ignore"):
+        q = (c + cells * spacing / 2.0 + spacing / 2.0) / spacing
+        wild = ~np.isfinite(q) | (np.abs(q) >= 2.0 ** 63)
+        near = np.abs(q - np.round(q)) <= (cells + np.abs(q)) * 2.0 ** -21
+    return wild | (near & (half64 != half32))
+
+
+def out_of_map_excused(coord, cells, spacing):
+    """one axis of out_of_map: |coord| between the fp32 half extent formed from the float64 spacing (the reference) and the one
+    formed from the fp32 spacing (the kernels), both included"""
+    a = np.abs(np.asarray(coord, np.float32))
+    h64 = np.float32(cells * spacing / 2.0)
+    h32 = np.float32(0.5) * np.float32(np.float32(cells) * np.float32(spacing))
+    return (h64 != h32) & (a >= min(h64, h32)) & (a <= max(h64, h32))
+
+
+# The edge sets live under tests/golden/ only: tests/golden/*_edges.npz (input seeds as generated) and tests/golden/seed1000/*_edges.npz
+# (WL_GOLDEN_SEED_OFFSET=1000), or WL_GOLDEN_DIR alone when it is set (the fresh-seed rerun of test_oracle_golden_drift.py).  The
+# edge values themselves are fixed; only their random filler follows the offset.
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_SEED1000 = os.path.join(_GOLDEN, "seed1000")
+# WL_GOLDEN_DIR = tests/golden_seed1000 (the conftest's second set): its edge files are the ones under tests/golden/seed1000
+_EDGE_DIR_OF = {os.path.realpath(os.path.join(_GOLDEN, os.pardir, "golden_seed1000")): _SEED1000}
+EDGE_SETS = ([_EDGE_DIR_OF.get(os.path.realpath(os.environ["WL_GOLDEN_DIR"]), os.environ["WL_GOLDEN_DIR"])] if os.environ.get("WL_GOLDEN_DIR")
+             else [_GOLDEN, _SEED1000])
+
+
+@pytest.fixture(scope="session", params=EDGE_SETS, ids=["edges" if d == _GOLDEN else "edges_" + os.path.basename(d.rstrip("/")) for d in EDGE_SETS])
+def edge_golden(request):
+    """edge_golden(name) -> the arrays of <set>/<name>.npz; edge_golden.task_map() -> the task's 500 x 500 map (the same in every set)"""
+    def load(name):
+        return dict(np.load(os.path.join(request.param, name + ".npz")))
+
+    def task_map():
+        g = np.load(os.path.join(_GOLDEN, "visual_trav.npz"))
+        return np.unpackbits(g["full_map_packed"])[: 500 * 500].reshape(500, 500).astype(bool)
+    load.task_map = task_map
+    return load

@@ -180,6 +180,13 @@ def test_layout_of_task_structs_and_misuse_codes(tmp_path):
     for big in (A.WlTravMap(base, base, 1 << 23, 2, 10, 0.5, 0.5), A.WlTravMap(base, base, 50000, 50000, 10, 0.5, 0.5)):
         assert lib.wl_visual_step(C.byref(vp), C.byref(good), C.byref(big), base, C.byref(out), 0, 0, None) == -1
         assert vr(C.byref(vp), C.byref(good), C.byref(big), base, C.byref(out), 100 * A.VIS_OBS_DIM, 100, 2, 0, 0, None) == -1
+    # non-square maps: the lookup's clamps (x to rows - 1, y to cols - 1) leave a [rows][cols] array past its shorter side
+    for rect in (A.WlTravMap(base, base, 400, 500, 10, 0.5, 0.5), A.WlTravMap(base, base, 500, 400, 10, 0.5, 0.5)):
+        assert lib.wl_visual_step(C.byref(vp), C.byref(good), C.byref(rect), base, C.byref(out), 0, 0, None) == -1
+        assert vr(C.byref(vp), C.byref(good), C.byref(rect), base, C.byref(out), 100 * A.VIS_OBS_DIM, 100, 2, 0, 0, None) == -1
+        assert lib.wl_visual_reset(C.byref(vp), C.byref(good), C.byref(rect), None, 0, 0, None) == -1
+        assert lib.wl_visual_observe(C.byref(vp), C.byref(good), C.byref(rect), base, None) == -1
+        assert lib.wl_visual_mdp(C.byref(vp), C.byref(rect), 100, 128, base, base, base, base, base, base, None) == -1
     # the visual-depth task's contact sampler reads the row-pair table: it must be there, 4-byte aligned, and indexable
     hf_args = lambda nx, ny, cell, pair: A.WlHeightField(base, nx, ny, 0.0, 0.0, cell, 0.0, 2.0 ** -13, pair)
     for hfx, rc in ((hf_args(8, 8, 1.0, None), -1), (hf_args(8, 8, 1.0, base + 2), -3), (hf_args(1 << 23, 2, 1.0, base), -1),

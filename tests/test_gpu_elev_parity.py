@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import parity_predicates as PRED
+from tests.parity_predicates import edge_golden  # noqa: F401  (fixture)
 from oracle import elev_step as OS
 from oracle import heightfield as OH
 
@@ -312,3 +313,50 @@ def test_row_pair_table_is_what_the_header_says():
     out = torch.empty(64, 689, device="cuda:0")
     rc = env.lib.wl_elev_observe(C.byref(env.p), C.byref(env._bufs), C.byref(bare), out.data_ptr(), None)
     assert rc == -1      # WL_EINVAL
+
+
+@pytest.mark.parametrize("with_timed_out", [False, True])
+def test_elev_mdp_kernel_matches_reference_edges(edge_golden, with_timed_out):
+    """elev_terms at every threshold (tests/golden/{,seed1000/}elevation_mdp_edges.npz): flags and the 0/1 terms bit for bit; the stuck
+    penalty with and without the time-out mask"""
+    from wheeledlab_amd import _abi as A
+    from wheeledlab_amd import params as PP
+    lib = A.load()
+    g = edge_golden("elevation_mdp_edges")
+    n = g["pos"].shape[0]
+    stride = ((n + 63) // 64) * 64
+    p = PP.elev_params()
+    K = g["ray_hits_z"].shape[1]
+    ins = [soa(g[k], stride) for k in ("pos", "quat", "lin_vel_b", "lin_vel_w")]
+    wheel, cmd = soa(g["joint_vel"][:, 2:6], stride), soa(g["command"][:, :2], stride)
+    sens = torch.from_numpy(g["sensor_pos_w"][:, 2].copy()).to(DEV)
+    hits = soa(g["ray_hits_z"], stride)
+    to = torch.from_numpy(g["timed_out"].astype(np.uint8)).to(DEV) if with_timed_out else None
+    terms = torch.zeros(4, stride, device=DEV)
+    flags = torch.zeros(4, stride, dtype=torch.uint8, device=DEV)
+    goal = torch.zeros(2, stride, device=DEV)
+    hmap = torch.zeros(K, stride, device=DEV)
+    rc = lib.wl_elev_mdp(C.byref(p), n, stride, *[t.data_ptr() for t in ins], wheel.data_ptr(), cmd.data_ptr(),
+                         to.data_ptr() if to is not None else None, K, sens.data_ptr(), hits.data_ptr(), terms.data_ptr(),
+                         flags.data_ptr(), goal.data_ptr(), hmap.data_ptr(), None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    T, Fg = terms.cpu().numpy()[:, :n], flags.cpu().numpy()[:, :n].astype(bool)
+    gv = (g["command"][:, :2] - g["pos"][:, :2]).astype(np.float64)
+    g2 = (gv ** 2).sum(-1)
+    tiny = (g2 > 0) & (g2 < 2.0 ** -126)   # |g|^2 below fp32's normal range: v_rsq_f32 flushes it, the kernel's 1/|g| is inf
+    print(f"goal_progress_rate: {tiny.sum()} of {n} excused (goal within 1e-19 m: subnormal |g|^2)")
+    np.testing.assert_allclose(T[0][~tiny], g["goal_progress_rate"][~tiny], rtol=1e-5, atol=1e-5, equal_nan=True)
+    np.testing.assert_array_equal(T[1], g["higher_elevation"])
+    np.testing.assert_array_equal(T[2] > 0.5, g["is_falling_penalty"])
+    stuck_pen = g["stuck"] & ~g["timed_out"] if with_timed_out else g["stuck"]
+    np.testing.assert_array_equal(T[3] > 0.5, stuck_pen)
+    np.testing.assert_array_equal(Fg[0], g["below_min_height"])
+    np.testing.assert_array_equal(Fg[1], g["stuck"])
+    np.testing.assert_array_equal(Fg[3], g["close_to_goal"])
+    ex = PRED.rollover_norm_excused(g["quat"], g["upright_r33"])
+    print(f"rollover: {ex.sum()} of {n} excused (quaternion norm moves R33 across cos 60 deg)")
+    np.testing.assert_array_equal(Fg[2][~ex], g["upright_bool"][~ex])
+    np.testing.assert_allclose(goal.cpu().numpy()[:, :n].T, g["goal_relative_xyz"], rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(hmap.cpu().numpy()[:, :n].T, g["world_height_map"], rtol=1e-6, atol=4e-6, equal_nan=True)
+    assert (g["stuck"] & g["timed_out"]).any() and (g["stuck"] & ~g["timed_out"]).any()

@@ -2,6 +2,7 @@
 import numpy as np
 
 from oracle import elev_mdp as E
+from tests.parity_predicates import edge_golden  # noqa: F401  (fixture)
 
 
 def test_elevation_terms_match_reference(golden):
@@ -159,3 +160,49 @@ def test_saturation_and_hue_on_a_grey_image():
         assert np.abs(out - img).max() <= 1.8e-4 + 1e-7
     for shift in (-0.5, -0.2, 0.3, 0.5):
         np.testing.assert_allclose(adjust_hue(img, shift), img, rtol=0, atol=1e-6)
+
+
+def test_elevation_edges_match_reference(edge_golden):
+    """every threshold of the elevation terms hit exactly, 1 and 2 ulps either side, (1 +- 1e-6) and +- 1e-4 away
+    (tests/golden/gen_golden.py::gen_elevation_edges): booleans bit for bit"""
+    from tests import parity_predicates as PRED
+    g = edge_golden("elevation_mdp_edges")
+    with np.errstate(all="ignore"):
+        np.testing.assert_allclose(E.goal_progress_rate(g["pos"], g["lin_vel_w"], g["command"]), g["goal_progress_rate"],
+                                   rtol=1e-5, atol=1e-5, equal_nan=True)
+        np.testing.assert_allclose(E.world_height_map(g["sensor_pos_w"][:, 2], g["ray_hits_z"], g["pos"][:, 2]),
+                                   g["world_height_map"], rtol=1e-6, atol=4e-6, equal_nan=True)
+    np.testing.assert_allclose(E.goal_relative_xyz(g["pos"], g["command"]), g["goal_relative_xyz"], rtol=2e-6, atol=2e-6)
+    np.testing.assert_array_equal(E.higher_elevation(g["pos"], g["lin_vel_b"]), g["higher_elevation"])
+    np.testing.assert_array_equal(E.forward_vel(g["lin_vel_b"]), g["forward_vel"])
+    np.testing.assert_array_equal(E.is_falling_penalty(g["lin_vel_b"]), g["is_falling_penalty"])
+    np.testing.assert_array_equal(E.stuck(g["lin_vel_b"], g["joint_vel"][:, 2:6]), g["stuck"])
+    np.testing.assert_array_equal(E.close_to_goal(g["pos"], g["command"]), g["close_to_goal"])
+    np.testing.assert_array_equal(E.root_height_below_minimum(g["pos"]), g["below_min_height"])
+    ex = PRED.rollover_norm_excused(g["quat"], g["upright_r33"])
+    print(f"rollover: {ex.sum()} of {ex.size} excused (quaternion norm moves R33 across cos 60 deg)")
+    np.testing.assert_array_equal(E.upright_bool(g["quat"])[~ex], g["upright_bool"][~ex])
+    assert ((g["upright_r33"] == 0.5) & ~ex & g["upright_bool"]).sum() >= 2      # the tie itself is held, and it is rolled over
+    assert g["stuck"].sum() >= 8 and g["close_to_goal"].sum() >= 20 and g["below_min_height"].sum() >= 4
+
+
+def test_visual_edges_match_reference(edge_golden):
+    """map lookups and terms on five geometries (500^2 at 0.5, spacing 0.3, unequal spacings, 101^2, a non-square map where the
+    reference can index it): cell lines in x and y, the map's edges +- ulps, the far field and non-finite points, bit for bit"""
+    from oracle import visual_mdp as V
+    t, m = edge_golden("visual_trav_edges"), edge_golden("visual_mdp_edges")
+    full = edge_golden.task_map()
+    for gi, (rows, cols, rs, cs) in enumerate(t["geoms"]):
+        rows, cols, p = int(rows), int(cols), f"g{gi}_"
+        trav = full if gi == 0 else np.unpackbits(t[p + "map_packed"])[: rows * cols].reshape(rows, cols).astype(bool)
+        kw = dict(num_rows=rows, num_cols=cols, row_spacing=rs, col_spacing=cs)
+        xy = t[p + "xy"]
+        with np.errstate(all="ignore"):
+            xi, yi = V.get_map_id(xy[:, 0], xy[:, 1], **kw)
+            np.testing.assert_array_equal(xi, t[p + "x_idx"], err_msg=p)
+            np.testing.assert_array_equal(yi, t[p + "y_idx"], err_msg=p)
+            np.testing.assert_array_equal(V.get_traversability(trav, xy, **kw), t[p + "trav"], err_msg=p)
+            np.testing.assert_array_equal(V.traversable_reward(trav, m[p + "pos"], **kw), m[p + "traversable_reward"], err_msg=p)
+        np.testing.assert_array_equal(V.forward_vel(m[p + "lin_vel_b"]), m[p + "forward_vel"], err_msg=p)
+        np.testing.assert_array_equal(V.out_of_map(m[p + "pos"], rows * rs, cols * cs), m[p + "out_of_map"], err_msg=p)
+        assert 0.1 < m[p + "out_of_map"].mean() < 0.8 and (t[p + "y_idx"].max() == cols - 1 or rows != cols)   # both sides occur

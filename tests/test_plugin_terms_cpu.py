@@ -1,7 +1,7 @@
 """the reward functions the reference's elevation cfg module defines without registering them
 (mushr_elevation_env_cfg.py:159-164,175-231,256-266) exist in the build as torch terms on the env's state views
 (wheeledlab_amd/envs/mdp.py) so that a config override can wire them in; here they are held against the outputs of the
-reference's own functions (tests/golden*/elevation_unwired.npz, made by tests/golden/gen_golden.py)."""
+reference's own functions (tests/golden/{,seed1000/}elevation_unwired.npz, made by tests/golden/gen_golden.py)."""
 import types
 
 import numpy as np
@@ -10,6 +10,7 @@ import torch
 
 from wheeledlab_amd.envs import mdp
 from wheeledlab_amd.envs.scene import MUSHR_BODY_NAMES, MUSHR_JOINT_NAMES, ArticulationView
+from tests.parity_predicates import edge_golden  # noqa: F401  (fixture)
 
 
 class _Data:
@@ -186,3 +187,44 @@ def test_lidar_terms_read_any_sensor_with_linear_depth():
     assert torch.equal(got, want) and got.min() == 0.0 and got.max() == 1.0
     inner = (r > 1.0) & (r < 9.0)
     assert abs(float(((got * 9.6 + 0.4) - r)[inner].std()) - 0.1) < 0.005          # the noise is there, at its sigma
+
+
+def test_unwired_elevation_terms_at_the_edges(edge_golden):
+    """the unwired torch terms on the elevation edge states (tests/golden/{,seed1000/}elevation_unwired_edges.npz): forward_wheel_spin's cap at
+    200 hit exactly and straddled, quaternions of norm 1 +- a few ulp, R33 at cos 60 deg"""
+    g = edge_golden("elevation_unwired_edges")
+    env = _make_env(g)
+    cases = {
+        "forward_wheel_spin": mdp.forward_wheel_spin(env),
+        "change_in_elevation": mdp.change_in_elevation(env),
+        "steep_penalty": mdp.steep_penalty(env, 0.2),
+        "yaw_change_onElev": mdp.yaw_change_onElev(env, 0.5, 0.1),
+        "roll_on_elev": mdp.roll_on_elev(env, 0.1, 0.1),
+        "ascending": mdp.ascending(env),
+        "low_vel_penalty": mdp.low_vel_penalty(env, 0.1),
+        "upright_penalty_30": mdp.upright_penalty(env, 30.0),
+    }
+    for name, got in cases.items():
+        np.testing.assert_allclose(got.numpy(), g[name].astype(np.float32), rtol=2e-5, atol=2e-5, err_msg=name)
+    np.testing.assert_array_equal(cases["forward_wheel_spin"].numpy(), g["forward_wheel_spin"])   # the cap, bit for bit
+    assert (g["forward_wheel_spin"] == 200.0).sum() >= 4
+
+
+def test_traversability_lookup_at_the_edges(edge_golden):
+    """mdp._traversability_at (through is_traversable_speed_scaled) on the five geometries of tests/golden/{,seed1000/}visual_trav_edges.npz:
+    cell lines in x and y, the map's edges, the far field and non-finite points, bit for bit with the reference's lookups; on the
+    non-square map the points the reference can index"""
+    t = edge_golden("visual_trav_edges")
+    full = edge_golden.task_map().astype(np.uint8)
+    for gi, (rows, cols, rs, cs) in enumerate(t["geoms"]):
+        rows, cols, p = int(rows), int(cols), f"g{gi}_"
+        tmap = full if gi == 0 else np.unpackbits(t[p + "map_packed"])[: rows * cols].reshape(rows, cols)
+        xy = t[p + "xy"]
+        n = xy.shape[0]
+        pos = np.zeros((n, 3), np.float32)
+        pos[:, :2] = xy
+        data = types.SimpleNamespace(root_pos_w=torch.from_numpy(pos), root_lin_vel_b=torch.ones(n, 3))
+        env = types.SimpleNamespace(scene=_Scene(types.SimpleNamespace(data=data), n),
+                                    traversability=(torch.from_numpy(tmap.copy()), (float(rs), float(cs))))
+        got = mdp.is_traversable_speed_scaled(env)
+        np.testing.assert_array_equal(got.numpy() > 0, t[p + "trav"], err_msg=p)

@@ -80,6 +80,7 @@ def test_viewer_refuses_bad_arguments_without_a_gpu():
     assert call(p=_params(ground=A.VIEWER_HEIGHTFIELD)) == -1          # heightfield mode without the field
     assert call(h=hf, pyr=fake) == -1                                  # a field handed to the plane mode
     assert call(p=_params(checker=0.0)) == -1                          # no map and no checker
+    assert call(m=A.WlTravMap(fake, None, 40, 60, 0, 0.5, 0.5, None)) == -1   # a non-square map (lookups would leave it)
     assert call(p=_params(far_clip=0.0)) == -1 and call(p=_params(fx=float("nan"))) == -1
     assert call(scratch=fake + 4) == -3                                # misaligned scratch
 

@@ -486,6 +486,10 @@ class VisualBatch(_MetricsView):
         if trav_map is None:  # generated at construction from a seeded RNG (the reference uses the global numpy RNG)
             trav_map = generate_traversability_map(rng=np.random.RandomState(self.seed), **(map_kwargs or {}))
         trav_map = np.ascontiguousarray(np.asarray(trav_map, dtype=bool))
+        if trav_map.ndim != 2 or trav_map.shape[0] != trav_map.shape[1]:
+            # map[y_idx, x_idx] with x clamped to rows - 1 and y to cols - 1 (traversability_utils.py:78-88) only stays inside a
+            # square map: the reference raises IndexError past the shorter side, and the kernels refuse such a map
+            raise ValueError(f"VisualBatch: the traversability map must be square, got {trav_map.shape}")
         self.trav_map = torch.from_numpy(trav_map.astype(np.uint8)).to(dev)
         self.cells = torch.from_numpy(spawn_cells(trav_map)).contiguous().to(dev)
         # one bit per cell (bit k & 31 of word k >> 5, k = iy * cols + ix): what the camera kernels keep in LDS

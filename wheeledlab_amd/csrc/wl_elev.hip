@@ -59,6 +59,9 @@ WL_DEV void yaw_cs(Quat q, float& c, float& s) {
 
 WL_DEV float sym(float u, float a) { return (2.f * u - 1.f) * a; }
 
+// torch.nan_to_num(x, nan=0) (:55): nan -> 0, and +-inf -> +-FLT_MAX (its default posinf / neginf)
+WL_DEV float nan_to_num(float x) { return x != x ? 0.f : fminf(fmaxf(x, -3.40282347e38f), 3.40282347e38f); }
+
 struct ElevTerms {
     float t[WL_ER_NTERMS];
     bool flag[WL_ET_NTERMS];
@@ -71,9 +74,11 @@ WL_DEV ElevTerms elev_terms(const WlElevParams& p, V3 pos, float up_dot, V3 vb, 
     const float gx = cbx - pos.x, gy = cby - pos.y;   // goal vector: base-frame command minus world position (:50-55 quirk)
     r.flag[WL_ET_BELOW_MIN_HEIGHT] = pos.z < p.min_height;                                            // :356-359
     r.flag[WL_ET_STUCK] = fminf(vb.x, p.stuck_vel_cap) < p.stuck_min_vel && wheel_sum > p.stuck_wheel_spin;   // :342-347
-    r.flag[WL_ET_ROLLOVER] = up_dot < p.upright_cos;                                                  // :217-222, 339-340
+    // :217-222, 339-340: rad2deg(arccos(R33)) > 60 in fp32 is 60.000004 at R33 = 0.5 exactly, so the tie counts as rolled over
+    r.flag[WL_ET_ROLLOVER] = up_dot <= p.upright_cos;
     const float g2 = fmaf(gx, gx, gy * gy);
-    r.flag[WL_ET_AT_GOAL] = fsqrt(g2) < p.goal_dist;                               // :268-273
+    // :268-273: torch.norm of a 2-vector is the correctly rounded sqrt of fma(y, y, x * x) -- that product order, not v_sqrt_f32
+    r.flag[WL_ET_AT_GOAL] = sqrtf(fmaf(gy, gy, gx * gx)) < p.goal_dist;
     r.t[WL_ER_GOAL_PROGRESS] = p.progress_offset + fmaf(vw.x, gx, vw.y * gy) * rsq(g2);   // :239-249
     const float z = pos.z - p.elev_z0;
     r.t[WL_ER_HIGHER_ELEVATION] = clampf((z > p.elev_min && vb.x > p.elev_min_vel) ? z : 0.f, 0.f, 1.f);       // :166-173
@@ -100,8 +105,7 @@ WL_DEV void write_elev_prop(const WlElevParams& p, float* __restrict__ row, V3 p
     }
     if (!lead) return;
     const float gx = cbx - pos.x, gy = cby - pos.y;
-    const float v[13] = {gx != gx ? 0.f : gx,   // nan_to_num(nan=0) (:55); +-inf are left to the policy as in the reference
-                         gy != gy ? 0.f : gy,
+    const float v[13] = {nan_to_num(gx), nan_to_num(gy),
                          eu.x, eu.y, eu.z,
                          clampf(vb.x, -p.obs_clip, p.obs_clip), clampf(vb.y, -p.obs_clip, p.obs_clip), clampf(vb.z, -p.obs_clip, p.obs_clip),
                          clampf(wb.x, -p.obs_clip, p.obs_clip), clampf(wb.y, -p.obs_clip, p.obs_clip), clampf(wb.z, -p.obs_clip, p.obs_clip),
@@ -1338,8 +1342,8 @@ __global__ void __launch_bounds__(kBlock) elev_mdp_kernel(const WlElevParams p, 
 #pragma unroll
     for (int i = 0; i < WL_ET_NTERMS; ++i) flags[i * stride + e] = tm.flag[i] ? 1 : 0;
     const float gx = cbx - P.x, gy = cby - P.y;
-    goal_rel[e] = gx != gx ? 0.f : gx;
-    goal_rel[stride + e] = gy != gy ? 0.f : gy;
+    goal_rel[e] = nan_to_num(gx);
+    goal_rel[stride + e] = nan_to_num(gy);
     if (hit_z) {
         const float sz = sensor_z[e];
         for (int k = 0; k < n_rays; ++k) hmap[k * stride + e] = -(sz - hit_z[k * stride + e] - p.scan_offset) + (P.z - p.elev_z0);

@@ -245,7 +245,7 @@ int wl_viewer_render(const WlViewerParams* p, const WlEnvBuffers* b, const WlHei
         return WL_EINVAL;
     }
     if (map) {
-        if (!map->map || map->rows <= 0 || map->cols <= 0 || !finite_pos(map->row_spacing) || !finite_pos(map->col_spacing)) return WL_EINVAL;
+        if (!map->map || map->rows <= 0 || map->cols != map->rows || !finite_pos(map->row_spacing) || !finite_pos(map->col_spacing)) return WL_EINVAL;
     } else if (!finite_pos(p->checker)) {
         return WL_EINVAL;
     }

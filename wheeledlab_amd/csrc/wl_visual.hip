@@ -614,6 +614,10 @@ int check_visual(const WlVisualParams* p, const WlEnvBuffers* b, const WlTravMap
     const int rc = check_implicit_env(p, b);
     if (rc != WL_OK) return rc;
     if (!m || !m->map || !m->cells || m->n_cells <= 0 || m->rows <= 0 || m->cols <= 0) return WL_EINVAL;
+    // square maps only: the lookup clamps x to rows - 1 and y to cols - 1 but reads map[y][x] of a [rows][cols] array
+    // (traversability_utils.py:78-88); past the shorter side the reference raises IndexError, and the kernels would read
+    // outside the allocation
+    if (m->rows != m->cols) return WL_EINVAL;
     // the camera indexes the map by 24-bit multiplies and reads it through a buffer resource of rows * cols bytes
     if (m->rows >= (1 << 23) || m->cols >= (1 << 23) || (int64_t)m->rows * m->cols > 0x7fffffffLL) return WL_EINVAL;
     return WL_OK;
@@ -741,6 +745,7 @@ int wl_visual_mdp(const WlVisualParams* p, const WlTravMap* m, int32_t n, int64_
                   const float* lin_vel_b, float* terms, uint8_t* out_of_map_, int32_t* x_idx, int32_t* y_idx, void* stream) {
     if (!p || !m || !m->map || n <= 0 || stride < n || !pos || !lin_vel_b || !terms || !out_of_map_ || !x_idx || !y_idx)
         return WL_EINVAL;
+    if (m->rows <= 0 || m->rows != m->cols) return WL_EINVAL;   // square maps only (check_visual)
     clear_error();
     visual_mdp_kernel<<<grid_for(n), kBlock, 0, (hipStream_t)stream>>>(*p, *m, n, stride, pos, lin_vel_b, terms, out_of_map_,
                                                                         x_idx, y_idx);

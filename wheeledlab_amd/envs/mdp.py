@@ -346,7 +346,9 @@ def yaw_change_onElev(env, threshold_yaw, threshold_z):         # :206-212
 
 def upright_penalty(env, thresh_deg):                           # :217-222: tilt of the body z axis beyond thresh_deg [deg]
     q = root_quat_w(env)
-    up = 1.0 - 2.0 * (q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2])   # R[2, 2]
+    # R[2, 2] of isaaclab's matrix_from_quat, which divides by |q|^2: without it a quaternion of norm 1 + 1 ulp turned upside down
+    # gives R33 < -1, arccos nan and no penalty where the reference has 150 deg
+    up = 1.0 - (2.0 / (q * q).sum(-1)) * (q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2])
     tilt = torch.rad2deg(torch.arccos(up))
     return torch.where(tilt > thresh_deg, tilt - thresh_deg, torch.zeros_like(tilt))
 
