@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define WL_ABI_VERSION 23
+#define WL_ABI_VERSION 24
 
 enum WlStatus { WL_OK = 0, WL_EINVAL = -1, WL_ELAUNCH = -2, WL_EALIGN = -3, WL_ENODEV = -4 };
 
@@ -176,9 +176,7 @@ typedef struct WlEnvBuffers {
 #define WL_FLAG_STREAM 1       /* streaming forms: rows / observation rows / outputs written with non-temporal (sc1 nt) stores; */
                                /* drift: the lane-per-env streaming instantiation (`lanes` must not be 4)                        */
 #define WL_FLAG_NO_STREAM 2    /* cache-allocating stores whatever the batch size                                                */
-#define WL_FLAG_SCAN_LDS 4     /* elevation height scan: the env's terrain patch staged in LDS (lane form / wl_elev_observe)     */
-#define WL_FLAG_SCAN_GATHER 8  /* elevation height scan: per-ray gathers from the L2-resident field                              */
-#define WL_FLAG_MASK 15
+#define WL_FLAG_MASK 3
 
 /* ---- outputs of one step -------------------------------------------------------------------------------- */
 typedef struct WlStepOut {
@@ -568,13 +566,8 @@ int wl_elev_rollout_persistent(const WlElevParams* p, const WlEnvBuffers* b, con
                                const WlStepOut* out, int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps, uint64_t seed,
                                uint64_t step0, void* stream);
 
-/* ---- the runner's collection step in ONE launch, elevation task (policy in the loop) -------------------
- * modified_rsl_rl_runner.py:70-80 per step: actions = alg.act(obs) -> obs, rewards, dones = env.step(actions) -> storage.
- * `io` are rows k of an rsl_rl RolloutStorage: the observation row the policy reads and the action / mean / log-prob /
- * value rows it fills; `out` is where the step writes (observation row k + 1, reward / flags / dones rows k).  Quad form
- * only (n_envs <= 32 768; WL_EINVAL beyond: call wl_actor_critic_act + wl_elev_step).  Equals those two calls bit for bit
- * where wl_actor_critic_act splits the features four ways (<= 8192 rows), to rounding elsewhere.  Measured at 4096 envs:
- * 47.9 us against 45.4 us for the two calls (its 16-row blocks double the first-layer operand traffic from L2). */
+/* ---- the runner's collection loop in ONE launch, elevation task (policy in the loop) -------------------
+ * rows of an rsl_rl RolloutStorage: the observation rows the policy reads and the action / mean / log-prob / value rows it fills */
 typedef struct WlCollectIo {
     const float* obs_in;             /* [n][obs_dim] */
     float* actions;                  /* [n][2] */
@@ -582,9 +575,6 @@ typedef struct WlCollectIo {
     float* log_prob;                 /* [n] */
     float* values;                   /* [n] */
 } WlCollectIo;
-int wl_elev_collect_step(const WlElevParams* p, const WlEnvBuffers* b, const WlHeightField* hf, const WlMlp* actor, const WlMlp* critic,
-                         const float* std, const WlCollectIo* io, const WlStepOut* out, int32_t deterministic, uint64_t seed,
-                         uint64_t step, void* stream);
 
 /* The runner's collection loop -- n_steps x { actions = actor(obs) -> env.step -> storage rows } (modified_rsl_rl_runner.py:
  * 70-80) -- as ONE launch.  `io` / `out` are rows 0 of [n_steps (+ 1)][n]... blocks of an rsl_rl RolloutStorage: step k reads

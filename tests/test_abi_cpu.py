@@ -166,6 +166,9 @@ def test_layout_of_task_structs_and_misuse_codes(tmp_path):
     assert cr(C.byref(ep), C.byref(lanes1e), C.byref(hfb), C.byref(na), C.byref(nc), base, C.byref(io), C.byref(nxt), 4, 0, 0, 0, None) == -1
     assert cr(C.byref(ep), C.byref(good), C.byref(hfb), C.byref(na), C.byref(net(3)), base, C.byref(io), C.byref(nxt), 4, 0, 0, 0, None) == -1  # critic out_dim
     assert cr(C.byref(ep), C.byref(good), C.byref(hfb), C.byref(na), C.byref(nc), None, C.byref(io), C.byref(nxt), 4, 0, 0, 0, None) == -1       # no std
+    big = A.WlEnvBuffers(state=base, episode_len=base, ref_poses=base, metrics=base, stride=65536, n_envs=65536, env_offset=0,
+                         metrics_slots=1)
+    assert cr(C.byref(ep), C.byref(big), None, C.byref(na), C.byref(nc), base, C.byref(io), C.byref(nxt), 4, 0, 0, 0, None) == -1  # no heightfield (and beyond the quad form)
     # persistent visual rollout: refused without a map, in the lane form, and with per-step rows that alias
     vp = PP.visual_params()
     tm = A.WlTravMap(base, base, 500, 500, 10, 0.5, 0.5)
@@ -255,13 +258,6 @@ def test_layout_of_learner_structs_and_their_argument_checks(tmp_path):
     sc = A.WlActScratch(base, base, base, 704, 5, 4096, 0)                            # needs ceil(704 / 128) = 6 partial-sum rows
     assert lib.wl_actor_critic_act_planes(C.byref(a), C.byref(c), base, 128, base, 689, base, base, base, base, 0, 1, 2, 0, 3,
                                           C.byref(sc), None) == -1
-    io = A.WlCollectIo(base, base, base, base, base)
-    out = A.WlStepOut(base, base, base, base, None)
-    ep = PP.elev_params()
-    big = A.WlEnvBuffers(state=base, episode_len=base, ref_poses=base, metrics=base, stride=65536, n_envs=65536, env_offset=0,
-                         metrics_slots=1)
-    assert lib.wl_elev_collect_step(C.byref(ep), C.byref(big), None, C.byref(a), C.byref(c), base, C.byref(io), C.byref(out), 0, 1, 2,
-                                    None) == -1       # no heightfield (and beyond the quad form)
 
 
 def test_host_rules_of_the_wide_learner_and_the_policy_step_forms():

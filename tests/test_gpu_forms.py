@@ -2,8 +2,7 @@
 
 The step / scan / camera launchers switch forms by size: the streaming drift step beyond 1.22 M envs (`sc1 nt` row stores,
 csrc/wl_drift.hip launch_step), non-temporal observation rows of the height scan beyond 97 k envs and of the camera beyond
-20.9 k (wl_elev.hip launch_elev_scan, wl_visual.hip launch_visual_obs); the height scan through LDS patches is a flag (round 6: with
-the row-pair table the gather form is the faster one at every size and the default).
+20.9 k (wl_elev.hip launch_elev_scan, wl_visual.hip launch_visual_obs).
 bench.py's `large_n_sweep` / `other_tasks_large_n` rows -- the 4 M-env row carries the north-star's HBM fraction -- are
 measured on exactly those forms.  Here:
 
@@ -64,7 +63,7 @@ def test_streaming_f1tenth_form_matches_oracle_single_steps(A, mode):
 def test_flag_combinations_are_validated(A):
     env = _drift(256, 1)
     a = torch.zeros(256, 2, device=DEV)
-    for bad in (A.FLAG_STREAM | A.FLAG_NO_STREAM, A.FLAG_SCAN_LDS | A.FLAG_SCAN_GATHER, 16, -1):
+    for bad in (A.FLAG_STREAM | A.FLAG_NO_STREAM, 4, 8, 16, -1):      # 4, 8: the retired height-scan form bits
         env.set_flags(bad)
         with pytest.raises(A.WlError):
             env.step(a)
@@ -125,9 +124,8 @@ def _elev(n, seed, flags=0, lanes=0, off=0, params=None, hf=None):
 
 @pytest.mark.parametrize("z_scale", [None, 0.005])
 def test_height_scan_forms_are_bit_identical(A, z_scale):
-    """gather / LDS-patch x cache-allocating / non-temporal: the four scan instantiations write the same 676 values per env --
-    cars anywhere on the terrain at any yaw, incl. on and beyond its border (rays that miss: +inf clipped to 10; a patch origin
-    clamped to the grid) and tilted.  z_scale 0.005: the terrain's codes at IsaacLab's default vertical_scale (not a power of two:
+    """cache-allocating / non-temporal / by size: the scan instantiations write the same 676 values per env -- cars anywhere on
+    the terrain at any yaw, incl. on and beyond its border (rays that miss: +inf clipped to 10) and tilted.  z_scale 0.005: the terrain's codes at IsaacLab's default vertical_scale (not a power of two:
     the decode's product is rounded; every form must round it the same way) -- and the scan against the oracle on those codes."""
     n = 3000 + 11
     hf = None
@@ -136,7 +134,7 @@ def test_height_scan_forms_are_bit_identical(A, z_scale):
         from oracle import heightfield as OH
         from tests.depth_cases import on_lattice
         hf = on_lattice(OH.make_terrain(), z_scale)
-    env = _elev(n, 31, flags=A.FLAG_SCAN_GATHER | A.FLAG_NO_STREAM, hf=None if hf is None else hf + (z_scale,))
+    env = _elev(n, 31, flags=A.FLAG_NO_STREAM, hf=None if hf is None else hf + (z_scale,))
     if hf is not None:
         assert env.hf.z_scale == z_scale and torch.equal(env.height.cpu(), torch.from_numpy(hf[0]))        # decoded = the oracle's grid
     g = torch.Generator(device=DEV).manual_seed(2)
@@ -151,7 +149,7 @@ def test_height_scan_forms_are_bit_identical(A, z_scale):
     q = torch.randn(4, n, device=DEV, generator=g)
     q[1:3] *= 0.15                                                                  # mostly yaw, some roll / pitch
     st[3:7, :n] = q / q.norm(dim=0, keepdim=True)
-    st[3:7, 160:192] = torch.tensor([[0.92388, 0.0, 0.0, 0.38268]], device=DEV).T    # yaw 45 deg: the widest bounding box
+    st[3:7, 160:192] = torch.tensor([[0.92388, 0.0, 0.0, 0.38268]], device=DEV).T    # yaw 45 deg: the widest footprint
     ref = env.observe().clone()
     torch.cuda.synchronize()
     assert torch.isfinite(ref).all() and (ref[:, 13:].abs() <= 10.0).all()
@@ -161,8 +159,7 @@ def test_height_scan_forms_are_bit_identical(A, z_scale):
         d = np.abs(ref[:, 13:].cpu().numpy() - want)
         # a ray within 1e-4 cell of a cell line or the border may fall on the other side in the other arithmetic (counted)
         assert (d > 2e-5).mean() < 2e-4 and np.median(d) < 1e-6, (float((d > 2e-5).mean()), float(d.max()))
-    for flags in (A.FLAG_SCAN_GATHER | A.FLAG_STREAM, A.FLAG_SCAN_LDS | A.FLAG_NO_STREAM, A.FLAG_SCAN_LDS | A.FLAG_STREAM,
-                  A.FLAG_SCAN_LDS, A.FLAG_STREAM):
+    for flags in (A.FLAG_STREAM, 0):
         env.set_flags(flags)
         env.obs.fill_(-77.0)
         got = env.observe()
@@ -171,16 +168,16 @@ def test_height_scan_forms_are_bit_identical(A, z_scale):
         assert not bad.any(), (flags, int(bad.sum()), bad.nonzero()[:5].tolist(), float((got - ref).abs().max()))
 
 
-def test_a_field_the_lds_patch_cannot_take_falls_back_to_the_gather_scan(A):
-    """the LDS form stages 16-byte words from 4-byte aligned addresses: a field with an ODD row pitch (or narrower than a patch row)
-    is scanned by the gather form whatever the flags ask for -- same observation rows, and right against the oracle"""
+def test_odd_pitch_and_narrow_fields_scan_against_the_oracle(A):
+    """fields with an ODD row pitch and narrower than the scan's footprint: both store forms write the same observation rows, and
+    they are right against the oracle"""
     from oracle import elev_step as OE
     from oracle import heightfield as OH
     full = OH.make_terrain()
     for ny, nx in ((613, 349), (200, 90)):
         hf = (np.ascontiguousarray(full[0][:ny, :nx]), full[1], full[2], full[3])
         n = 777
-        env = _elev(n, 23, flags=A.FLAG_SCAN_GATHER | A.FLAG_NO_STREAM, hf=hf)
+        env = _elev(n, 23, flags=A.FLAG_NO_STREAM, hf=hf)
         g = torch.Generator(device=DEV).manual_seed(3)
         st = env.state
         st[0, :n] = float(hf[1]) + torch.rand(n, device=DEV, generator=g) * (nx - 1) * 0.05
@@ -189,18 +186,17 @@ def test_a_field_the_lds_patch_cannot_take_falls_back_to_the_gather_scan(A):
         q[1:3] *= 0.1
         st[3:7, :n] = q / q.norm(dim=0, keepdim=True)
         ref = env.observe().clone()
-        for flags in (A.FLAG_SCAN_LDS, A.FLAG_SCAN_LDS | A.FLAG_STREAM):
-            env.set_flags(flags)
-            env.obs.fill_(-77.0)
-            assert torch.equal(env.observe(), ref), (nx, flags)
+        env.set_flags(A.FLAG_STREAM)
+        env.obs.fill_(-77.0)
+        assert torch.equal(env.observe(), ref), nx
         want = OE.height_map(OE.elev_params(), env.state[:, :n].cpu().numpy(), hf)
         d = np.abs(ref[:, 13:].cpu().numpy() - want)
         assert (d > 2e-5).mean() < 2e-4 and (np.abs(want) < 5).any() and (want == 10.0).any(), (nx, float(d.max()))
 
 
 def test_elevation_lane_form_steps_are_bit_identical_across_scan_forms(A):
-    """the two-launch lane form (what runs beyond 32 768 envs) with the scan through LDS / with streaming rows == the same form
-    with gathers, through resets and command resamples"""
+    """the two-launch lane form (what runs beyond 12 288 envs) with streaming rows == the same form with cache-allocating rows,
+    through resets and command resamples"""
     from wheeledlab_amd.params import elev_params
     n = 2048 + 19
 
@@ -208,7 +204,7 @@ def test_elevation_lane_form_steps_are_bit_identical_across_scan_forms(A):
         p = elev_params()
         p.max_episode_length = 6
         return _elev(n, 17, flags, 1, params=p)
-    envs = [make(A.FLAG_SCAN_GATHER | A.FLAG_NO_STREAM), make(A.FLAG_SCAN_LDS | A.FLAG_STREAM), make(A.FLAG_SCAN_LDS), make(A.FLAG_STREAM)]
+    envs = [make(A.FLAG_NO_STREAM), make(A.FLAG_STREAM)]
     assert _same_rollout(envs, n, 14) > n
 
 
@@ -311,7 +307,7 @@ def test_drift_65536_envs_equal_two_shards(A):
 
 
 def test_elevation_262144_envs_equal_two_shards(A):
-    """other_tasks_large_n: lane-form step + the large-batch height scan (LDS patches, non-temporal rows)"""
+    """other_tasks_large_n: lane-form step + the large-batch height scan (gathers, non-temporal rows)"""
     from wheeledlab_amd.params import elev_params
 
     def make(m, off):

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-WL_ABI_VERSION = 23
+WL_ABI_VERSION = 24
 WL_MAX_REW_TERMS = 8
 
 # WlStateField
@@ -25,7 +25,7 @@ ELEV_DONE_NAMES = ("cart_out_of_bounds", "stuck", "rollover", "at_goal")
 # WlMetric
 M_EPSUM0, M_RESETS, M_TIMEOUTS, M_TERM0, M_NONFINITE, M_EPLEN, M_COUNT = 0, 8, 9, 10, 14, 15, 16
 # WlEnvBuffers.flags (WL_FLAG_*): force an instantiation the launchers otherwise pick from the batch size
-FLAG_STREAM, FLAG_NO_STREAM, FLAG_SCAN_LDS, FLAG_SCAN_GATHER = 1, 2, 4, 8
+FLAG_STREAM, FLAG_NO_STREAM = 1, 2
 M_SHARDS = 32   # WL_M_SHARDS: an accumulator vector is [M_SHARDS][M_COUNT], its value the sum over shards
 # WlDriftRewTerm
 DRIFT_TERM_NAMES = ("side_slip", "vel", "progress", "tlgr", "turn_energy", "cross_track", "term_pens")
@@ -223,8 +223,6 @@ SIGNATURES = {
     "wl_elev_step": (C.c_int, [_P(WlElevParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _P(WlStepOut), _u64, _u64, _vp]),
     "wl_elev_rollout": (C.c_int, [_P(WlElevParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _P(WlStepOut), _i64, _i64,
                                   _i32, _u64, _u64, _vp]),
-    "wl_elev_collect_step": (C.c_int, [_P(WlElevParams), _P(WlEnvBuffers), _P(WlHeightField), _P(WlMlp), _P(WlMlp), _vp, _P(WlCollectIo),
-                                       _P(WlStepOut), _i32, _u64, _u64, _vp]),
     "wl_elev_collect_rollout": (C.c_int, [_P(WlElevParams), _P(WlEnvBuffers), _P(WlHeightField), _P(WlMlp), _P(WlMlp), _vp, _P(WlCollectIo),
                                           _P(WlStepOut), _i32, _i32, _u64, _u64, _vp]),
     "wl_elev_rollout_persistent": (C.c_int, [_P(WlElevParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _P(WlStepOut), _i64, _i64,

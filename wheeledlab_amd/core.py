@@ -137,8 +137,7 @@ class _MetricsView:
 
     def set_flags(self, flags: int = 0):
         """WlEnvBuffers.flags (_abi.FLAG_*): force an instantiation the launchers otherwise pick from the batch size -- the
-        streaming (non-temporal store) forms, the cache-allocating forms, the height scan through LDS patches or through
-        gathers.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa)."""
+        streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa)."""
         self._bufs.flags = int(flags)
 
     def _ring_aliases(self, n_steps: int) -> bool:
@@ -403,28 +402,6 @@ class ElevBatch(_MetricsView):
         A.check(fn(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), actions.data_ptr(), C.byref(out), os_, vs_, K, self.seed,
                    self.step_count, self._stream()), "wl_elev_rollout")
         self.step_count += K
-
-
-    def collect_step(self, actor_critic, storage, k: int, deterministic: bool = False):
-        """rows k of the storage <- policy(observation row k); env.step(); observation row k + 1, reward / flags / dones rows k
-        -- the runner's collection step (modified_rsl_rl_runner.py:70-80) as ONE launch (wl_elev_collect_step).
-        `actor_critic`: the kernel view (policy.ActorCritic: .actor, .critic, .std).  Quad form only (n <= 32 768)."""
-        st = storage
-        key = (st.observations.data_ptr(), actor_critic.actor.w1.data_ptr(), actor_critic.critic.w1.data_ptr(), actor_critic.std.data_ptr())
-        if getattr(self, "_collect_key", None) != key:
-            assert st.n_envs == self.n and st.observations.shape[2] == self.OBS_DIM and st.observations.is_contiguous()
-            self._collect_key = key
-            self._collect_nets = (actor_critic.actor.struct(), actor_critic.critic.struct())
-        a, c = self._collect_nets
-        obs = st.observations
-        io = A.WlCollectIo(obs[k].data_ptr(), st.actions[k].data_ptr(), st.mu[k].data_ptr(), st.actions_log_prob[k].data_ptr(),
-                           st.values[k].data_ptr())
-        out = A.WlStepOut(obs[k + 1].data_ptr(), st.rewards[k].data_ptr(), st.terminated[k].data_ptr(), st.time_outs[k].data_ptr(),
-                          st.dones[k].data_ptr())
-        A.check(self.lib.wl_elev_collect_step(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), C.byref(a), C.byref(c),
-                                              actor_critic.std.data_ptr(), C.byref(io), C.byref(out), int(bool(deterministic)),
-                                              self.seed, self.step_count, self._stream()), "wl_elev_collect_step")
-        self.step_count += 1
 
     def collect_rollout(self, actor_critic, storage, start: int = 0, count: int | None = None, deterministic: bool = False):
         """rows start .. start + count - 1 of the storage (and observation row start + count) from observation row `start`: the

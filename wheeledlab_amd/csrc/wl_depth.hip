@@ -116,7 +116,8 @@ WL_DEV DepthCam depth_cam(const WlVisualParams& p, const WlEnvBuffers& b, int e)
 }
 
 // one ray per lane, one 4 x 16 tile per wavefront: the wavefront lives as long as its longest ray (lanes busy 0.6 of the steps on
-// the bench poses) -- and is still the fastest form measured (the ray-pool form below: 1.3 - 2 x slower).
+// the bench poses) -- and is still the fastest form measured (a ray pool per wavefront, idle lanes refilled with the next rays of
+// the image: 1.3 - 2 x slower).
 // ROWS names what the launch writes -- 0: the 60 x 80 image of wl_visual_depth, 1: the observation rows of the visual-depth task
 // (stride 4808) -- same code; two instantiations so that a kernel-statistics summary keeps the two workloads apart.
 template <int ROWS>
@@ -134,90 +135,6 @@ __global__ void __launch_bounds__(64) visual_depth_tile_kernel(const WlVisualPar
     // non-temporal: the image rows must not push the pyramid and the heights (4.3 MB for the 800 x 800 field, an XCD's L2 holds 4 MB)
     // out of L2 -- round 4, 4096 images: counter reads 176 -> 69 MB per render (the compulsory fill is 8 XCDs x 4.3 MB), 380 -> 372 us
     __builtin_nontemporal_store(t, depth + (int64_t)e * row_stride + row * WL_VIS_IMG_W + col);
-}
-
-// Ray POOL per wavefront (round 4; MEASURED SLOWER, not the default: -DWL_DEPTH_POOL_ROWS=4 | 12 | 20 | 60 builds it).  A tile's
-// walk lengths differ 5 x between lanes (sky 2 - 3 steps, near ground 8 - 10, the rows below the horizon 15 - 20, grazing rays
-// 100 +): with one ray per lane 40 % of the lane-steps are idle lanes waiting for the tile's longest ray.  Here a wavefront owns
-// POOL_ROWS image rows of one env (in 4 x 16 tile order, so that the lanes start as neighbours) and a lane whose ray is done takes
-// the next ray of the pool: whenever at least THRESH lanes are idle they are refilled in ONE pass of the set-up code (ballot +
-// prefix count give each idle lane its pool index).  The host simulation of the same walk (tests/host_sim) promised 11.8
-// wave-steps per 64 rays against 15.2 (lanes busy 0.80 instead of 0.60).  On the device, 4096 cameras, us per render: tile form
-// 545; pools of 4 rows 718, 12 rows 839 (THRESH 12 / 20 / 32: 849 / 839 / 893; non-temporal stores 802), 20 rows 890, 60 rows
-// 1083.  What the simulation does not see: lanes that hold rays from different tiles at different depths of their walks gather
-// from 64 unrelated places per step (the tile form's neighbours share their cache lines), and the fewer, longer wavefronts
-// balance worse over the chip.  Idle lanes are the cheaper evil.
-#ifndef WL_DEPTH_POOL_ROWS
-#define WL_DEPTH_POOL_ROWS 0     // 0: the tile form
-#endif
-#ifndef WL_DEPTH_POOL_THRESH
-#define WL_DEPTH_POOL_THRESH 20
-#endif
-template <int POOL_ROWS, int THRESH>
-__global__ void __launch_bounds__(64) visual_depth_pool_kernel(const WlVisualParams p, const WlEnvBuffers b, const DepthGrid g,
-                                                                const Pyramid py, const float* __restrict__ buf, const unsigned buf_bytes,
-                                                                const float max_depth, float* __restrict__ depth, const int64_t row_stride) {
-    static_assert(POOL_ROWS % kStripRows == 0 && WL_VIS_IMG_H % POOL_ROWS == 0, "whole strips per pool, whole pools per image");
-    constexpr int kPools = WL_VIS_IMG_H / POOL_ROWS, kPool = POOL_ROWS * WL_VIS_IMG_W;
-    const int e = blockIdx.x / kPools, r0 = (blockIdx.x - e * kPools) * POOL_ROWS;
-    const DepthCam cam = depth_cam(p, b, e);
-    const FieldMem mem{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(buf), 0, (int)buf_bytes, 0x00020000)};
-    const PyrHead hd = pyramid_head(g, py, mem);
-    const float zclear = hd.zclear;
-    float* img = depth + (int64_t)e * row_stride + r0 * WL_VIS_IMG_W;
-    const int lane = threadIdx.x;
-    const int max_walk = max_walk_steps(g);
-    // pool index -> pixel of the pool's rows: tile (q >> 6) = strip-major 4 x 16 tiles, (q & 63) = row-major inside the tile
-    auto pixel = [](int q, int& row, int& col) {
-        const int tile = q >> 6, in = q & 63;
-        const int strip = (int)(__umul24((unsigned)tile, 13108u) >> 16);    // tile / 5 for tile < 2^14
-        row = strip * kStripRows + (in >> 4);
-        col = (tile - strip * kTilesPerStrip) * kTileCols + (in & 15);
-    };
-    // pixel -> ray through the reciprocal focal lengths (one division each per wavefront, not two per ray set-up)
-    const float ifx = 1.f / p.fx, ify = 1.f / p.fy;
-    auto ray_dir = [&](int prow, int pcol) {
-        return mul(cam.R, v3(1.f, -(((float)pcol + 0.5f - p.cx) * ifx), -(((float)(r0 + prow) + 0.5f - p.cy) * ify)));
-    };
-    int q = lane, row, col, steps = 0;
-    pixel(q, row, col);
-    RayWalk w = ray_begin(g, py, zclear, cam.o, ray_dir(row, col), max_depth);
-    bool have = true;
-    int next = 64;          // wave-uniform: the first pool index nobody has taken
-#pragma unroll 1
-    for (;;) {
-        if (have) {
-            if (w.live && steps < max_walk) {
-                ray_step(g, py, hd, mem, w);
-                ++steps;
-            } else {
-#ifdef WL_DEPTH_NT
-                __builtin_nontemporal_store(ray_result(g, w), img + row * WL_VIS_IMG_W + col);
-#else
-                img[row * WL_VIS_IMG_W + col] = ray_result(g, w);
-#endif
-                have = false;
-            }
-        }
-        const uint64_t idle = __ballot(!have);
-        const int n_idle = __popcll(idle);
-        if (next < kPool) {
-            if (n_idle >= THRESH) {
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-                const int qn = next + rank;
-                if (!have && qn < kPool) {
-                    q = qn;
-                    pixel(q, row, col);
-                    w = ray_begin(g, py, zclear, cam.o, ray_dir(row, col), max_depth);
-                    steps = 0;
-                    have = true;
-                }
-                next += n_idle;
-            }
-        } else if (n_idle == 64) {
-            break;
-        }
-    }
 }
 
 // the 8 proprioceptive columns of the visual-depth observation (base_lin_vel | base_ang_vel | last_action clipped) of the state as it
@@ -276,15 +193,10 @@ int wl_visual_depth_rows(const WlVisualParams* p, const WlEnvBuffers* b, const W
     const Pyramid py = make_pyramid(hf->nx, hf->ny);
     const unsigned bytes = (unsigned)(pyramid_total_floats(hf->nx, hf->ny) * 4);
     clear_error();
-#if WL_DEPTH_POOL_ROWS > 0
-    visual_depth_pool_kernel<WL_DEPTH_POOL_ROWS, WL_DEPTH_POOL_THRESH><<<b->n_envs * (WL_VIS_IMG_H / WL_DEPTH_POOL_ROWS), 64, 0, (hipStream_t)stream>>>(
-        *p, *b, make_depth_grid(hf), py, pyramid, bytes, max_depth, rows, row_stride);
-#else
     if (row_stride == WL_VISDEPTH_NPIX)
         visual_depth_tile_kernel<0><<<b->n_envs * kTiles, 64, 0, (hipStream_t)stream>>>(*p, *b, make_depth_grid(hf), py, pyramid, bytes, max_depth, rows, row_stride);
     else
         visual_depth_tile_kernel<1><<<b->n_envs * kTiles, 64, 0, (hipStream_t)stream>>>(*p, *b, make_depth_grid(hf), py, pyramid, bytes, max_depth, rows, row_stride);
-#endif
     return launch_status();
 }
 

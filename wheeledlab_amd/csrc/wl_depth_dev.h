@@ -214,9 +214,9 @@ inline DepthGrid make_depth_grid(const WlHeightField* hf) {
     return DepthGrid{hf->nx, hf->nx - 1, hf->ny - 1, hf->x0, hf->y0, 1.f / hf->cell, hf->outside_z, hf->z_scale};
 }
 
-// The walk of ONE ray as a state machine, so that a wavefront can keep its lanes busy: ray_begin() sets a ray up (or answers it
-// at once: never over the grid, underground, ...), ray_step() advances it by one pyramid cell, ray_result() closes it.  The
-// kernel (wl_depth.hip) hands a lane the next ray of its pool the moment the lane's ray is done.  Spec: oracle/depth.c::cast_ray.
+// The walk of ONE ray as a state machine: ray_begin() sets a ray up (or answers it at once: never over the grid, underground,
+// ...), ray_step() advances it by one pyramid cell, ray_result() closes it; cast_ray below runs it to the end.  Spec:
+// oracle/depth.c::cast_ray.
 struct RayWalk {
     // constants of the ray
     float ou, ov, du, dv, idu, idv, oz, dz;

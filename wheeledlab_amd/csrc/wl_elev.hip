@@ -10,10 +10,9 @@
 //   lane form: TWO --
 //   1. elev_step_kernel  (lane = env): the same step; state is read once / written once, sub-steps stay in VGPRs; also
 //      writes the 13 proprioceptive values of the observation row.
-//   2. elev_scan_kernel / elev_scan_lds_kernel (block = env): the 26 x 26 yaw-aligned height rays, four per lane, written as
-//      16-byte words -- this launch carries ~90 % of the task's HBM bytes (2.7 KB / env).  Gather form (two 4-byte gathers of
-//      two height codes per ray) below 16 384 envs, LDS-patch form (the footprint's codes staged by LDS-DMA) beyond; the terrain
-//      is 16-bit codes x z_scale since round 5 (wl_heightfield.h).  (Round 2 history: staging the env's
+//   2. elev_scan_kernel (block = env): the 26 x 26 yaw-aligned height rays, four per lane, written as 16-byte words -- this
+//      launch carries ~90 % of the task's HBM bytes (2.7 KB / env).  One 8-byte gather of four height codes per ray from the
+//      row-pair table; the terrain is 16-bit codes x z_scale since round 5 (wl_heightfield.h).  (Round 2 history: staging the env's
 //      terrain patch in LDS -- its bounding box fetched row by row with coalesced 8-byte requests, corners read from
 //      the tile -- was measured slower in every form tried: block per env 15.8 us, persistent blocks with the next
 //      env's pose prefetched 18 us, against 11.3 us for the gathers; round 2, DESIGN.md section 6.  Round 3: the same for the
@@ -197,13 +196,12 @@ WL_DEV ScanCell scan_cell(const ScanFrame& f, const WlHeightField& hf, float fix
     c.i = i, c.j = j;
     return c;
 }
-// a ray in flight: the gather(s) of its cell's four corner codes, decoded and consumed by scan_value.
-// PAIR (the gather forms, round 6): ONE 8-byte gather from the row-pair table (WlHeightField.pair): lo = (c00 | c01 << 16), hi = (c10 |
-// c11 << 16).  The gather forms were bound by the texture unit's address rate -- rocprofv3 on the fused launch at 4096 envs: TA busy
-// 16 000 cycles per CU = the whole scan phase, 57 cache accesses per 64-lane gather instruction, L1 hit rate 0.91 -- and a ray cost
-// two of them (rows j and j + 1 of the code field); with the pair table it costs one (measured: fused step 20.5 -> 17.5 us, gather-form
-// scan at 262 144 envs 484 -> 319 us).  !PAIR (the LDS patch form, which reads the code field's rows): lo = codes (i, i + 1) of row j,
-// hi = of row j + 1, low half = the first.
+// a ray in flight: the gather of its cell's four corner codes, decoded and consumed by scan_value.
+// Round 6: ONE 8-byte gather from the row-pair table (WlHeightField.pair): lo = (c00 | c01 << 16), hi = (c10 | c11 << 16).  The
+// gathers were bound by the texture unit's address rate -- rocprofv3 on the fused launch at 4096 envs: TA busy 16 000 cycles per CU
+// = the whole scan phase, 57 cache accesses per 64-lane gather instruction, L1 hit rate 0.91 -- and a ray cost two of them (rows j
+// and j + 1 of the code field); with the pair table it costs one (measured: fused step 20.5 -> 17.5 us, gather-form scan at 262 144
+// envs 484 -> 319 us).
 struct ScanRay {
     uint32_t lo, hi;
     float fu, fv;
@@ -229,7 +227,7 @@ WL_DEV ScanRay scan_request(const ScanFrame& f, const WlHeightField& hf, const S
     return r;
 }
 // FOUR consecutive rays per lane, stored as ONE 16-byte word (round 4).  The scan's 676 four-byte stores per env were what bound
-// it, in the gather form and the LDS form alike (both 500 us per launch at 262 144 envs whatever the read side did): a store
+// it, whatever the read side did (gathers or an LDS patch, DESIGN.md section 7: 500 us per launch at 262 144 envs either way): a store
 // instruction costs the memory pipeline per INSTRUCTION far more than per byte (MI355X_MICROARCH.md: narrow stores are issue-bound,
 // a dword store ~6 x a dwordx4 store per byte).  Rays 4 q .. 4 q + 3 of an env (q < 169) are neighbours along x; the scan row has 26
 // = 6.5 quads, so a quad starting at ix = 24 continues at (0, iy + 1): ray pairs (0, 1) and (2, 3) never straddle a row.
@@ -243,15 +241,12 @@ WL_DEV void scan_quad_slot(int idx, int& j, int& q) {
 }
 // bilinear height under the ray -> the observation value: -(sensor_z - hit_z - offset) + (root_z - plane_init_value), +inf on a
 // miss, clipped to +- obs_clip
-template <bool PAIR = true>
 WL_DEV float scan_value(const WlElevParams& p, const ScanRay& r, float z_scale, float pz) {
     // the blend runs on the CODES and is scaled once (3 instructions per ray fewer than decoding the four corners first; the large-batch
     // scan is VALU-bound since round 5).  Exactly the decode-first value when z_scale is a power of two (terrain.py's default: scaling
     // by 2^k commutes with every rounding); for other scales it differs from it in the last bit -- every scan form shares this function
-    // (codes are < 2^15 in magnitude: their differences are exact in either layout, so both give the same bits)
-    const float lo0 = (float)(int)(int16_t)(r.lo & 0xffffu), lo1 = (float)((int)r.lo >> 16);
-    const float hi0 = (float)(int)(int16_t)(r.hi & 0xffffu), hi1 = (float)((int)r.hi >> 16);
-    const float c00 = lo0, c10 = PAIR ? hi0 : lo1, c01 = PAIR ? lo1 : hi0, c11 = hi1;
+    const float c00 = (float)(int)(int16_t)(r.lo & 0xffffu), c01 = (float)((int)r.lo >> 16);
+    const float c10 = (float)(int)(int16_t)(r.hi & 0xffffu), c11 = (float)((int)r.hi >> 16);
     const float a = fmaf(r.fu, c10 - c00, c00), b = fmaf(r.fu, c11 - c01, c01);
     float hz;
     {
@@ -272,11 +267,10 @@ WL_DEV void scan_quad_request(const ScanFrame& f, const WlHeightField& hf, const
     r[3] = scan_request(f, hf, sf, fx2 + 1.f, fy2);
 }
 // ... and their four values as one 16-byte word
-template <bool PAIR = true>
 WL_DEV wl_float4_u scan_quad_value(const WlElevParams& p, const ScanRay (&r)[4], float z_scale, float pz) {
     wl_float4_u v;
-    v.x = scan_value<PAIR>(p, r[0], z_scale, pz), v.y = scan_value<PAIR>(p, r[1], z_scale, pz), v.z = scan_value<PAIR>(p, r[2], z_scale, pz);
-    v.w = scan_value<PAIR>(p, r[3], z_scale, pz);
+    v.x = scan_value(p, r[0], z_scale, pz), v.y = scan_value(p, r[1], z_scale, pz), v.z = scan_value(p, r[2], z_scale, pz);
+    v.w = scan_value(p, r[3], z_scale, pz);
     return v;
 }
 #ifndef WL_FUSED_SCAN_NT
@@ -514,215 +508,37 @@ __global__ void __launch_bounds__(kScanThreads) elev_scan_kernel(const WlElevPar
     scan_quad_request(fr, ground.f, sf, tid, cr);     // this lane's four rays: their 8 gathers in flight together
     scan_quad_store<STREAM>(obs + (int64_t)e * WL_ELEV_OBS_DIM + 13, tid, scan_quad_value(p, cr, sf.z_scale, pz));
 }
-// The same scan with the env's terrain patch staged in LDS (BASELINE config 3: "heightfield gather ... in LDS").  One block =
-// one env.  The bounding box of the yaw-rotated 2.5 m footprint -- at most 74 x 74 grid points of the 0.05 m field -- is fetched
-// as whole rows (consecutive lanes = consecutive 16-byte words: full-rate coalesced requests, against two divergent 4-byte
-// gathers per ray) and the 676 rays read their four corners from LDS (two aligned dword pairs each, the code pair cut out with v_alignbit) with
-// the arithmetic of scan_cell / scan_value: the rows are bit-identical to the gather form's.  The staging costs NO vector
-// arithmetic per element: THREADS lanes x 16 bytes = a whole number of patch rows of PITCH codes per pass, so a thread's column
-// group never changes and its row advances by a constant -- the global offset of pass `it` is the thread's constant lane offset
-// + a SCALAR offset, its LDS address the wavefront's M0 base + an immediate.  Rows past the field's end read 0 through the buffer
-// resource's bounds check (never used: rays there are misses).
-// Round 5: 16-bit codes -- a patch row of 80 codes is 160 B instead of 320, the block stages half of round 4's 25.6 KB (the L2 -> LDS
-// volume was the scan's largest stream: ~6 GB per launch at 262 144 envs).  The patch origin
-// is an EVEN column (16-byte requests from 4-byte aligned addresses need an even code index; the row pitch nx must be even too:
-// scan_patch_fits), one column of the 80 - 74 spare.
-// (Round 4, first version: 256 threads, pitch 74, flat index split by multiply-shift per element, pass count by a chain of scalar
-// branches -- 245 VALU + 216 SALU per wavefront, four wavefronts per env: SLOWER than the gathers at every size, 597 against
-// 502 us per observation launch at 262 144 envs: the scan is instruction-bound before it is address-rate-bound.)
-constexpr int kPatch = 74;               // grid points per side the bounding box can need (scan_size * sqrt 2 / cell + 3 must fit)
-constexpr int kPatchRows = 80;           // patch rows staged at most (kPatch + slack, a multiple of 16)
-// Block shape (round 5, us per observation launch at 262 144 envs, same box): 320 threads / pitch 80 (round 4's shape, three
-// requests per thread) 411 - 414; 256 / 128: the same; 192 / 96 (the three wavefronts that cast the rays also stage, five requests
-// per thread, 15.4 KB per env) 355 - 357 -- fewer, fuller wavefronts per env; shipped.
-#ifndef WL_SCAN_LDS_THREADS
-#define WL_SCAN_LDS_THREADS 192
-#endif
-#ifndef WL_SCAN_LDS_PITCH
-#define WL_SCAN_LDS_PITCH 96             // codes per LDS row (>= kPatch + 2: an even origin costs one column)
-#endif
-#ifndef WL_SCAN_LDS_STAGERS
-#define WL_SCAN_LDS_STAGERS WL_SCAN_LDS_THREADS      // threads that issue staging requests (a whole number of patch rows per pass)
-#endif
-// the 7 pose rows of env e (block-uniform address) by ONE lane per wavefront, broadcast with v_readfirstlane: the texture unit is
-// charged per lane address, and with five wavefronts per env the pose loads were 35 of the block's 133 full-width vector-memory
-// instructions.  (Through the scalar cache instead -- s_load_dword x 7 -- the launch is faster up to 16 384 envs, 12.6 against
-// 13.9 us at 4096, and TWICE as slow beyond, 911 against 483 us at 262 144: every block's seven lines miss the small scalar cache.)
-WL_DEV void load_pose_lane0(const Rows& S, int e, float (&v)[7]) {
-    float r[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    static_assert(WL_S_PX == 0 && WL_S_QZ == 6, "pose = rows 0 .. 6");
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) r[k] = S.ld(k, e);
-    }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) v[k] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, r[k])));
-}
-// Block = one env.  Wavefront 0 alone fetches the pose rows and sets the env up (yaw, lattice frame, the patch's
-// origin and row count) and hands 11 words to the others through LDS: the launch is bound by the INSTRUCTIONS it issues, not by
-// what it moves or waits for (measured at 262 144 envs, us per observation launch, profiles/r04_scan_experiments.txt: half of the
-// staging lanes switched off 522 against 538; two / three envs per block with all their requests overlapped 442 / 572 against
-// 418), and with the set-up repeated by all five wavefronts it was a third of them.
-struct ScanSetup {      // what wavefront 0 publishes (44 bytes)
-    ScanFrame fr;
-    int origin, i0, j0, rows;      // byte offset of the patch origin in the field; its column and row; patch rows needed
-};
-template <bool STREAM, int THREADS, int PITCH, int STAGERS = THREADS>
-__global__ void __launch_bounds__(THREADS) elev_scan_lds_kernel(const WlElevParams p, const WlEnvBuffers b, const HeightFieldGround ground,
-                                                                float* __restrict__ obs) {
-    constexpr int kWordsPerRow = PITCH / 8;                          // 16-byte words per patch row
-    constexpr int kRowsPerPass = STAGERS / kWordsPerRow;
-    constexpr int kPasses = (kPatchRows + kRowsPerPass - 1) / kRowsPerPass;
-    constexpr int kAlways = 64 / kRowsPerPass;                      // 64 rows: the footprint at yaw 0 (52 rows) and a little beyond
-    static_assert(PITCH % 8 == 0 && PITCH >= kPatch + 2 && THREADS % 64 == 0 && THREADS >= 192, "whole 16-byte words per row; three ray wavefronts");
-    static_assert(kRowsPerPass * kWordsPerRow == STAGERS && STAGERS <= THREADS && 64 % kRowsPerPass == 0 && kAlways >= 1 && kAlways <= kPasses, "whole rows per pass");
-    __shared__ __attribute__((aligned(16))) int16_t patch[PITCH * kRowsPerPass * kPasses + 8];   // + the dword past the last pair read
-    __shared__ __attribute__((aligned(16))) ScanSetup setup;
-    const int e = blockIdx.x, tid = threadIdx.x;
-    const WlHeightField& f = ground.f;
-    if (tid < 64) {
-        float pose[7];
-        load_pose_lane0(make_rows(b.state, b.stride), e, pose);
-        float c, s;
-        yaw_cs(Quat{pose[3], pose[4], pose[5], pose[6]}, c, s);
-        const ScanFrame fr = scan_frame(p, ground, ScanPose{pose[0], pose[1], pose[2], c, s});
-        // the patch: the lattice's bounding box in grid units (its corners are rays (0,0), (25,0), (0,25), (25,25)), the +1 corner
-        // of the last cell, a little slack for rounding; the origin column rounded down to an even one
-        constexpr float kSpan = (float)(WL_ELEV_SCAN_N - 1);
-        const float u_lo = fr.u0 + fminf(kSpan * fr.ux, 0.f) + fminf(kSpan * fr.uy, 0.f), v_lo = fr.v0 + fminf(kSpan * fr.vx, 0.f) + fminf(kSpan * fr.vy, 0.f);
-        const float v_hi = fr.v0 + fmaxf(kSpan * fr.vx, 0.f) + fmaxf(kSpan * fr.vy, 0.f);
-        const int i0 = min(max((int)floorf(u_lo - 0.02f), 0) & ~1, f.nx - PITCH), j0 = min(max((int)floorf(v_lo - 0.02f), 0), f.ny - kPatch);
-        if (tid == 0) {
-            setup.fr = fr;
-            setup.origin = (j0 * f.nx + i0) * 2;
-            setup.i0 = i0, setup.j0 = j0;
-            setup.rows = min(max((int)floorf(v_hi + 0.02f) + 2 - j0, 1), kPatch);
-        }
-    }
-    __syncthreads();
-    const int origin = __builtin_amdgcn_readfirstlane(setup.origin), rows = __builtin_amdgcn_readfirstlane(setup.rows);
-    // staging: 16 bytes (8 codes) per lane and request, kRowsPerPass patch rows per pass: a thread's column group never changes and
-    // its row advances by kRowsPerPass -- global offset = constant lane offset + a SCALAR pass offset.  Straight into LDS
-    // (buffer_load_dwordx4 ... lds): a wavefront's 64 lanes land as 1 KB at its M0 base -- exactly this layout (consecutive
-    // threads = consecutive 16-byte words) -- with no staging registers and no ds_write.  The compiler does not wait for LDS-DMA:
-    // vmcnt(0) by hand before the barrier that publishes the patch.
-    const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t*>(f.height), 0, f.nx * f.ny * 2, 0x00020000);
-    const int r0 = tid / kWordsPerRow;                               // compile-time divisor: multiply-shift
-    const int c8 = tid - r0 * kWordsPerRow;
-    const int lane_off = ((int)__umul24((unsigned)r0, (unsigned)f.nx) + 8 * c8) * 2;
-    const int pass_bytes = kRowsPerPass * f.nx * 2;
-    if (STAGERS == THREADS || tid < STAGERS) {
-        typedef __attribute__((address_space(3))) void* lds_ptr;
-        int16_t* wave_base = patch + (tid >> 6) * 512;              // 64 lanes x 16 B = 512 codes
-#pragma unroll
-        for (int it = 0; it < kAlways; ++it)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(hr, (lds_ptr)(wave_base + it * STAGERS * 8), 16, lane_off, origin + it * pass_bytes, 0, 0);
-#pragma unroll
-        for (int it = kAlways; it < kPasses; ++it)
-            if (rows > it * kRowsPerPass)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(hr, (lds_ptr)(wave_base + it * STAGERS * 8), 16, lane_off, origin + it * pass_bytes, 0, 0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0)
-    }
-    __syncthreads();
-    if (tid < kScanQuads) {     // the first three wavefronts: one quad of rays per lane
-        const ScanFrame fr = setup.fr;
-        const int i0 = setup.i0, j0 = setup.j0;
-        float fx[4], fy[4];
-        scan_ray_xy(4 * tid, fx[0], fy[0]);
-        scan_ray_xy(4 * tid + 2, fx[2], fy[2]);
-        fx[1] = fx[0] + 1.f, fy[1] = fy[0], fx[3] = fx[2] + 1.f, fy[3] = fy[2];
-        ScanRay cr[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const ScanCell cell = scan_cell(fr, f, fx[m], fy[m]);
-            // clamped (unsigned minimum: a negative offset wraps to the top and is clamped with everything else): a point the
-            // bounding box missed would read a wrong corner (the parity tests would show it), never out of bounds
-            // ALIGNED dword pairs + v_alignbit: a code pair at an odd column straddles two LDS dwords, and a misaligned ds_read_b32
-            // is served lane by lane (measured: the scan launch at 262 144 envs 698 us with 2-byte aligned reads against 404 us for
-            // the fp32 patch of round 4)
-            const unsigned rj = min((unsigned)(cell.j - j0), (unsigned)(kRowsPerPass * kPasses - 2)), ri = min((unsigned)(cell.i - i0), (unsigned)(PITCH - 2));
-            const uint32_t* h = reinterpret_cast<const uint32_t*>(patch) + rj * (PITCH / 2) + (ri >> 1);
-            const unsigned sh = (ri & 1u) * 16u;
-            cr[m].lo = __builtin_amdgcn_alignbit(h[1], h[0], sh);
-            cr[m].hi = __builtin_amdgcn_alignbit(h[PITCH / 2 + 1], h[PITCH / 2], sh);
-            cr[m].fu = cell.fu, cr[m].fv = cell.fv, cr[m].inside = cell.inside;
-        }
-        scan_quad_store<STREAM>(obs + (int64_t)e * WL_ELEV_OBS_DIM + 13, tid, scan_quad_value<false>(p, cr, f.z_scale, fr.pz));
-    }
-}
-// the staged patch must hold the footprint's bounding box at any yaw; 16-byte staging requests need an even row pitch (and the
-// even origin column one spare code)
-inline bool scan_patch_fits(const WlElevParams* p, const WlHeightField* hf) {
-    return hf->nx >= WL_SCAN_LDS_PITCH && hf->ny >= kPatch && (hf->nx & 1) == 0 && p->scan_size * 1.41422f / hf->cell + 3.2f <= (float)kPatch;
-}
-// Which form (round 6): the GATHER form at every size.  With the row-pair table a ray is one lane address instead of two and the
-// gather form passed the LDS form everywhere (us per observation launch, same box, gather / LDS: 16 384 envs 26.8 / 28.3, 65 536:
-// 94 / 95, 262 144: 345 / 356, 1 M: 1223 / 1252; rounds 4 - 5, two gathers per ray: 484 - 515 against 404 -> 334 at 262 144).  Both
-// the gather form is bound by the texture unit's one lane address per cycle (676 per env); what holds the LDS form at the same time
-// (its texture-unit and vector work are each ~half of its launch) was never pinned down.  WL_FLAG_SCAN_LDS still selects the LDS form
-// (BASELINE config 3's "heightfield patch in LDS"; the parity tests run both), WL_SCAN_LDS_MIN_ENVS (default: never) a size from
-// which it is the default.
-#ifndef WL_SCAN_LDS_MIN_ENVS
-#define WL_SCAN_LDS_MIN_ENVS 0x7fffffff
-#endif
 #ifndef WL_ELEV_FUSED_MAX_ENVS
 #define WL_ELEV_FUSED_MAX_ENVS 12288
 #endif
 #ifndef WL_ELEV_STREAM_BYTES
 #define WL_ELEV_STREAM_BYTES 0ll
 #endif
+// The gathers at every size (round 6): with the row-pair table a ray is one lane address, and the gather scan passed the LDS-patch
+// scan (the env's footprint staged by LDS-DMA; measured, dropped: DESIGN.md section 7) at every size.
 inline void launch_elev_scan(const WlElevParams* p, const WlEnvBuffers* b, const HeightFieldGround& g, float* obs, hipStream_t hs) {
     // non-temporal map rows at every size unless WL_FLAG_NO_STREAM asks otherwise (round 4: 2 - 3 % of the step from 4096 envs up; the rows
     // are not read again by this launch, and an XCD's L2 does not survive the launch boundary anyway)
     const bool stream = use_streaming(b, (int64_t)b->n_envs * WL_ELEV_OBS_DIM * 4, WL_ELEV_STREAM_BYTES);
-    const bool lds = scan_patch_fits(p, &g.f) && ((b->flags & WL_FLAG_SCAN_LDS) || (!(b->flags & WL_FLAG_SCAN_GATHER) && b->n_envs >= WL_SCAN_LDS_MIN_ENVS));
-    if (lds) {
-        if (stream) elev_scan_lds_kernel<true, WL_SCAN_LDS_THREADS, WL_SCAN_LDS_PITCH, WL_SCAN_LDS_STAGERS><<<b->n_envs, WL_SCAN_LDS_THREADS, 0, hs>>>(*p, *b, g, obs);
-        else elev_scan_lds_kernel<false, WL_SCAN_LDS_THREADS, WL_SCAN_LDS_PITCH, WL_SCAN_LDS_STAGERS><<<b->n_envs, WL_SCAN_LDS_THREADS, 0, hs>>>(*p, *b, g, obs);
-        return;
-    }
     if (stream) elev_scan_kernel<true><<<b->n_envs, kScanThreads, 0, hs>>>(*p, *b, g, obs);
     else elev_scan_kernel<false><<<b->n_envs, kScanThreads, 0, hs>>>(*p, *b, g, obs);
 }
 
 // env.step() AND the height scan as ONE launch (quad form, n <= 32 768): block = 16 envs, 8 wavefronts.  Wavefront 0
-// steps them (16 quads, as in elev_step_kernel<4>) and leaves each env's post-step pose in LDS; then all eight
-// wavefronts cast the 16 x 676 rays (flat index over (env, ray): 21.1 per lane, in three batches of gathers).  Against the
-// two-launch form this removes the scan kernel's own start (launch gap, wave ramp, the pose rows' first-touch latency)
-// from the step's dependent chain, and one physics wavefront per CU spreads the step over 256 CUs instead of 64 (4096 envs).
+// steps them (16 quads, as in elev_step_kernel<4>) while wavefront 1 draws their reset poses (ResetHelper), and leaves each
+// env's post-step lattice frame in LDS; then all eight wavefronts cast the 16 x 169 quads of rays (flat index over (env, quad),
+// one quad per lane and batch: the scan phase below).  Against the two-launch form this removes the scan kernel's own start
+// (launch gap, wave ramp, the pose rows' first-touch latency) from the step's dependent chain, and one physics wavefront per CU
+// spreads the step over 256 CUs instead of 64 (4096 envs).
 constexpr int kFusedThreads = 512, kFusedEnvs = 16;
 
-// what the policy phase of the collector kernel reads and fills: rows k of an rsl_rl RolloutStorage
-struct PolicyIo {
-    WlMlp actor, critic;
-    const float* std;
-    const float* obs_in;   // [n][689] observation row k
-    float *actions, *mu, *log_prob, *values;
-    int deterministic;
-};
-
-// POLICY: the runner's whole collection step -- actions = alg.act(obs) -> env.step(actions) -> next observation
-// (modified_rsl_rl_runner.py:70-80) -- in this one launch.  Phase A: the eight wavefronts are 2 nets x 4 shares of the 689
-// features of layer 1 for the block's 16 observation rows -- the structure AND the arithmetic of
-// actor_critic_act_kernel<ACT, 4, RT> (same feature ranges, bias on the first share, partial accumulators summed in the same
-// order; f32 MFMA is an fmaf chain), so the collector equals { wl_actor_critic_act; wl_elev_step } bit for bit wherever that
-// kernel splits the features four ways (the elevation agent at <= 8192 rows).  Wavefront 0 (actor) and wavefront 4 (critic)
-// then finish their nets (layers 2-3, draw, log-prob) and wavefront 0 hands the 16 actions to the physics through LDS.
-// MEASURED SLOWER than the two launches it replaces (4096 envs: 47.9 us against 16.2 + 29.1 = 45.4 us per collection step;
-// with layer 1's MFMA loop cut out 34.4, with the tail cut out 44.0): a block of 16 rows streams BOTH first-layer matrices
-// (352 KB) from L2 -- 90 MB per launch, twice the stand-alone policy kernel's traffic (32 rows per block), and that kernel
-// is already bound by exactly this L2 -> L1 operand stream.  More rows per block would halve it and double the scan phase
-// per CU.  The entry point stays (bit-identical to the two calls, tests/test_gpu_training.py); the runner does not use it.
-template <bool POLICY, int ACT = WL_ACT_ELU>
 __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlElevParams p_arg, const VehDerived vd_arg,
                                                                        const WlEnvBuffers b, const HeightFieldGround ground,
                                                                        const float2* __restrict__ actions, const WlStepOut out,
-                                                                       const uint64_t seed, const uint64_t step, const PolicyIo pio) {
+                                                                       const uint64_t seed, const uint64_t step) {
     __shared__ float blk_metrics[WL_M_COUNT];
     __shared__ ScanFrame frame[kFusedEnvs];
-    __shared__ __attribute__((aligned(16))) float hbuf[POLICY ? 2 * 3 * kMlpTiles * 64 * 4 : 4];   // partial accumulators [net][share - 1][tile][lane][4]
-    __shared__ float2 act_lds[kFusedEnvs];
-    __shared__ ResetHelper<ElevReset, kFusedEnvs> resets;     // the block's 16 reset draws, by wavefront 1 while wavefront 0 integrates (!POLICY)
+    __shared__ ResetHelper<ElevReset, kFusedEnvs> resets;     // the block's 16 reset draws, by wavefront 1 while wavefront 0 integrates
     const int tid = threadIdx.x;
     if (tid < 64) WL_TL(0);
     resets.init();
@@ -730,103 +546,6 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
     const int m_slot = b.metrics_slots > 1 ? (int)(step % (uint64_t)b.metrics_slots) : 0;
     if (b.metrics_slots > 1) clear_metric_slot(b, (m_slot + 1) % b.metrics_slots);
     const int e0 = blockIdx.x * kFusedEnvs;
-    if constexpr (POLICY) {
-        const int lane = tid & 63, wave = tid >> 6, m = lane & 15, g = lane >> 4;
-        const int which = wave >> 2, share = wave & 3;        // net, share of the features
-        const WlMlp& net = which == 0 ? pio.actor : pio.critic;
-        constexpr int D = WL_ELEV_OBS_DIM, kShares = 4, kFull = D >> 4, kPer = (kFull + kShares - 1) / kShares;
-        const float* w_lane = net.w1 + (int64_t)m * D + 4 * g;      // unit m (+ 16 t), features 4 g ..
-        const float* x_lane = pio.obs_in + (int64_t)min(e0 + m, b.n_envs - 1) * D + 4 * g;
-        // the tail's weights and the draw are independent of layer 1: requested / computed in the shadow of its loads
-        MlpTail W;
-        float z0 = 0.f, z1 = 0.f;
-        if (share == 0) {
-            load_tail(net, lane, W);
-            if (which == 0 && !pio.deterministic) {
-                const F4 u = philox_uniform4((uint32_t)(b.env_offset + e0 + m), step, WL_RS_POLICY, seed);
-                box_muller(u.x, u.y, z0, z1);
-            }
-        }
-        f32x4 h[kMlpTiles];
-#pragma unroll
-        for (int t = 0; t < kMlpTiles; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[t][r] = share == 0 ? net.b1[16 * t + 4 * g + r] : 0.f;   // the bias seeds the first share
-        const int c0 = min(share * kPer, kFull), c1 = min(c0 + kPer, kFull);
-        constexpr int kDepth = 4;   // chunks of operands in flight (4 weight tiles + the observation rows each)
-        wl_f4u ra[kDepth][kMlpTiles], rb[kDepth];
-#pragma unroll
-        for (int j = 0; j < kDepth; ++j)
-            if (c0 + j < c1) {
-#pragma unroll
-                for (int t = 0; t < kMlpTiles; ++t) ra[j][t] = *reinterpret_cast<const wl_f4u*>(w_lane + (int64_t)16 * t * D + ((c0 + j) << 4));
-                rb[j] = *reinterpret_cast<const wl_f4u*>(x_lane + ((c0 + j) << 4));
-            }
-        wl_f4u la[kMlpTiles], lb;   // the partial last chunk (last share), requested up front as well
-        const bool has_last = share == kShares - 1 && (D & 15);
-        if (has_last) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bool in = (kFull << 4) + 4 * g + s < D;
-#pragma unroll
-                for (int t = 0; t < kMlpTiles; ++t) la[t][s] = in ? w_lane[(int64_t)16 * t * D + (kFull << 4) + s] : 0.f;
-                lb[s] = in ? x_lane[(kFull << 4) + s] : 0.f;
-            }
-        }
-        for (int c = c0; c < c1; c += kDepth) {
-#pragma unroll
-            for (int j = 0; j < kDepth; ++j) {
-                if (c + j < c1) {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s)
-#pragma unroll
-                        for (int t = 0; t < kMlpTiles; ++t) h[t] = mfma4(ra[j][t][s], rb[j][s], h[t]);
-                    if (c + j + kDepth < c1) {
-#pragma unroll
-                        for (int t = 0; t < kMlpTiles; ++t)
-                            ra[j][t] = *reinterpret_cast<const wl_f4u*>(w_lane + (int64_t)16 * t * D + ((c + j + kDepth) << 4));
-                        rb[j] = *reinterpret_cast<const wl_f4u*>(x_lane + ((c + j + kDepth) << 4));
-                    }
-                }
-            }
-        }
-        if (has_last) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int t = 0; t < kMlpTiles; ++t) h[t] = mfma4(la[t][s], lb[s], h[t]);
-        }
-        // shares 1..3 hand their partial accumulators to share 0 through LDS: [net][share - 1][tile][lane] f32x4
-        if (share > 0) {
-#pragma unroll
-            for (int t = 0; t < kMlpTiles; ++t)
-                *reinterpret_cast<f32x4*>(hbuf + (((which * 3 + share - 1) * kMlpTiles + t) * 64 + lane) * 4) = h[t];
-        }
-        __syncthreads();
-        if (share == 0) {
-#pragma unroll
-            for (int k = 0; k < kShares - 1; ++k)
-#pragma unroll
-                for (int t = 0; t < kMlpTiles; ++t)
-                    h[t] += *reinterpret_cast<const f32x4*>(hbuf + (((which * 3 + k) * kMlpTiles + t) * 64 + lane) * 4);
-            const f32x4 o4 = eval_tail<ACT>(W, h, lane);
-            const int r_out = e0 + m;
-            if (g == 0) {
-                if (which == 1) {
-                    if (r_out < b.n_envs) pio.values[r_out] = o4[0];
-                } else {
-                    const float std0 = pio.std[0], std1 = pio.std[1];
-                    const float2 av = make_float2(fmaf(std0, z0, o4[0]), fmaf(std1, z1, o4[1]));
-                    act_lds[m] = av;
-                    if (r_out < b.n_envs) {
-                        reinterpret_cast<float2*>(pio.actions)[r_out] = av;
-                        reinterpret_cast<float2*>(pio.mu)[r_out] = make_float2(o4[0], o4[1]);
-                        pio.log_prob[r_out] = fmaf(-0.5f, fmaf(z0, z0, z1 * z1), -(log_fast(std0) + log_fast(std1)) - kLog2PiA);
-                    }
-                }
-            }
-        }
-    }
     __syncthreads();
     if (tid < 64) {
         const int wid = tid & 3, e = e0 + (tid >> 2);
@@ -838,15 +557,11 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
             // (the action through a buffer resource, like the state rows: as a plain global load the scheduler parked it behind
             // the parameter block, waiting for a register the burst still had in flight -- a second round trip)
             float2 a;
-            if constexpr (POLICY) {
-                a = act_lds[tid >> 2];
-            } else {
-                float2* ap = const_cast<float2*>(actions);
-                asm volatile("" : "+s"(ap));   // launder the read-only / no-alias argument: its loads are otherwise free to cross the boundary below
-                const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(ap, 0, b.n_envs * 8, 0x00020000);
-                a.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ar, e * 8, 0, 0));
-                a.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ar, e * 8, 4, 0));
-            }
+            float2* ap = const_cast<float2*>(actions);
+            asm volatile("" : "+s"(ap));   // launder the read-only / no-alias argument: its loads are otherwise free to cross the boundary below
+            const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(ap, 0, b.n_envs * 8, 0x00020000);
+            a.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ar, e * 8, 0, 0));
+            a.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ar, e * 8, 4, 0));
             const Rows S = make_rows(b.state, b.stride);
             VehRows<4> rows = load_veh_rows<4>(S, e, wid);
             WlElevParams p;
@@ -872,8 +587,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
                     __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 };
-                // (the collector's other wavefronts are busy with the nets: it draws its resets inline)
-                const HelperReset<ElevReset, kFusedEnvs> reset_src{&resets, e0, !POLICY};
+                const HelperReset<ElevReset, kFusedEnvs> reset_src{&resets, e0, true};
                 (void)elev_env_step<4>(p, vd, b, ground, a, rows, out, seed, step, S, e, wid, wid == 0, blk_metrics, nullptr, nullptr, reset_src, pose);
             }
         }
@@ -884,12 +598,10 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
             if (m != 0.f) atomicAdd(metric_shard(b, m_slot) + tid, m);
         }
     } else {
-        if constexpr (!POLICY) {
-            if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics
-                const int j = tid - 64;
-                resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs,
-                               [&] { return draw_elev_reset(p_arg, ground, (uint32_t)(b.env_offset + e0 + j), step, seed); });
-            }
+        if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics
+            const int j = tid - 64;
+            resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs,
+                           [&] { return draw_elev_reset(p_arg, ground, (uint32_t)(b.env_offset + e0 + j), step, seed); });
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();
@@ -1043,8 +755,8 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
 //      physics as in elev_rollout_persistent_kernel (rows and bookkeeping parked in LDS between steps: registers are the
 //      scarce resource here -- every wavefront's allocation carries the 96 weight registers)
 //   D  all wavefronts: the 16 x 676 height rays of the post-step poses, into the storage's next observation row AND the LDS rows
-// Three s_barriers per step.  (The one-launch-per-step collector above streams both matrices from L2 for 16 rows per step
-// and block -- 90 MB per step chip-wide -- and is bound by exactly that.)
+// Three s_barriers per step.  (A one-launch-per-step collector, both first-layer matrices streamed from L2 for 16 rows per
+// step and block -- 90 MB per step chip-wide -- was bound by exactly that: DESIGN.md section 7.)
 // The CRITIC is not in here: its values are not needed to step, and the caller evaluates all K + 1 observation rows in one
 // batched pass afterwards.  Measured with the critic inside (its first layer streamed from L2 by wavefronts 1..7 beside
 // the physics, wavefront 1 finishing the net): 55 us per step against 33.7 without -- not the streaming itself (pacing it
@@ -1052,6 +764,15 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
 // inside the sub-step loop of the lone physics wavefront.
 // Arithmetic: layer 1 is summed in eight partial sums per unit (wl_actor_critic_act: four): equal to that kernel to rounding,
 // not bit for bit; the env.step is elev_env_step's.
+// what the collector kernel's policy phase reads and fills: rows k of an rsl_rl RolloutStorage
+struct PolicyIo {
+    WlMlp actor, critic;
+    const float* std;
+    const float* obs_in;   // [n][689] observation row k
+    float *actions, *mu, *log_prob, *values;
+    int deterministic;
+};
+
 constexpr int kColWavesA = 8;                                                  // wavefronts sharing the actor's first layer
 constexpr int kColChunks = (WL_ELEV_OBS_DIM + 15) / 16;                        // 44 (the last holds one feature)
 constexpr int kColMaxA = (kColChunks + kColWavesA - 1) / kColWavesA;           // 6
@@ -1404,38 +1125,12 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
         const WlStepOut o = step_out_at(*out, k, obs_step_stride, vec_step_stride);
         const float2* a = (const float2*)(actions + (int64_t)k * b->n_envs * 2);
         if (quad) {   // step + scan in one launch
-            elev_step_scan_kernel<false><<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k, PolicyIo{});
+            elev_step_scan_kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k);
         } else {
             elev_step_kernel<1><<<grid_for(b->n_envs), kBlock, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k);
             launch_elev_scan(p, b, g, o.obs, (hipStream_t)stream);
         }
     }
-    return launch_status();
-}
-
-int wl_elev_collect_step(const WlElevParams* p, const WlEnvBuffers* b, const WlHeightField* hf, const WlMlp* actor, const WlMlp* critic,
-                         const float* std, const WlCollectIo* io, const WlStepOut* out, int32_t deterministic, uint64_t seed,
-                         uint64_t step, void* stream) {
-    int rc = check_elev(p, b, hf);
-    if (rc != WL_OK) return rc;
-    if (!use_quad(b)) return WL_EINVAL;   // the one-launch collector is the quad form's (n <= 32 768); beyond: act + step
-    if (!actor || !critic || !std || !io || !io->obs_in || !io->actions || !io->mu || !io->log_prob || !io->values) return WL_EINVAL;
-    if (!out || !out->obs || !out->reward || !out->terminated || !out->truncated) return WL_EINVAL;
-    for (const WlMlp* m : {actor, critic})
-        if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3 || m->hidden != kMlpHidden || m->in_dim != WL_ELEV_OBS_DIM ||
-            (m->activation != WL_ACT_ELU && m->activation != WL_ACT_RELU))
-            return WL_EINVAL;
-    if (actor->out_dim != 2 || critic->out_dim != 1 || actor->activation != critic->activation) return WL_EINVAL;
-    if (((uintptr_t)io->actions & 7u) || ((uintptr_t)io->mu & 7u) || ((uintptr_t)io->obs_in & 3u)) return WL_EALIGN;
-    const HeightFieldGround g = make_ground(hf);
-    const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
-    const PolicyIo pio{*actor, *critic, std, io->obs_in, io->actions, io->mu, io->log_prob, io->values, deterministic};
-    const int grid = (b->n_envs + kFusedEnvs - 1) / kFusedEnvs;
-    clear_error();
-    if (actor->activation == WL_ACT_ELU)
-        elev_step_scan_kernel<true, WL_ACT_ELU><<<grid, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, nullptr, *out, seed, step, pio);
-    else
-        elev_step_scan_kernel<true, WL_ACT_RELU><<<grid, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, nullptr, *out, seed, step, pio);
     return launch_status();
 }
 

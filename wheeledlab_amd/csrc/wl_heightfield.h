@@ -26,7 +26,7 @@ WL_DEV void hf_decode_pair(uint32_t w, float z_scale, float& a, float& b) {
     b = (float)((int)w >> 16) * z_scale;
 }
 // (Rounds 4 - 5 read two adjacent codes as ONE 2-byte aligned dword gather from the code field, `hf_pair`, two per cell; the aligned
-// 8 bytes around the pair + v_alignbit instead -- what the LDS patch reads need, wl_elev.hip -- was slower from global memory: the
+// 8 bytes around the pair + v_alignbit instead -- what the LDS-patch scan of rounds 4 - 6 read -- was slower from global memory: the
 // gather-form scan at 262 144 envs 504 against 482 us per launch, the fused 4096-env step 25.2 against 25.0 us.  The depth walk still
 // reads its code pairs that way, from its own copy of the codes: wl_depth_dev.h.)
 // a cell's four corner heights from the ROW-PAIR table (WlHeightField.pair, ABI 23: pair[j][i] = code[j][i] | code[j + 1][i] << 16):

@@ -208,7 +208,6 @@ inline bool flags_ok(const WlEnvBuffers* b) {
     const int f = b->flags;
     if (f & ~WL_FLAG_MASK) return false;
     if ((f & WL_FLAG_STREAM) && (f & WL_FLAG_NO_STREAM)) return false;
-    if ((f & WL_FLAG_SCAN_LDS) && (f & WL_FLAG_SCAN_GATHER)) return false;
     return true;
 }
 // streaming (non-temporal) stores: forced by the flags, otherwise when `bytes` (what the launch writes and will not read again

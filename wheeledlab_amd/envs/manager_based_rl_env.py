@@ -352,12 +352,7 @@ class ManagerBasedRLEnv:
         self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
-        # curriculum: evaluated inside _reset_idx in IsaacLab, i.e. on steps where >= 1 env resets; every built-in
-        # term is a no-op off episode boundaries, so the (synchronising) any() runs once per max_episode_length steps
-        if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
-            if bool((terminated | truncated).any()):
-                for name, term in self._flat.curriculum:
-                    term.func(self, None, **term.params)
+        self._curriculum_at_boundary(lambda: terminated | truncated)
         if self.cfg.sync_episode_log:
             if bool((terminated | truncated).any()):
                 self.extras["log"] = dict(self._episode_log(slot).items())
@@ -378,19 +373,6 @@ class ManagerBasedRLEnv:
             raise ValueError("custom (torch) reward terms run between steps; use step()")
         b = self._batch
         a = storage.actions[k]
-        if self._task == "elevation" and b.n <= 32768 and os.environ.get("WL_ELEV_COLLECT", "0") == "1":
-            # policy step, env.step() and the height scan in ONE launch (wl_elev_collect_step): measured 5 % SLOWER than the
-            # two launches below (the 16-row blocks double the first-layer operand traffic), so it is opt-in
-            b.collect_step(actor_critic, storage, k)
-            self.action_manager.prev_action = a
-            self.common_step_counter += 1
-            self._sim_step_counter += self.cfg.decimation
-            self._run_frame_hooks()
-            if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
-                if bool(storage.dones[k].any()):
-                    for name, term in self._flat.curriculum:
-                        term.func(self, None, **term.params)
-            return
         # (running only the actor's half here and the critic's on a side stream next to the env's launches was measured
         # SLOWER -- elevation 7.1e7 -> 5.8e7 env-steps/s: the event / stream hand-off per step costs more than the overlap gains)
         # (planes_fresh: the parameters only change between collections, so the bf16 form's weight planes built at k = 0 hold)
@@ -404,10 +386,31 @@ class ManagerBasedRLEnv:
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
+        self._curriculum_at_boundary(lambda: storage.dones[k])
+
+    def _curriculum_at_boundary(self, dones):
+        """curriculum: evaluated inside _reset_idx in IsaacLab, i.e. on steps where >= 1 env resets; every built-in term is a
+        no-op off episode boundaries, so the (synchronising) any() -- and `dones()`, the step's done flags -- runs once per
+        max_episode_length steps"""
         if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
-            if bool(storage.dones[k].any()):
+            if bool(dones().any()):
                 for name, term in self._flat.curriculum:
                     term.func(self, None, **term.params)
+
+    def _in_curriculum_segments(self, storage, run):
+        """storage.n_steps steps as launches run(start, count), cut at curriculum boundaries (common_step_counter %
+        max_episode_length == 0), where IsaacLab's _reset_idx would evaluate the curriculum terms, so reward weights change on
+        the same step as they do when stepping"""
+        K, k = storage.n_steps, 0
+        while k < K:
+            seg = K - k
+            if self._has_curriculum:
+                seg = min(seg, self.max_episode_length - self.common_step_counter % self.max_episode_length)
+            run(k, seg)
+            k += seg
+            self.common_step_counter += seg
+            self._sim_step_counter += seg * self.cfg.decimation
+            self._curriculum_at_boundary(lambda: storage.dones[k - 1])
 
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
@@ -422,20 +425,9 @@ class ManagerBasedRLEnv:
         cut at curriculum boundaries exactly as rollout_policy() cuts the drift task's; call finish_collection() after it."""
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
-        b, K, k = self._batch, storage.n_steps, 0
-        while k < K:
-            seg = K - k
-            if self._has_curriculum:
-                seg = min(seg, self.max_episode_length - self.common_step_counter % self.max_episode_length)
-            b.collect_rollout(actor_critic, storage, start=k, count=seg)
-            k += seg
-            self.common_step_counter += seg
-            self._sim_step_counter += seg * self.cfg.decimation
-            if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
-                if bool(storage.dones[k - 1].any()):
-                    for name, term in self._flat.curriculum:
-                        term.func(self, None, **term.params)
-        self.action_manager.prev_action = storage.actions[K - 1]
+        b = self._batch
+        self._in_curriculum_segments(storage, lambda k, n: b.collect_rollout(actor_critic, storage, start=k, count=n))
+        self.action_manager.prev_action = storage.actions[storage.n_steps - 1]
 
     def finish_collection(self, storage, n_steps: int | None = None):
         """after the last collect_step(): the env's own observation buffer and episode log catch up with the storage"""
@@ -455,19 +447,8 @@ class ManagerBasedRLEnv:
             raise NotImplementedError("fused policy rollouts exist for the drift task (14-dim observation)")
         if self._has_custom_rewards:
             raise ValueError("custom (torch) reward terms run between steps; use step()")
-        b, K, k = self._batch, storage.n_steps, 0
-        while k < K:
-            seg = K - k
-            if self._has_curriculum:
-                seg = min(seg, self.max_episode_length - self.common_step_counter % self.max_episode_length)
-            b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=seg)
-            k += seg
-            self.common_step_counter += seg
-            self._sim_step_counter += seg * self.cfg.decimation
-            if self._has_curriculum and self.common_step_counter % self.max_episode_length == 0:
-                if bool(storage.dones[k - 1].any()):
-                    for name, term in self._flat.curriculum:
-                        term.func(self, None, **term.params)
+        b, K = self._batch, storage.n_steps
+        self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))
         self.obs_buf = {"policy": b.obs}
         self.extras["log"] = self._episode_log(None) if b.metrics_slots == 1 else EpisodeLog(
