@@ -38,11 +38,12 @@ def elev_params():
 
 def ground_fn(hf, probe=None):
     """probe (see vehicle.substep): `cell_margin` -- per env the smallest distance, in cells, of a wheel's sample point from a
-    cell line of the grid (where the bilinear surface's normal jumps), minimised over every call"""
-    h, x0, y0, cell = hf
+    cell line of the grid (where the bilinear surface's normal jumps), minimised over every call.  hf: heightfield.unpack's forms
+    (a 5-tuple carries the field's outside_z)"""
+    h, x0, y0, cell, outside = H.unpack(hf)
 
     def g(xy):
-        z, n, _ = H.sample(h, x0, y0, cell, xy[:, 0], xy[:, 1], outside=0.0)
+        z, n, _ = H.sample(h, x0, y0, cell, xy[:, 0], xy[:, 1], outside=outside)
         if probe is not None:
             u = (f32(xy[:, 0]) - F(x0)) / F(cell)
             v = (f32(xy[:, 1]) - F(y0)) / F(cell)
@@ -80,7 +81,8 @@ def reset_envs(p, state, episode_len, hf, ids, seed, step, env_offset=0):
     gid = np.asarray(ids) + env_offset
     u = PH.uniform4(gid, step, S_RESET, seed)
     x, y = sym(u[0], p.reset_xy), sym(u[1], p.reset_xy)
-    zt, _, _ = H.sample(*hf, x, y, outside=0.0)
+    h, x0, y0, cell, outside = H.unpack(hf)
+    zt, _, _ = H.sample(h, x0, y0, cell, x, y, outside=outside)
     state[PX, ids], state[PX + 1, ids] = x, y
     state[PX + 2, ids] = np.maximum(F(p.reset_z), zt + F(p.spawn_clearance))
     yaw = sym(u[2], p.reset_yaw)
@@ -99,7 +101,8 @@ def reset_envs(p, state, episode_len, hf, ids, seed, step, env_offset=0):
 
 
 def height_map(p, state, hf):
-    """E1: 26 x 26 yaw-aligned grid of terrain heights relative to the base plane, clipped (x fastest)"""
+    """E1: 26 x 26 yaw-aligned grid of terrain heights relative to the base plane, clipped (x fastest).  Sampled WITHOUT the contact
+    samplers' far-border guard, as wl_elev.hip::scan_cell does; a ray off the grid misses (+inf, clipped), whatever outside_z is"""
     n = state.shape[1]
     k = np.arange(N_RAYS, dtype=np.float32)
     g = (F(-0.5 * p.scan_size) + k * F(p.scan_res)).astype(F)
@@ -108,7 +111,7 @@ def height_map(p, state, hf):
     c, s = yaw_cs(state[QW:QW + 4].T)
     wx = state[PX][:, None] + c[:, None] * lx[None] - s[:, None] * ly[None]
     wy = state[PX + 1][:, None] + s[:, None] * lx[None] + c[:, None] * ly[None]
-    z, _, inside = H.sample(*hf, wx.reshape(-1), wy.reshape(-1), outside=0.0)
+    z, _, inside = H.sample(*H.unpack(hf)[:4], wx.reshape(-1), wy.reshape(-1), guard=False)
     z, inside = z.reshape(n, -1), inside.reshape(n, -1)
     rz = state[PX + 2]
     val = E.world_height_map(rz, z, rz, p.scan_offset, p.elev_z0)

@@ -46,19 +46,32 @@ def make_terrain(n=800, cell=0.05, seed=0):
     return decode(quantize(h)), F(-half), F(-half), F(cell)
 
 
-def sample(hf, x0, y0, cell, x, y, outside=0.0):
+def unpack(hf):
+    """a field as the task oracles take it -> (height, x0, y0, cell, outside_z): `(height, x0, y0, cell)` or, with the height of the
+    plane beyond the grid (WlHeightField.outside_z), `(height, x0, y0, cell, outside_z)`; a 4-tuple's plane is z = 0"""
+    h, x0, y0, cell, *rest = hf
+    return h, x0, y0, cell, (float(rest[0]) if rest else 0.0)
+
+
+def sample(hf, x0, y0, cell, x, y, outside=0.0, guard=True):
     """bilinear height and unit normal at world (x, y) [N]; outside the grid -> height `outside`, normal +z.
-    -> z [N], n [N,3], inside [N] bool"""
+    -> z [N], n [N,3], inside [N] bool.  The wheel-contact samplers' definition (wl_heightfield.h): u, v clamped to
+    [0, n - 1 - 1e-3] in fp32 (the far-border guard) and the integer cell clamped to n - 2, so that the guard's vanishing on
+    fields 32 770 or more points wide (n - 1 - 1e-3 rounds to n - 1 there) still reads inside the grid; `guard=False` is the
+    height scan's (wl_elev.hip::scan_cell): no clamp of u, v -- the cell clamp alone keeps the read on the grid"""
     hf = f32(hf)
     ny, nx = hf.shape
     inv = F(1) / F(cell)
     u = (f32(x) - F(x0)) * inv
     v = (f32(y) - F(y0)) * inv
     inside = (u >= 0) & (v >= 0) & (u < nx - 1) & (v < ny - 1)
-    uc = np.clip(u, 0, nx - 1 - 1e-3).astype(F)
-    vc = np.clip(v, 0, ny - 1 - 1e-3).astype(F)
-    i = np.floor(uc).astype(np.int32)
-    j = np.floor(vc).astype(np.int32)
+    if guard:
+        uc = np.clip(u, F(0), F(nx - 1) - F(1e-3)).astype(F)
+        vc = np.clip(v, F(0), F(ny - 1) - F(1e-3)).astype(F)
+    else:
+        uc, vc = np.where(inside, u, F(0)).astype(F), np.where(inside, v, F(0)).astype(F)
+    i = np.minimum(np.floor(uc), nx - 2).astype(np.int32)
+    j = np.minimum(np.floor(vc), ny - 2).astype(np.int32)
     fu, fv = (uc - i).astype(F), (vc - j).astype(F)
     h00, h10 = hf[j, i], hf[j, i + 1]
     h01, h11 = hf[j + 1, i], hf[j + 1, i + 1]

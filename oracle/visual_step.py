@@ -57,7 +57,8 @@ def reset_envs(p, state, episode_len, cells, ids, seed, step, env_offset=0, hf=N
     state[PX + 2, ids] = F(p.reset_z)
     if hf is not None:
         from . import heightfield as H
-        zt, _, _ = H.sample(hf[0], hf[1], hf[2], hf[3], state[PX, ids], state[PX + 1, ids], outside=0.0)
+        h, x0, y0, cell, outside = H.unpack(hf)
+        zt, _, _ = H.sample(h, x0, y0, cell, state[PX, ids], state[PX + 1, ids], outside=outside)
         state[PX + 2, ids] = (F(p.reset_z) + zt.astype(F)).astype(F)
     yaw = u[1] * F(2.0 * math.pi)                                                     # U(0, 360) deg
     state[QW, ids], state[QW + 1, ids], state[QW + 2, ids], state[QW + 3, ids] = np.cos(yaw * F(.5)), 0, 0, np.sin(yaw * F(.5))
@@ -127,12 +128,14 @@ def observe(p, state, trav):
 
 def observe_depth(p, state, hf, max_depth):
     """observation of the visual-depth extension task (BASELINE config 5): distance_to_image_plane 60 x 80 against the heightfield
-    (oracle/depth.c) | base_lin_vel | base_ang_vel | last_action"""
+    (oracle/depth.c) | base_lin_vel | base_ang_vel | last_action.  hf: a 5-tuple carries the field's outside_z"""
     from . import depth as D
+    from . import heightfield as H
     R = matrix_from_quat(state[QW:QW + 4].T)
     v_b = np.einsum("nji,nj->ni", R, state[VX:VX + 3].T).astype(F)
     w_b = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
-    img = D.depth(p, state[PX:PX + 3].T.copy(), state[QW:QW + 4].T.copy(), hf, max_depth).reshape(state.shape[1], -1)
+    img = D.depth(p, state[PX:PX + 3].T.copy(), state[QW:QW + 4].T.copy(), H.unpack(hf)[:4], max_depth,
+                  H.unpack(hf)[4]).reshape(state.shape[1], -1)
     return np.concatenate([img, v_b, w_b, np.clip(state[ACT0:ACT0 + 2].T, F(-1), F(1))], -1).astype(F)
 
 

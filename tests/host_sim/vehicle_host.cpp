@@ -55,4 +55,32 @@ void hs_vehicle_integrate(const WlVehicleParams* vp, float sim_dt, int decimatio
     }
 #undef RUN
 }
+
+// The contact samplers alone (tests/test_heightfield_geometry_cpu.py): paths [n_paths][n_pts] of sample points, z [n_paths][n_pts],
+// normals [n_paths][n_pts][3].  HeightFieldGround::sample_full on every point; HeightFieldGroundCached on the same points, paths
+// 4 k .. 4 k + 3 as the four wheels of one sampler (each keeps its wheel's cell between calls, as in the lane-form step).
+void hs_heightfield_probe(const WlHeightField* hf, int n_paths, int n_pts, const float* x, const float* y, float* z, float* nrm,
+                          uint8_t* inside, float* z_cached, float* nrm_cached) {
+    const HeightFieldGround g = make_ground(hf);
+    for (int k = 0; k < n_paths * n_pts; ++k) {
+        V3 n;
+        inside[k] = g.sample_full(x[k], y[k], z[k], n);
+        nrm[3 * k] = n.x, nrm[3 * k + 1] = n.y, nrm[3 * k + 2] = n.z;
+    }
+    for (int p0 = 0; p0 < n_paths; p0 += 4) {
+        const HeightFieldGroundCached c(g);
+        for (int t = 0; t < n_pts; ++t)
+            for (int w = 0; w < 4 && p0 + w < n_paths; ++w) {
+                const int k = (p0 + w) * n_pts + t;
+                V3 n;
+                switch (w) {
+                    case 0: c.sample_wheel<0>(x[k], y[k], z_cached[k], n); break;
+                    case 1: c.sample_wheel<1>(x[k], y[k], z_cached[k], n); break;
+                    case 2: c.sample_wheel<2>(x[k], y[k], z_cached[k], n); break;
+                    default: c.sample_wheel<3>(x[k], y[k], z_cached[k], n); break;
+                }
+                nrm_cached[3 * k] = n.x, nrm_cached[3 * k + 1] = n.y, nrm_cached[3 * k + 2] = n.z;
+            }
+    }
+}
 }

@@ -67,9 +67,10 @@ class DeviceHeightField:
     vertical scale, z = code * z_scale.  `heightfield` is `(height, x0, y0, cell)` with float heights (quantised: terrain.
     quantize_heights' rule, z_scale 2^-13 m unless the range needs more) or `(codes int16, x0, y0, cell, z_scale)`, arrays or
     tensors; or another DeviceHeightField on the same device (shared).  `.heights`: the decoded fp32 grid -- exactly the values
-    every kernel sees (what tests hand to the oracle)."""
+    every kernel sees (what tests hand to the oracle).  `outside_z`: the height of the plane beyond the grid (what the contact samplers
+    and the depth walk meet there); None keeps a shared field's own, else 0."""
 
-    def __init__(self, heightfield, device, outside_z: float = 0.0):
+    def __init__(self, heightfield, device, outside_z: float | None = None):
         from .terrain import default_z_scale
         self.device = _canonical_device(device)
         if isinstance(heightfield, DeviceHeightField):
@@ -78,6 +79,7 @@ class DeviceHeightField:
                 raise ValueError(f"a DeviceHeightField lives on {src.device}; it cannot be shared with {self.device}")
             self.codes, self.z_scale, self.heights, self.pairs = src.codes, src.z_scale, src.heights, src.pairs
             self.x0, self.y0, self.cell = src.x0, src.y0, src.cell
+            outside_z = src.outside_z if outside_z is None else outside_z
         else:
             h, x0, y0, cell, *rest = heightfield
             h = torch.as_tensor(h)
@@ -102,7 +104,7 @@ class DeviceHeightField:
             self.heights = self.codes.to(torch.float32) * torch.tensor(self.z_scale, dtype=torch.float32, device=self.device)
             self.x0, self.y0, self.cell = float(x0), float(y0), float(cell)
             self.pairs = None
-        self.outside_z = float(outside_z)
+        self.outside_z = float(0.0 if outside_z is None else outside_z)
         ny, nx = self.codes.shape
         self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, None)
         if self.pairs is None:
@@ -634,7 +636,7 @@ class DepthCamera:
 
     IMG_H, IMG_W = 60, 80
 
-    def __init__(self, heightfield, device="cuda:0", params: A.WlVisualParams | None = None, outside_z: float = 0.0):
+    def __init__(self, heightfield, device="cuda:0", params: A.WlVisualParams | None = None, outside_z: float | None = None):
         from .params import visual_params
         self.lib = A.load()
         self.device = torch.device(device)

@@ -155,9 +155,11 @@ struct ScanPose {
 // keep in LDS) and a ray costs ~35 VALU instructions instead of ~62 (the ray's metres -> rotate -> translate -> grid units chain,
 // four float compares for the inside test and 64-bit address arithmetic went; the scan was as much instruction- as gather-bound:
 // 676 rays x 62 / 64 lanes = 655 wavefront-instructions per env against ~1100 clocks per env and CU).  Same definition
-// (oracle/elev_step.py::height_map, heightfield.py::sample); fp32 rounding of the ray position differs by a few ulp of the grid
-// coordinate (<= 1e-4 cell) from the metre chain, and the sampler's 1e-3-cell guard at the far border is not needed (the
-// integer cell index is clamped instead): both far inside the parity tolerance (2e-5 m on the height map).
+// (oracle/elev_step.py::height_map, heightfield.py::sample with guard=False); fp32 rounding of the ray position differs by a few ulp
+// of the grid coordinate from the metre chain (tests/heightfield_reference.py derives the bound).  The scan has NO far-border guard:
+// the contact samplers clamp u, v to n - 1 - 1e-3 (wl_heightfield.h), the scan samples the ray's own cell -- on a border that slopes
+// the two differ by up to 1e-3 cell x the slope (1e-4 m at 0.1 m cells and a slope of 1), beyond the scan's 2e-5 m, so the scan's
+// definition is the guard-free one (tests/test_gpu_heightfield_geometry.py holds every scan form to it).
 struct ScanFrame {
     float u0, v0, ux, vx, uy, vy, pz;
 };
