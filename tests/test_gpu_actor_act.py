@@ -22,7 +22,8 @@ def _nets(D, activation, seed):
 
 
 @pytest.mark.parametrize("activation", ["elu", "relu"])
-@pytest.mark.parametrize("D,n", [(689, 4096), (3208, 512), (689, 100), (3208, 4096), (689, 16401), (14, 300), (16, 64), (33, 17), (1, 5)])
+@pytest.mark.parametrize("D,n", [(689, 4096), (3208, 512), (689, 100), (3208, 4096), (689, 16401), (14, 300), (16, 64), (33, 17), (1, 5),
+                                 (4808, 512), (4808, 4097)])   # 4808: the visual-depth agent (VISUAL_DEPTH_CONFIG)
 def test_policy_step_matches_oracle(D, n, activation):
     ac, actor_np, critic_np = _nets(D, activation, seed=D + n)
     g = torch.Generator(device=DEV).manual_seed(1)
@@ -123,7 +124,7 @@ def test_actor_and_critic_halves_equal_the_joint_launch():
 
 @pytest.mark.parametrize("two_launches", [False, True])
 @pytest.mark.parametrize("D,n,activation", [(689, 4096, "elu"), (3208, 1024, "elu"), (3208, 1000, "relu"), (100, 77, "elu"), (128, 300, "relu"),
-                                            (3208, 2000, "elu"), (689, 1700, "relu")])
+                                            (3208, 2000, "elu"), (689, 1700, "relu"), (4808, 1024, "elu"), (4808, 1500, "relu")])
 def test_bf16_plane_form_matches_oracle_and_the_f32_kernel(D, n, activation, two_launches):
     """wl_actor_critic_act_planes (layer 1 on the bf16 pipe, observation rows split hi + lo in registers: 16 mantissa bits), in
     its one-launch form (feature shares folded through LDS; row tiles per block 1 / 2 / 4 by the row count) and its two-launch

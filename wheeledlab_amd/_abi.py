@@ -140,7 +140,7 @@ class WlPolicyRollout(C.Structure):
 
 
 PPO_NUM_PARAMS, PPO_PARTIAL_STRIDE, PPO_BLOCKS, PPO_OPERAND_FLOATS = 10437, 10440, 256, 23296
-PPO_CTRL_LR, PPO_CTRL_NORM2, PPO_CTRL_STATS = 0, 2, 4
+PPO_CTRL_LR, PPO_CTRL_NORM2, PPO_CTRL_STATS, PPO_CTRL_STD = 0, 2, 4, 8
 
 
 class WlPpoBatch(C.Structure):
