@@ -1,6 +1,6 @@
-"""DriftBatch: device buffers of one shard of drift envs + thin calls into the C ABI.
+"""DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch: device buffers of one shard of a task's envs + thin calls into the C ABI.
 
-PyTorch is plumbing here: it owns the HBM allocations and the stream; every kernel is ours (csrc/wl_drift.hip).
+PyTorch is plumbing here: it owns the HBM allocations and the stream; every kernel is ours (csrc/*.hip).
 """
 from __future__ import annotations
 
@@ -122,59 +122,46 @@ class DeviceHeightField:
         return self.heights, self.x0, self.y0, self.cell
 
 
-class _MetricsView:
-    """`metrics_raw` is what the kernels add into: [slots][WL_M_SHARDS][WL_M_COUNT].  `metrics` is the logical value
-    (sum over the shards): [WL_M_COUNT] for one accumulator, [slots][WL_M_COUNT] for a ring; a fresh tensor per read."""
+def ring_plan(step0: int, n_steps: int, slots: int):
+    """How a persistent launch of `n_steps` steps from step `step0` runs on a metric ring of `slots` slots.  The launch folds all
+    its steps into slot step0 % R and clears slot (step0 + n) % R for its successor.  Returns (segments, zero):
+    segments -- the launches as (first step, steps): [(0, n)], or [(0, 1), (1, n - 1)] when n is a multiple of R: those two
+    slots are then the same and the C ABI refuses the launch (WL_EINVAL).  Like n single steps, the split leaves the ring without
+    the first step's counts (a ring of R slots holds R - 1 steps);
+    zero -- the slots the host clears before the launches: those of the steps a launch folds away, which would otherwise keep
+    the counts of an earlier pass over the ring."""
+    if slots <= 1 or n_steps <= 1:
+        return [(0, n_steps)], []
+    segments = [(0, 1), (1, n_steps - 1)] if n_steps % slots == 0 else [(0, n_steps)]
+    zero = sorted({(step0 + k0 + i) % slots for k0, k in segments for i in range(1, k)})
+    return segments, zero
 
-    @property
-    def metrics(self) -> torch.Tensor:
-        m = self.metrics_raw.sum(1)
-        return m[0] if self.metrics_slots == 1 else m
 
+class _EnvBatch:
+    """What every task's batch holds: n envs resident on one GPU as a SoA state matrix [S_COUNT, stride] (fp32), the per-step
+    output rows, the episode-metric accumulators and the WlEnvBuffers / WlStepOut structs that hand them to the C ABI.  A task
+    names its C entry points (_C_*) and sets `_args`: WlEnvBuffers and the task's own structs, by reference -- the arguments
+    after the params of every reset / step / rollout call.
+
+    `metrics_raw` is what the kernels add into: [slots][WL_M_SHARDS][WL_M_COUNT].  `metrics` is the logical value (sum over the
+    shards): [WL_M_COUNT] for one accumulator, [slots][WL_M_COUNT] for a ring; a fresh tensor per read."""
+
+    OBS_DIM: int
+    LANES = (0, 1, 4)              # the step-kernel forms set_lanes() accepts
+    _C_RESET = _C_STEP = _C_ROLLOUT = _C_PERSISTENT = None
+    _PERSISTENT_NEEDS_ROWS = True  # the persistent kernel writes step k's observation while step k + 1 runs
     pose_epoch = 0       # bumped by everything that moves cars WITHOUT advancing step_count (resets, plugin pose writes)
+    _out_key = None
+    _ring_split_warned = False
 
-    def touch_pose(self):
-        """anything cached per env.step() from the poses (the scene camera's render) is stale after this"""
-        self.pose_epoch = self.pose_epoch + 1
-
-    def set_flags(self, flags: int = 0):
-        """WlEnvBuffers.flags (_abi.FLAG_*): force an instantiation the launchers otherwise pick from the batch size -- the
-        streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa)."""
-        self._bufs.flags = int(flags)
-
-    def _ring_aliases(self, n_steps: int) -> bool:
-        """a persistent launch folds its steps into ring slot step0 % R and clears slot (step0 + n) % R for its successor: with n
-        a multiple of R those are the same slot and the C ABI refuses the launch (WL_EINVAL).  The host layer then runs the
-        rollout as two launches (1 and n - 1 steps) -- the same rollout; like n single steps it leaves the ring without the
-        first step's counts (a ring of R slots holds R - 1 steps)."""
-        return self.metrics_slots > 1 and n_steps > 1 and n_steps % self.metrics_slots == 0
-
-    def _warn_ring_alias(self, n_steps: int):
-        if not getattr(self, "_ring_alias_warned", False):
-            import warnings
-            warnings.warn(f"a persistent rollout of {n_steps} steps with a metric ring of {self.metrics_slots} slots is run as 1 + "
-                          f"{n_steps - 1} steps: the ring then misses the first step's episode counts (choose a rollout length that is "
-                          "not a multiple of metrics_slots to keep them)", stacklevel=3)
-            self._ring_alias_warned = True
-
-
-class DriftBatch(_MetricsView):
-    """n drift envs resident on one GPU as a SoA state matrix [S_COUNT, stride] (fp32)."""
-
-    OBS_DIM = 14
-
-    def __init__(self, n_envs: int, device="cuda:0", params: A.WlDriftParams | None = None, seed: int = 42,
-                 env_offset: int = 0, randomize: bool = True, metrics_slots: int = 1, startup=None):
+    def __init__(self, n_envs: int, device, params, seed: int, env_offset: int, metrics_slots: int, ref_table=None):
         self.lib = A.load()  # raises HipExtensionMissing -- no fallback
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise A.HipExtensionMissing("DriftBatch needs a HIP device (device='cuda:N'); there is no CPU path")
+            raise A.HipExtensionMissing(f"{type(self).__name__} needs a HIP device (device='cuda:N'); there is no CPU path")
         self.n = int(n_envs)
         self.stride = ((self.n + 63) // 64) * 64
-        self.p = params if params is not None else drift_params()
-        self.seed = int(seed)
-        self.env_offset = int(env_offset)
-        self.step_count = 0
+        self.p, self.seed, self.env_offset, self.step_count = params, int(seed), int(env_offset), 0
         dev = self.device
         self.state = torch.zeros(A.S_COUNT, self.stride, dtype=torch.float32, device=dev)
         self.episode_len = torch.zeros(self.stride, dtype=torch.int32, device=dev)
@@ -186,33 +173,43 @@ class DriftBatch(_MetricsView):
         self.terminated = torch.zeros(self.n, dtype=torch.bool, device=dev)
         self.truncated = torch.zeros(self.n, dtype=torch.bool, device=dev)
         self.dones = torch.zeros(self.n, dtype=torch.long, device=dev)   # terminated | truncated, as RSL-RL consumes it
-        g = torch.Generator().manual_seed(self.seed)
-        # reference poses are drawn ONCE at construction (events.py:31,35)
-        self.ref_table = torch.zeros(3, 32, dtype=torch.float32)
-        tr = (startup.track_radius, startup.track_straight) if startup is not None else (0.8, 0.8)
-        self.ref_table[:, : self.p.num_ref_points] = stadium_reference_poses(torch.rand(self.p.num_ref_points, generator=g), *tr)
-        self.ref_table = self.ref_table.to(dev)
-        self._bufs = A.WlEnvBuffers(self.state.data_ptr(), self.episode_len.data_ptr(), self.ref_table.data_ptr(),
-                                    self.metrics_raw.data_ptr(), self.stride, self.n, self.env_offset, self.metrics_slots, 0, 0)
-        self._startup_events(randomize, startup)
+        if ref_table is not None:
+            self.ref_table = ref_table.to(dev)
+        self._bufs = A.WlEnvBuffers(self.state.data_ptr(), self.episode_len.data_ptr(),
+                                    None if ref_table is None else self.ref_table.data_ptr(), self.metrics_raw.data_ptr(),
+                                    self.stride, self.n, self.env_offset, self.metrics_slots, 0, 0)
         self._out = A.WlStepOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
                                 self.truncated.data_ptr(), self.dones.data_ptr())
-
-    # startup events (mushr_drift_env_cfg.py:98-119, 145-154)
-    def _startup_events(self, randomize: bool, su=None):
-        if su is None:  # the RSS drift defaults
-            from .envs.flatten import StartupSpec
-            su = StartupSpec(wheel_mu_s=(0.3, 0.5), wheel_mu_d=(0.3, 0.5), mu_buckets=20, mu_consistent=True,
-                             damping=(10.0, 50.0), mass_add=(0.3, 0.5))
-        apply_startup_events(self.lib, self._bufs, su, self.seed, self._stream(), randomize)
+        self._args = (C.byref(self._bufs),)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    @property
+    def metrics(self) -> torch.Tensor:
+        m = self.metrics_raw.sum(1)
+        return m[0] if self.metrics_slots == 1 else m
+
+    def read_metrics(self, zero: bool = True) -> torch.Tensor:
+        m = self.metrics
+        if zero:
+            self.metrics_raw.zero_()
+        return m
+
+    def touch_pose(self):
+        """anything cached per env.step() from the poses (the scene camera's render) is stale after this"""
+        self.pose_epoch = self.pose_epoch + 1
+
+    def set_flags(self, flags: int = 0):
+        """WlEnvBuffers.flags (_abi.FLAG_*): force an instantiation the launchers otherwise pick from the batch size -- the
+        streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa)."""
+        self._bufs.flags = int(flags)
+
     def set_lanes(self, lanes: int = 0):
-        """step-kernel form: 0 = by env count (quad up to 32 768 envs, lane form with packed axles up to 262 144, with the
-        scalar wheel loop beyond), 1 = lane per env / packed axles, 2 = lane per env / scalar wheel loop, 4 = quad per env"""
-        assert lanes in (0, 1, 2, 4)   # 2: lane form with the scalar wheel loop (drift only; treated as 1 elsewhere)
+        """step-kernel form, one of LANES: 0 = by env count (quad up to 32 768 envs; drift: lane form with packed axles up to
+        262 144, with the scalar wheel loop beyond), 1 = lane per env (drift: packed axles), 2 = drift's lane form with the scalar
+        wheel loop, 4 = quad per env"""
+        assert lanes in self.LANES
         self._bufs.lanes = lanes
 
     def set_dones_output(self, on: bool = True):
@@ -223,8 +220,99 @@ class DriftBatch(_MetricsView):
     def reset(self, mask: torch.Tensor | None = None):
         self.touch_pose()
         m = None if mask is None else mask.to(torch.uint8).contiguous()
-        A.check(self.lib.wl_drift_reset(C.byref(self.p), C.byref(self._bufs), None if m is None else m.data_ptr(),
-                                        self.seed, self.step_count, self._stream()), "wl_drift_reset")
+        A.check(getattr(self.lib, self._C_RESET)(C.byref(self.p), *self._args, None if m is None else m.data_ptr(), self.seed,
+                                                 self.step_count, self._stream()), self._C_RESET)
+
+    def _actions(self, actions: torch.Tensor) -> torch.Tensor:
+        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.n, 2):
+            actions = actions.to(torch.float32).reshape(self.n, 2).contiguous()
+        return actions
+
+    def step(self, actions: torch.Tensor):
+        """actions [n, 2] -> (obs [n, OBS_DIM], reward [n], terminated [n], truncated [n]): the batch's own rows (views)"""
+        return self._step(actions)
+
+    def _step(self, actions, *after_actions):
+        A.check(getattr(self.lib, self._C_STEP)(C.byref(self.p), *self._args, self._actions(actions).data_ptr(), *after_actions,
+                                                C.byref(self._out), self.seed, self.step_count, self._stream()), self._C_STEP)
+        self.step_count += 1
+        return self.obs, self.reward, self.terminated, self.truncated
+
+    def rollout(self, actions: torch.Tensor, obs_out=None, rew_out=None, term_out=None, trunc_out=None, dones_out=None,
+                persistent: bool = False):
+        """K fused steps with pre-staged actions [K, n, 2]; optional [K, ...] output storage (else the batch's own rows,
+        overwritten).  persistent=True runs them as ONE launch with the state in registers (_C_PERSISTENT: quad form,
+        n <= 32 768; the elevation scan / the visual camera of step k overlapped with step k + 1); same results."""
+        self._rollout(actions, (obs_out, rew_out, term_out, trunc_out, dones_out), persistent)
+
+    def _rollout(self, actions, rows, persistent):
+        K = actions.shape[0]
+        assert actions.shape == (K, self.n, 2) and actions.dtype == torch.float32 and actions.is_contiguous()
+        if not persistent:
+            return self._launch_rollout(self._C_ROLLOUT, actions, rows)
+        assert rows[0] is not None or K == 1 or not self._PERSISTENT_NEEDS_ROWS, "a persistent rollout needs per-step output rows"
+        segments = self._ring_segments(K)
+        if len(segments) == 1:
+            return self._launch_rollout(self._C_PERSISTENT, actions, rows)
+        for k0, k in segments:
+            self._launch_rollout(self._C_PERSISTENT, actions[k0:k0 + k], [None if t is None else t[k0:k0 + k] for t in rows])
+
+    def _launch_rollout(self, fn, actions, rows):
+        obs_out, rew_out, term_out, trunc_out, dones_out = rows
+        if obs_out is not None:
+            key = (obs_out.data_ptr(), rew_out.data_ptr(), term_out.data_ptr(), trunc_out.data_ptr(),
+                   None if dones_out is None else dones_out.data_ptr())
+            if self._out_key != key:      # the struct of the caller's storage rows, rebuilt when they change
+                self._out_key, self._out_rows = key, A.WlStepOut(*key)
+            out, os_, vs_ = self._out_rows, self.n * self.OBS_DIM, self.n
+        else:
+            out, os_, vs_ = self._out, 0, 0
+        K = actions.shape[0]
+        A.check(getattr(self.lib, fn)(C.byref(self.p), *self._args, actions.data_ptr(), C.byref(out), os_, vs_, K, self.seed,
+                                      self.step_count, self._stream()), fn)
+        self.step_count += K
+
+    def _ring_segments(self, n_steps: int):
+        """the launches (first step, steps) of a persistent run of n_steps steps from step_count (ring_plan), after clearing the
+        ring slots they fold away; warns once per batch when the run is split"""
+        segments, zero = ring_plan(self.step_count, n_steps, self.metrics_slots)
+        if len(segments) > 1 and not self._ring_split_warned:
+            import warnings
+            warnings.warn(f"a persistent rollout of {n_steps} steps with a metric ring of {self.metrics_slots} slots is run as 1 + "
+                          f"{n_steps - 1} steps: the ring then misses the first step's episode counts (choose a rollout length that is "
+                          "not a multiple of metrics_slots to keep them)", stacklevel=4)
+            self._ring_split_warned = True
+        if zero:
+            self.metrics_raw[zero] = 0
+        return segments
+
+
+class DriftBatch(_EnvBatch):
+    """n drift envs resident on one GPU (csrc/wl_drift.hip)."""
+
+    OBS_DIM = 14
+    LANES = (0, 1, 2, 4)           # 2: lane form with the scalar wheel loop (drift only)
+    _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_drift_reset", "wl_drift_step", "wl_drift_rollout", "wl_drift_rollout_persistent"
+    _PERSISTENT_NEEDS_ROWS = False
+
+    def __init__(self, n_envs: int, device="cuda:0", params: A.WlDriftParams | None = None, seed: int = 42,
+                 env_offset: int = 0, randomize: bool = True, metrics_slots: int = 1, startup=None):
+        p = params if params is not None else drift_params()
+        # reference poses are drawn ONCE at construction (events.py:31,35)
+        ref_table = torch.zeros(3, 32, dtype=torch.float32)
+        tr = (startup.track_radius, startup.track_straight) if startup is not None else (0.8, 0.8)
+        g = torch.Generator().manual_seed(int(seed))
+        ref_table[:, : p.num_ref_points] = stadium_reference_poses(torch.rand(p.num_ref_points, generator=g), *tr)
+        super().__init__(n_envs, device, p, seed, env_offset, metrics_slots, ref_table)
+        self._startup_events(randomize, startup)
+
+    # startup events (mushr_drift_env_cfg.py:98-119, 145-154)
+    def _startup_events(self, randomize: bool, su=None):
+        if su is None:  # the RSS drift defaults
+            from .envs.flatten import StartupSpec
+            su = StartupSpec(wheel_mu_s=(0.3, 0.5), wheel_mu_d=(0.3, 0.5), mu_buckets=20, mu_consistent=True,
+                             damping=(10.0, 50.0), mass_add=(0.3, 0.5))
+        apply_startup_events(self.lib, self._bufs, su, self.seed, self._stream(), randomize)
 
     def observe(self, noise: torch.Tensor | None = None) -> torch.Tensor:
         A.check(self.lib.wl_drift_observe(C.byref(self.p), C.byref(self._bufs),
@@ -234,40 +322,14 @@ class DriftBatch(_MetricsView):
 
     def step(self, actions: torch.Tensor, noise: torch.Tensor | None = None):
         """actions [n,2] fp32 on device -> (obs [n,14], reward [n], terminated u8 [n], truncated u8 [n]) (views)"""
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.n, 2):
-            actions = actions.to(torch.float32).reshape(self.n, 2).contiguous()
-        A.check(self.lib.wl_drift_step(C.byref(self.p), C.byref(self._bufs), actions.data_ptr(),
-                                       None if noise is None else noise.data_ptr(), C.byref(self._out), self.seed,
-                                       self.step_count, self._stream()), "wl_drift_step")
-        self.step_count += 1
-        return self.obs, self.reward, self.terminated, self.truncated
+        return self._step(actions, None if noise is None else noise.data_ptr())
 
     def rollout(self, actions: torch.Tensor, obs_out: torch.Tensor | None = None, rew_out: torch.Tensor | None = None,
                 term_out: torch.Tensor | None = None, trunc_out: torch.Tensor | None = None, persistent: bool = False,
                 dones_out: torch.Tensor | None = None):
         """K fused steps with pre-staged actions [K,n,2]; optional [K,...] output storage (else overwrite).
         persistent=True runs them as ONE launch with the state held in registers (wl_drift_rollout_persistent)."""
-        K = actions.shape[0]
-        assert actions.shape == (K, self.n, 2) and actions.dtype == torch.float32 and actions.is_contiguous()
-        if persistent and self._ring_aliases(K):
-            self._warn_ring_alias(K)
-            cut = lambda t, a, b: None if t is None else t[a:b]
-            for a, b in ((0, 1), (1, K)):
-                self.rollout(actions[a:b], cut(obs_out, a, b), cut(rew_out, a, b), cut(term_out, a, b), cut(trunc_out, a, b), True,
-                             cut(dones_out, a, b))
-            return
-        if obs_out is not None:
-            key = (obs_out.data_ptr(), rew_out.data_ptr(), term_out.data_ptr(), trunc_out.data_ptr(),
-                   None if dones_out is None else dones_out.data_ptr())
-            if getattr(self, "_out_key", None) != key:      # the struct of the caller's storage rows, rebuilt when they change
-                self._out_key, self._out_rows = key, A.WlStepOut(*key)
-            out, os_, vs_ = self._out_rows, self.n * self.OBS_DIM, self.n
-        else:
-            out, os_, vs_ = self._out, 0, 0
-        fn = self.lib.wl_drift_rollout_persistent if persistent else self.lib.wl_drift_rollout
-        A.check(fn(C.byref(self.p), C.byref(self._bufs), actions.data_ptr(), C.byref(out), os_, vs_, K, self.seed,
-                   self.step_count, self._stream()), "wl_drift_rollout")
-        self.step_count += K
+        self._rollout(actions, (obs_out, rew_out, term_out, trunc_out, dones_out), persistent)
 
     def rollout_policy(self, actor_critic, storage, evaluate_critic: bool = True, start: int = 0, count: int | None = None):
         """The runner's collection loop (modified_rsl_rl_runner.py:70-80) as one launch: `count` times
@@ -277,91 +339,46 @@ class DriftBatch(_MetricsView):
         current observation; self.obs ends as the last one."""
         K = storage.n_steps - start if count is None else int(count)
         assert storage.n_envs == self.n and actor_critic.actor.in_dim == self.OBS_DIM and 0 <= start and start + K <= storage.n_steps
-        if self._ring_aliases(K):
-            self.rollout_policy(actor_critic, storage, False, start, 1)
-            return self.rollout_policy(actor_critic, storage, evaluate_critic, start + 1, K - 1)
-        storage.observations[start].copy_(self.obs)
-        if self.metrics_slots > 1 and K > 1:
-            # the launch folds all K steps into ring slot step0 % R and clears slot (step0 + K) % R; the slots it skips
-            # would otherwise keep counts from R steps ago
-            R = self.metrics_slots
-            self.metrics_raw[[(self.step_count + i) % R for i in range(1, K)]] = 0
-        actor, io = actor_critic.actor.struct(), storage.struct(start)
-        A.check(self.lib.wl_drift_rollout_policy(C.byref(self.p), C.byref(self._bufs), C.byref(actor),
-                                                 actor_critic.std.data_ptr(), C.byref(io), K, self.seed, self.step_count,
-                                                 self._stream()), "wl_drift_rollout_policy")
-        self.step_count += K
-        if K > 0:
-            e = start + K
-            self.obs.copy_(storage.observations[e])
-            self.reward.copy_(storage.rewards[e - 1])
-            self.terminated.copy_(storage.terminated[e - 1])
-            self.truncated.copy_(storage.time_outs[e - 1])
-            self.dones.copy_(storage.dones[e - 1])
+        for k0, k in self._ring_segments(K):
+            s = start + k0
+            storage.observations[s].copy_(self.obs)
+            actor, io = actor_critic.actor.struct(), storage.struct(s)
+            A.check(self.lib.wl_drift_rollout_policy(C.byref(self.p), C.byref(self._bufs), C.byref(actor),
+                                                     actor_critic.std.data_ptr(), C.byref(io), k, self.seed, self.step_count,
+                                                     self._stream()), "wl_drift_rollout_policy")
+            self.step_count += k
+            if k > 0:
+                e = s + k
+                self.obs.copy_(storage.observations[e])
+                self.reward.copy_(storage.rewards[e - 1])
+                self.terminated.copy_(storage.terminated[e - 1])
+                self.truncated.copy_(storage.time_outs[e - 1])
+                self.dones.copy_(storage.dones[e - 1])
         if evaluate_critic:
             storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))
         return storage
 
-    def read_metrics(self, zero: bool = True) -> torch.Tensor:
-        m = self.metrics
-        if zero:
-            self.metrics_raw.zero_()
-        return m
 
-
-class ElevBatch(_MetricsView):
+class ElevBatch(_EnvBatch):
     """n elevation-task envs on one GPU (same SoA state matrix; rows WL_S_CMD_* carry the goal command)."""
 
     OBS_DIM = A.ELEV_OBS_DIM
+    _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_elev_reset", "wl_elev_step", "wl_elev_rollout", "wl_elev_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params: A.WlElevParams | None = None, seed: int = 42,
                  env_offset: int = 0, heightfield=None, metrics_slots: int = 1, startup=None):
         from .params import elev_params
         from .terrain import synthetic_heightfield
-        self.lib = A.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("ElevBatch needs a HIP device; there is no CPU path")
-        self.n, self.stride = int(n_envs), ((int(n_envs) + 63) // 64) * 64
-        self.p = params if params is not None else elev_params()
-        self.seed, self.env_offset, self.step_count = int(seed), int(env_offset), 0
-        dev = self.device
-        self.state = torch.zeros(A.S_COUNT, self.stride, dtype=torch.float32, device=dev)
-        self.episode_len = torch.zeros(self.stride, dtype=torch.int32, device=dev)
-        self.metrics_slots = int(metrics_slots)
-        self.metrics_raw = torch.zeros(self.metrics_slots, A.M_SHARDS, A.M_COUNT, dtype=torch.float32, device=dev)
-        self.obs = torch.zeros(self.n, self.OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.terminated = torch.zeros(self.n, dtype=torch.bool, device=dev)
-        self.truncated = torch.zeros(self.n, dtype=torch.bool, device=dev)
-        self.dones = torch.zeros(self.n, dtype=torch.long, device=dev)   # terminated | truncated, as RSL-RL consumes it
-        self.hf = DeviceHeightField(heightfield if heightfield is not None else synthetic_heightfield(), dev)
+        super().__init__(n_envs, device, params if params is not None else elev_params(), seed, env_offset, metrics_slots)
+        self.hf = DeviceHeightField(heightfield if heightfield is not None else synthetic_heightfield(), self.device)
         self.height, self._hf = self.hf.heights, self.hf.struct       # the DECODED fp32 grid (what the kernels see); the ABI struct
+        self._args = (C.byref(self._bufs), C.byref(self._hf))
         # startup events (elevation cfg :387-407): wheel friction fixed (2.0, 1.0), base mass += U(0.2, 0.5)
         if startup is None:
             from .envs.flatten import StartupSpec
             startup = StartupSpec(wheel_mu_s=(2.0, 2.0), wheel_mu_d=(1.0, 1.0), mu_buckets=5, mu_consistent=False,
                                   damping=(1000.0, 1000.0), mass_add=(0.2, 0.5))
-        self._bufs = A.WlEnvBuffers(self.state.data_ptr(), self.episode_len.data_ptr(), None, self.metrics_raw.data_ptr(),
-                                    self.stride, self.n, self.env_offset, self.metrics_slots, 0, 0)
         apply_startup_events(self.lib, self._bufs, startup, self.seed, self._stream())
-        self._out = A.WlStepOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-                                self.truncated.data_ptr(), self.dones.data_ptr())
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def set_lanes(self, lanes: int = 0):
-        """step-kernel form: 0 = by env count (quad up to 32768 envs), 1 = lane per env, 4 = quad per env"""
-        assert lanes in (0, 1, 4)
-        self._bufs.lanes = lanes
-
-    def reset(self, mask: torch.Tensor | None = None):
-        self.touch_pose()
-        m = None if mask is None else mask.to(torch.uint8).contiguous()
-        A.check(self.lib.wl_elev_reset(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf),
-                                       None if m is None else m.data_ptr(), self.seed, self.step_count, self._stream()),
-                "wl_elev_reset")
 
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """observation of the current state into self.obs (or a caller's [n, 689] buffer)"""
@@ -370,74 +387,35 @@ class ElevBatch(_MetricsView):
                                          self._stream()), "wl_elev_observe")
         return out
 
-    def step(self, actions: torch.Tensor):
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.n, 2):
-            actions = actions.to(torch.float32).reshape(self.n, 2).contiguous()
-        A.check(self.lib.wl_elev_step(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), actions.data_ptr(),
-                                      C.byref(self._out), self.seed, self.step_count, self._stream()), "wl_elev_step")
-        self.step_count += 1
-        return self.obs, self.reward, self.terminated, self.truncated
-
-    def rollout(self, actions: torch.Tensor, obs_out=None, rew_out=None, term_out=None, trunc_out=None, dones_out=None,
-                persistent: bool = False):
-        """K fused steps with pre-staged actions [K,n,2]; optional [K,...] output storage (else overwrite).  persistent=True
-        (needs the storage, n <= 32 768) runs them as ONE launch with the state in registers and the height scan of step k
-        overlapped with the integration of step k + 1 (wl_elev_rollout_persistent); same results."""
-        K = actions.shape[0]
-        assert actions.shape == (K, self.n, 2) and actions.dtype == torch.float32 and actions.is_contiguous()
-        if persistent and obs_out is not None and self._ring_aliases(K):
-            cut = lambda t, a, b: None if t is None else t[a:b]
-            for a, b in ((0, 1), (1, K)):
-                self.rollout(actions[a:b], obs_out[a:b], rew_out[a:b], term_out[a:b], trunc_out[a:b], cut(dones_out, a, b), True)
-            return
-        if obs_out is not None:
-            out = A.WlStepOut(obs_out.data_ptr(), rew_out.data_ptr(), term_out.data_ptr(), trunc_out.data_ptr(),
-                              None if dones_out is None else dones_out.data_ptr())
-            os_, vs_ = self.n * self.OBS_DIM, self.n
-        else:
-            assert not persistent or K == 1, "a persistent rollout needs per-step output rows"
-            out, os_, vs_ = self._out, 0, 0
-        if persistent and self.metrics_slots > 1 and K > 1:
-            R = self.metrics_slots       # the launch folds all K steps into slot step0 % R: the slots it skips keep old counts
-            self.metrics_raw[[(self.step_count + i) % R for i in range(1, K)]] = 0
-        fn = self.lib.wl_elev_rollout_persistent if persistent else self.lib.wl_elev_rollout
-        A.check(fn(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), actions.data_ptr(), C.byref(out), os_, vs_, K, self.seed,
-                   self.step_count, self._stream()), "wl_elev_rollout")
-        self.step_count += K
-
     def collect_rollout(self, actor_critic, storage, start: int = 0, count: int | None = None, deterministic: bool = False):
         """rows start .. start + count - 1 of the storage (and observation row start + count) from observation row `start`: the
         runner's whole collection loop as ONE launch (wl_elev_collect_rollout: the actor's first layer in the blocks' registers,
         their observation rows in LDS, the critic beside the physics).  Quad form only (n <= 32 768)."""
         st = storage
         count = st.n_steps - start if count is None else int(count)
-        if self._ring_aliases(count):
-            self.collect_rollout(actor_critic, storage, start, 1, deterministic)
-            return self.collect_rollout(actor_critic, storage, start + 1, count - 1, deterministic)
-        key = (st.observations.data_ptr(), actor_critic.actor.w1.data_ptr(), actor_critic.critic.w1.data_ptr(), actor_critic.std.data_ptr())
-        if getattr(self, "_collect_key", None) != key:
-            assert st.n_envs == self.n and st.observations.shape[2] == self.OBS_DIM and st.observations.is_contiguous()
-            self._collect_key = key
-            self._collect_nets = (actor_critic.actor.struct(), actor_critic.critic.struct())
-        a, c = self._collect_nets
-        obs, k = st.observations, int(start)
-        io = A.WlCollectIo(obs[k].data_ptr(), st.actions[k].data_ptr(), st.mu[k].data_ptr(), st.actions_log_prob[k].data_ptr(),
-                           st.values[k].data_ptr())
-        out = A.WlStepOut(obs[k + 1].data_ptr(), st.rewards[k].data_ptr(), st.terminated[k].data_ptr(), st.time_outs[k].data_ptr(),
-                          st.dones[k].data_ptr())
-        if self.metrics_slots > 1 and count > 1:
-            R = self.metrics_slots       # the launch folds all its steps into slot step0 % R: the slots it skips keep old counts
-            self.metrics_raw[[(self.step_count + i) % R for i in range(1, count)]] = 0
-        A.check(self.lib.wl_elev_collect_rollout(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), C.byref(a), C.byref(c),
-                                                 actor_critic.std.data_ptr(), C.byref(io), C.byref(out), count, int(bool(deterministic)),
-                                                 self.seed, self.step_count, self._stream()), "wl_elev_collect_rollout")
-        self.step_count += count
+        for k0, k in self._ring_segments(count):
+            key = (st.observations.data_ptr(), actor_critic.actor.w1.data_ptr(), actor_critic.critic.w1.data_ptr(), actor_critic.std.data_ptr())
+            if getattr(self, "_collect_key", None) != key:
+                assert st.n_envs == self.n and st.observations.shape[2] == self.OBS_DIM and st.observations.is_contiguous()
+                self._collect_key = key
+                self._collect_nets = (actor_critic.actor.struct(), actor_critic.critic.struct())
+            a, c = self._collect_nets
+            obs, s = st.observations, int(start) + k0
+            io = A.WlCollectIo(obs[s].data_ptr(), st.actions[s].data_ptr(), st.mu[s].data_ptr(), st.actions_log_prob[s].data_ptr(),
+                               st.values[s].data_ptr())
+            out = A.WlStepOut(obs[s + 1].data_ptr(), st.rewards[s].data_ptr(), st.terminated[s].data_ptr(), st.time_outs[s].data_ptr(),
+                              st.dones[s].data_ptr())
+            A.check(self.lib.wl_elev_collect_rollout(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), C.byref(a), C.byref(c),
+                                                     actor_critic.std.data_ptr(), C.byref(io), C.byref(out), k, int(bool(deterministic)),
+                                                     self.seed, self.step_count, self._stream()), "wl_elev_collect_rollout")
+            self.step_count += k
 
 
-class VisualBatch(_MetricsView):
+class VisualBatch(_EnvBatch):
     """n visual-task envs on one GPU: flat black/white traversability plane + ray-cast grey camera."""
 
     OBS_DIM = A.VIS_OBS_DIM
+    _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_visual_reset", "wl_visual_step", "wl_visual_rollout", "wl_visual_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params=None, seed: int = 42, env_offset: int = 0, trav_map=None,
                  spacing=(0.5, 0.5), metrics_slots: int = 1, startup=None, map_kwargs=None):
@@ -445,23 +423,8 @@ class VisualBatch(_MetricsView):
 
         from .params import visual_params
         from .travmap import generate_traversability_map, spawn_cells
-        self.lib = A.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("VisualBatch needs a HIP device; there is no CPU path")
-        self.n, self.stride = int(n_envs), ((int(n_envs) + 63) // 64) * 64
-        self.p = params if params is not None else visual_params()
-        self.seed, self.env_offset, self.step_count = int(seed), int(env_offset), 0
+        super().__init__(n_envs, device, params if params is not None else visual_params(), seed, env_offset, metrics_slots)
         dev = self.device
-        self.state = torch.zeros(A.S_COUNT, self.stride, dtype=torch.float32, device=dev)
-        self.episode_len = torch.zeros(self.stride, dtype=torch.int32, device=dev)
-        self.metrics_slots = int(metrics_slots)
-        self.metrics_raw = torch.zeros(self.metrics_slots, A.M_SHARDS, A.M_COUNT, dtype=torch.float32, device=dev)
-        self.obs = torch.zeros(self.n, self.OBS_DIM, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.terminated = torch.zeros(self.n, dtype=torch.bool, device=dev)
-        self.truncated = torch.zeros(self.n, dtype=torch.bool, device=dev)
-        self.dones = torch.zeros(self.n, dtype=torch.long, device=dev)   # terminated | truncated, as RSL-RL consumes it
         if trav_map is None:  # generated at construction from a seeded RNG (the reference uses the global numpy RNG)
             trav_map = generate_traversability_map(rng=np.random.RandomState(self.seed), **(map_kwargs or {}))
         trav_map = np.ascontiguousarray(np.asarray(trav_map, dtype=bool))
@@ -476,22 +439,11 @@ class VisualBatch(_MetricsView):
         self.trav_bits = torch.from_numpy(bits.view(np.int32).copy()).to(dev)
         self._map = A.WlTravMap(self.trav_map.data_ptr(), self.cells.data_ptr(), trav_map.shape[0], trav_map.shape[1],
                                 self.cells.shape[0], float(spacing[0]), float(spacing[1]), self.trav_bits.data_ptr())
+        self._args = (C.byref(self._bufs), C.byref(self._map))
         if startup is None:
             from .envs.flatten import StartupSpec
             startup = StartupSpec(wheel_mu_s=(0.5, 0.5), wheel_mu_d=(0.5, 0.5), damping=(1000.0, 1000.0), mass_add=(0.0, 0.0))
-        self._bufs = A.WlEnvBuffers(self.state.data_ptr(), self.episode_len.data_ptr(), None, self.metrics_raw.data_ptr(),
-                                    self.stride, self.n, self.env_offset, self.metrics_slots, 0, 0)
         apply_startup_events(self.lib, self._bufs, startup, self.seed, self._stream())
-        self._out = A.WlStepOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-                                self.truncated.data_ptr(), self.dones.data_ptr())
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def set_lanes(self, lanes: int = 0):
-        """step-kernel form: 0 = by env count (quad up to 32768 envs), 1 = lane per env, 4 = quad per env"""
-        assert lanes in (0, 1, 4)
-        self._bufs.lanes = lanes
 
     def sample_augmentation(self, generator: torch.Generator | None = None):
         """one (brightness, contrast, blur sigma) per call, like torchvision's ColorJitter(brightness=.8, contrast=.2)
@@ -505,52 +457,10 @@ class VisualBatch(_MetricsView):
         self.p.blur_sigma = float(0.1 + 4.9 * u[2])
         self.p.contrast_first = int(order.index(1) < order.index(0))
 
-    def reset(self, mask: torch.Tensor | None = None):
-        self.touch_pose()
-        m = None if mask is None else mask.to(torch.uint8).contiguous()
-        A.check(self.lib.wl_visual_reset(C.byref(self.p), C.byref(self._bufs), C.byref(self._map),
-                                         None if m is None else m.data_ptr(), self.seed, self.step_count, self._stream()),
-                "wl_visual_reset")
-
     def observe(self) -> torch.Tensor:
         A.check(self.lib.wl_visual_observe(C.byref(self.p), C.byref(self._bufs), C.byref(self._map), self.obs.data_ptr(),
                                            self._stream()), "wl_visual_observe")
         return self.obs
-
-    def step(self, actions: torch.Tensor):
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.n, 2):
-            actions = actions.to(torch.float32).reshape(self.n, 2).contiguous()
-        A.check(self.lib.wl_visual_step(C.byref(self.p), C.byref(self._bufs), C.byref(self._map), actions.data_ptr(),
-                                        C.byref(self._out), self.seed, self.step_count, self._stream()), "wl_visual_step")
-        self.step_count += 1
-        return self.obs, self.reward, self.terminated, self.truncated
-
-    def rollout(self, actions: torch.Tensor, obs_out=None, rew_out=None, term_out=None, trunc_out=None, dones_out=None,
-                persistent: bool = False):
-        """K fused steps with pre-staged actions [K,n,2]; optional [K,...] output storage (else overwrite).  persistent=True
-        (needs the storage, n <= 32 768) runs them as ONE launch with the camera of step k rendered while step k + 1 is
-        integrated (wl_visual_rollout_persistent); same results."""
-        K = actions.shape[0]
-        assert actions.shape == (K, self.n, 2) and actions.dtype == torch.float32 and actions.is_contiguous()
-        if persistent and obs_out is not None and self._ring_aliases(K):
-            cut = lambda t, a, b: None if t is None else t[a:b]
-            for a, b in ((0, 1), (1, K)):
-                self.rollout(actions[a:b], obs_out[a:b], rew_out[a:b], term_out[a:b], trunc_out[a:b], cut(dones_out, a, b), True)
-            return
-        if obs_out is not None:
-            out = A.WlStepOut(obs_out.data_ptr(), rew_out.data_ptr(), term_out.data_ptr(), trunc_out.data_ptr(),
-                              None if dones_out is None else dones_out.data_ptr())
-            os_, vs_ = self.n * self.OBS_DIM, self.n
-        else:
-            assert not persistent or K == 1, "a persistent rollout needs per-step output rows"
-            out, os_, vs_ = self._out, 0, 0
-        if persistent and self.metrics_slots > 1 and K > 1:
-            R = self.metrics_slots       # the launch folds all K steps into slot step0 % R: the slots it skips keep old counts
-            self.metrics_raw[[(self.step_count + i) % R for i in range(1, K)]] = 0
-        fn = self.lib.wl_visual_rollout_persistent if persistent else self.lib.wl_visual_rollout
-        A.check(fn(C.byref(self.p), C.byref(self._bufs), C.byref(self._map), actions.data_ptr(), C.byref(out), os_, vs_, K, self.seed,
-                   self.step_count, self._stream()), "wl_visual_rollout")
-        self.step_count += K
 
     def depth(self, heightfield, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
         """distance_to_image_plane of the camera against a heightfield -> [n, 60, 80] (BASELINE config 5); `heightfield` is
@@ -568,6 +478,7 @@ class VisualDepthBatch(VisualBatch):
     cells = the terrain's 40 m square, generated like the reference's from the seed)."""
 
     OBS_DIM = A.VISDEPTH_OBS_DIM
+    _C_RESET = "wl_visual_reset_hf"
 
     def __init__(self, n_envs: int, device="cuda:0", params=None, seed: int = 42, env_offset: int = 0, trav_map=None,
                  spacing=(0.5, 0.5), metrics_slots: int = 1, startup=None, map_kwargs=None, heightfield=None, max_depth: float = 20.0):
@@ -580,16 +491,7 @@ class VisualDepthBatch(VisualBatch):
         self.max_depth = float(max_depth)
         self.camera = DepthCamera(self.hf, self.device, self.p)
         self._hf = self.camera._hf
-        self.obs = torch.zeros(self.n, self.OBS_DIM, dtype=torch.float32, device=self.device)
-        self._out = A.WlStepOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
-                                self.truncated.data_ptr(), self.dones.data_ptr())
-
-    def reset(self, mask: torch.Tensor | None = None):
-        self.touch_pose()
-        m = None if mask is None else mask.to(torch.uint8).contiguous()
-        A.check(self.lib.wl_visual_reset_hf(C.byref(self.p), C.byref(self._bufs), C.byref(self._map), C.byref(self._hf),
-                                            None if m is None else m.data_ptr(), self.seed, self.step_count, self._stream()),
-                "wl_visual_reset_hf")
+        self._args = (C.byref(self._bufs), C.byref(self._map), C.byref(self._hf))
 
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         out = self.obs if out is None else out
@@ -601,15 +503,12 @@ class VisualDepthBatch(VisualBatch):
         """the depth image is not augmented (mdp_sensors/observations.py:93-95 returns the raw distances)"""
 
     def step(self, actions: torch.Tensor):
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.n, 2):
-            actions = actions.to(torch.float32).reshape(self.n, 2).contiguous()
-        self._step_into(actions.data_ptr(), self._out)
+        self._step_into(self._actions(actions).data_ptr(), self._out)
         return self.obs, self.reward, self.terminated, self.truncated
 
     def _step_into(self, actions_ptr, out):
-        A.check(self.lib.wl_visual_depth_step(C.byref(self.p), C.byref(self._bufs), C.byref(self._map), C.byref(self._hf),
-                                              self.camera.pyramid.data_ptr(), self.max_depth, actions_ptr, C.byref(out), self.seed,
-                                              self.step_count, self._stream()), "wl_visual_depth_step")
+        A.check(self.lib.wl_visual_depth_step(C.byref(self.p), *self._args, self.camera.pyramid.data_ptr(), self.max_depth, actions_ptr,
+                                              C.byref(out), self.seed, self.step_count, self._stream()), "wl_visual_depth_step")
         self.step_count += 1
 
     def rollout(self, actions: torch.Tensor, obs_out=None, rew_out=None, term_out=None, trunc_out=None, dones_out=None,
@@ -653,8 +552,7 @@ class DepthCamera:
         A.check(self.lib.wl_heightfield_build_pyramid(C.byref(self._hf), self.pyramid.data_ptr(), self._stream()),
                 "wl_heightfield_build_pyramid")
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    _stream = _EnvBatch._stream
 
     def render(self, batch, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:

@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(kBlock) drift_rollout_kernel(const WlDriftPara
     const uint32_t gid = (uint32_t)(b.env_offset + e);
     float2 a_next = n_steps > 0 ? actions[e] : make_float2(0.f, 0.f);
     for (int k = 0; k < n_steps; ++k) {
-        WlStepOut o = out;
+        WlStepOut o = out;   // step_out_at, written out: the call changes this kernel's register allocation
         o.obs += k * obs_step_stride;
         o.reward += k * vec_step_stride;
         o.terminated += k * vec_step_stride;
@@ -292,10 +292,9 @@ static void launch_step(const WlDriftParams* p, const WlEnvBuffers* b, const Veh
     const bool streaming = use_streaming(b, (int64_t)b->stride * 4 * WL_S_COUNT, kStreamingStateBytes);
     const bool forced_stream = (b->flags & WL_FLAG_STREAM) != 0;
     if (!forced_stream && use_quad(b)) {
-        const int lanes = b->n_envs * 4;
-        if (b->n_envs <= 2048) drift_step_kernel<4, FlatGround, true, -1, 64><<<(lanes + 63) / 64, 64, 0, stream>>>(WL_STEP_ARGS);
-        else if (b->n_envs <= 8192) drift_step_kernel<4, FlatGround, true, -1, 128><<<(lanes + 127) / 128, 128, 0, stream>>>(WL_STEP_ARGS);
-        else drift_step_kernel<4, FlatGround><<<grid_for(lanes), kBlock, 0, stream>>>(WL_STEP_ARGS);
+        launch_quad(b->n_envs, [&](auto qb, int qgrid) {
+            drift_step_kernel<4, FlatGround, true, -1, decltype(qb)::value><<<qgrid, qb.value, 0, stream>>>(WL_STEP_ARGS);
+        });
     }
     else if (!forced_stream && use_unrolled(b)) {
         if (awd) drift_step_kernel<1, FlatGround, true, 1, LB><<<grid, LB, 0, stream>>>(WL_STEP_ARGS);
@@ -314,7 +313,7 @@ int wl_drift_step(const WlDriftParams* p, const WlEnvBuffers* b, const float* ac
                   const WlStepOut* out, uint64_t seed, uint64_t step, void* stream) {
     int rc = check_buffers(p, b);
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated) return WL_EINVAL;
+    if (!actions || !step_out_ok(out)) return WL_EINVAL;
     clear_error();
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     launch_step(p, b, vd, (const float2*)actions, noise, *out, seed, step, (hipStream_t)stream);
@@ -326,18 +325,12 @@ int wl_drift_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const float*
                      void* stream) {
     int rc = check_buffers(p, b);
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     clear_error();
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
-    for (int k = 0; k < n_steps; ++k) {
-        WlStepOut o = *out;
-        o.obs += k * obs_step_stride;
-        o.reward += k * vec_step_stride;
-        o.terminated += k * vec_step_stride;
-        o.truncated += k * vec_step_stride;
-        if (o.dones) o.dones += k * vec_step_stride;
-        launch_step(p, b, vd, (const float2*)(actions + (int64_t)k * b->n_envs * 2), nullptr, o, seed, step0 + (uint64_t)k, (hipStream_t)stream);
-    }
+    for (int k = 0; k < n_steps; ++k)
+        launch_step(p, b, vd, (const float2*)(actions + (int64_t)k * b->n_envs * 2), nullptr, step_out_at(*out, k, obs_step_stride, vec_step_stride),
+                    seed, step0 + (uint64_t)k, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -346,16 +339,15 @@ int wl_drift_rollout_persistent(const WlDriftParams* p, const WlEnvBuffers* b, c
                                 void* stream) {
     int rc = check_buffers(p, b);
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
-    if (b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0) return WL_EINVAL;   // ring slot aliasing
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
+    if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
-#define WL_ROLLOUT_ARGS *p, *b, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, \
-                        derive_vehicle(p->vehicle, p->sim_dt, p->decimation), metric_slots(b, step0, (uint64_t)n_steps)
-    const int lanes = b->n_envs * 4;
-    if (b->n_envs <= 2048) drift_rollout_kernel<FlatGround, 64><<<(lanes + 63) / 64, 64, 0, (hipStream_t)stream>>>(WL_ROLLOUT_ARGS);
-    else if (b->n_envs <= 8192) drift_rollout_kernel<FlatGround, 128><<<(lanes + 127) / 128, 128, 0, (hipStream_t)stream>>>(WL_ROLLOUT_ARGS);
-    else drift_rollout_kernel<FlatGround><<<grid_for(lanes), kBlock, 0, (hipStream_t)stream>>>(WL_ROLLOUT_ARGS);
-#undef WL_ROLLOUT_ARGS
+    const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
+    const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
+    launch_quad(b->n_envs, [&](auto qb, int qgrid) {
+        drift_rollout_kernel<FlatGround, decltype(qb)::value><<<qgrid, qb.value, 0, (hipStream_t)stream>>>(
+            *p, *b, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, vd, ms);
+    });
     return launch_status();
 }
 

@@ -1115,7 +1115,7 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
                     uint64_t step0, void* stream) {
     int rc = check_elev(p, b, hf);
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     const HeightFieldGround g = make_ground(hf);
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     // step + scan in one launch up to three 16-env blocks per CU; beyond, the lane-form step + the scan launch (round 6, us per step, fused /
@@ -1143,7 +1143,7 @@ int wl_elev_collect_rollout(const WlElevParams* p, const WlEnvBuffers* b, const 
     if (rc != WL_OK) return rc;
     if (!use_quad(b)) return WL_EINVAL;   // the quad form's (n <= 32 768); beyond: act + step
     if (!actor || !critic || !std || !io || !io->obs_in || !io->actions || !io->mu || !io->log_prob || !io->values || n_steps < 0) return WL_EINVAL;
-    if (!out || !out->obs || !out->reward || !out->terminated || !out->truncated) return WL_EINVAL;
+    if (!step_out_ok(out)) return WL_EINVAL;
     for (const WlMlp* m : {actor, critic})
         if (!m->w1 || !m->b1 || !m->w2 || !m->b2 || !m->w3 || !m->b3 || m->hidden != kMlpHidden || m->in_dim != WL_ELEV_OBS_DIM ||
             (m->activation != WL_ACT_ELU && m->activation != WL_ACT_RELU))
@@ -1152,7 +1152,7 @@ int wl_elev_collect_rollout(const WlElevParams* p, const WlEnvBuffers* b, const 
     if (((uintptr_t)io->actions & 7u) || ((uintptr_t)io->mu & 7u) || ((uintptr_t)io->obs_in & 3u)) return WL_EALIGN;
     // rows k of a [K + 1][n][689] observation block: the kernel writes row k + 1 where the caller's policy would read it
     if (out->obs != io->obs_in + (int64_t)b->n_envs * WL_ELEV_OBS_DIM) return WL_EINVAL;
-    if (b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0) return WL_EINVAL;   // ring slot aliasing
+    if (ring_aliases(b, n_steps)) return WL_EINVAL;
     const HeightFieldGround g = make_ground(hf);
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     const PolicyIo pio{*actor, *critic, std, io->obs_in, io->actions, io->mu, io->log_prob, io->values, deterministic};
@@ -1179,9 +1179,9 @@ int wl_elev_rollout_persistent(const WlElevParams* p, const WlEnvBuffers* b, con
     int rc = check_elev(p, b, hf);
     if (rc != WL_OK) return rc;
     if (!use_quad(b)) return WL_EINVAL;   // the quad form's (n <= 32 768)
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     if (n_steps > 1 && obs_step_stride < (int64_t)b->n_envs * WL_ELEV_OBS_DIM) return WL_EINVAL;   // the scan runs a step behind: rows must differ
-    if (b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0) return WL_EINVAL;   // ring slot aliasing
+    if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
     elev_rollout_persistent_kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(
         *p, derive_vehicle(p->vehicle, p->sim_dt, p->decimation), *b, make_ground(hf), (const float2*)actions, *out, obs_step_stride,

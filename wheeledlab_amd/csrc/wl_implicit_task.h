@@ -230,17 +230,6 @@ struct HelperReset {
     WL_DEV DRAW operator()(int e, F draw) const { return on ? h->take(e - e0) : draw(); }
 };
 
-// the outputs of step k of a K-step rollout: rows k of the caller's [K][n][obs] and [K][n] blocks
-__host__ __device__ inline WlStepOut step_out_at(const WlStepOut& out, int k, int64_t obs_stride, int64_t vec_stride) {
-    WlStepOut o = out;
-    o.obs += k * obs_stride;
-    o.reward += k * vec_stride;
-    o.terminated += k * vec_stride;
-    o.truncated += k * vec_stride;
-    if (o.dones) o.dones += k * vec_stride;
-    return o;
-}
-
 // the env-buffer half of check_elev / check_visual (P: their parameter struct)
 template <class P>
 inline int check_implicit_env(const P* p, const WlEnvBuffers* b) {

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/wheeledlab_amd.h"
 #include "wl_math.h"
 
@@ -187,6 +189,35 @@ inline MetricSlots metric_slots(const WlEnvBuffers* b, uint64_t step0, uint64_t 
 }
 
 inline int grid_for(int n) { return (n + kBlock - 1) / kBlock; }
+
+// ---- the C entry points' shared argument checks and launch shapes ----
+// a step's four output rows (`dones` is optional)
+inline bool step_out_ok(const WlStepOut* out) { return out && out->obs && out->reward && out->terminated && out->truncated; }
+// A persistent launch folds its steps into ring slot step0 % R and clears slot (step0 + n) % R for its successor: with n a
+// multiple of R those are the same slot, so the entry points refuse the launch (the host layer splits it: core.ring_plan).
+inline bool ring_aliases(const WlEnvBuffers* b, int32_t n_steps) {
+    return b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0;
+}
+// the outputs of step k of a K-step rollout: rows k of the caller's [K][n][obs] and [K][n] blocks
+__host__ __device__ inline WlStepOut step_out_at(const WlStepOut& out, int k, int64_t obs_stride, int64_t vec_stride) {
+    WlStepOut o = out;
+    o.obs += k * obs_stride;
+    o.reward += k * vec_stride;
+    o.terminated += k * vec_stride;
+    o.truncated += k * vec_stride;
+    if (o.dones) o.dones += k * vec_stride;
+    return o;
+}
+// The quad form's block (one env per 4 lanes): 64 threads up to 2048 envs, 128 up to 8192, kBlock beyond.  Calls
+// launch(qb, grid) with qb a std::integral_constant holding the block size (a template argument of the kernel) and the grid
+// of such blocks over the n_envs * 4 lanes.
+template <class F>
+inline void launch_quad(int n_envs, F&& launch) {
+    const int lanes = n_envs * 4;
+    if (n_envs <= 2048) launch(std::integral_constant<int, 64>{}, (lanes + 63) / 64);
+    else if (n_envs <= 8192) launch(std::integral_constant<int, 128>{}, (lanes + 127) / 128);
+    else launch(std::integral_constant<int, kBlock>{}, grid_for(lanes));
+}
 // Step kernels come in two forms (wl_vehicle.h): lane-per-env (no redundant work: best when the chip is full) and
 // quad-per-env (one wheel per lane: shorter critical path, 4x the waves: best while the chip is under-filled).
 // 256 CUs x 4 SIMDs = 1024 wave slots at one wave per SIMD; quads pay off up to a few waves per SIMD.

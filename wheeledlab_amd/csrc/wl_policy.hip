@@ -159,22 +159,19 @@ int wl_drift_rollout_policy(const WlDriftParams* p, const WlEnvBuffers* b, const
     if (!io || !io->obs || !io->actions || !io->mu || !io->log_prob || !io->reward || !io->terminated || !io->truncated)
         return WL_EINVAL;
     if (((uintptr_t)io->obs & 7u) || ((uintptr_t)io->actions & 7u) || ((uintptr_t)io->mu & 7u)) return WL_EALIGN;
-    if (b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0) return WL_EINVAL;   // ring slot aliasing
+    if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
-#define WL_PR_ARGS *p, *b, *actor, action_std, *io, n_steps, seed, step0, FlatGround{}, vd, metric_slots(b, step0, (uint64_t)n_steps)
-#define WL_PR_LAUNCH(ACT)                                                                                                       \
-    if (b->n_envs <= 2048) drift_policy_rollout_kernel<ACT, FlatGround, 64><<<(lanes + 63) / 64, 64, 0, (hipStream_t)stream>>>(WL_PR_ARGS);   \
-    else if (b->n_envs <= 8192) drift_policy_rollout_kernel<ACT, FlatGround, 128><<<(lanes + 127) / 128, 128, 0, (hipStream_t)stream>>>(WL_PR_ARGS); \
-    else drift_policy_rollout_kernel<ACT, FlatGround><<<grid_for(lanes), kBlock, 0, (hipStream_t)stream>>>(WL_PR_ARGS)
-    const int lanes = b->n_envs * 4;
-    if (actor->activation == WL_ACT_ELU) {
-        WL_PR_LAUNCH(WL_ACT_ELU);
-    } else {
-        WL_PR_LAUNCH(WL_ACT_RELU);
-    }
-#undef WL_PR_LAUNCH
-#undef WL_PR_ARGS
+    const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
+    const hipStream_t hs = (hipStream_t)stream;
+    const auto launch = [&](auto act) {   // the actor's activation: a std::integral_constant
+        launch_quad(b->n_envs, [&](auto qb, int qgrid) {
+            drift_policy_rollout_kernel<decltype(act)::value, FlatGround, decltype(qb)::value><<<qgrid, qb.value, 0, hs>>>(
+                *p, *b, *actor, action_std, *io, n_steps, seed, step0, FlatGround{}, vd, ms);
+        });
+    };
+    if (actor->activation == WL_ACT_ELU) launch(std::integral_constant<int, WL_ACT_ELU>{});
+    else launch(std::integral_constant<int, WL_ACT_RELU>{});
     return launch_status();
 }
 

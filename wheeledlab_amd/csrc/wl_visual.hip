@@ -637,7 +637,7 @@ int wl_visual_rollout(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
                       uint64_t step0, void* stream) {
     int rc = check_visual(p, b, m);
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     const bool quad = use_quad(b);
     clear_error();
@@ -648,12 +648,9 @@ int wl_visual_rollout(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
         const hipStream_t hs = (hipStream_t)stream;
         const int n = b->n_envs;
         if (quad)
-        {
-            const int lanes = n * 4;
-            if (n <= 2048) visual_step_kernel<4, 64><<<(lanes + 63) / 64, 64, 0, hs>>>(*p, vd, *b, *m, a, o, seed, st);
-            else if (n <= 8192) visual_step_kernel<4, 128><<<(lanes + 127) / 128, 128, 0, hs>>>(*p, vd, *b, *m, a, o, seed, st);
-            else visual_step_kernel<4><<<grid_for(lanes), kBlock, 0, hs>>>(*p, vd, *b, *m, a, o, seed, st);
-        }
+            launch_quad(n, [&](auto qb, int qgrid) {
+                visual_step_kernel<4, decltype(qb)::value><<<qgrid, qb.value, 0, hs>>>(*p, vd, *b, *m, a, o, seed, st);
+            });
         else
             visual_step_kernel<1><<<grid_for(n), kBlock, 0, hs>>>(*p, vd, *b, *m, a, o, seed, st);
         launch_visual_obs(p, b, m, o.obs, hs);
@@ -667,25 +664,27 @@ int wl_visual_rollout_persistent(const WlVisualParams* p, const WlEnvBuffers* b,
     int rc = check_visual(p, b, m);
     if (rc != WL_OK) return rc;
     if (!use_quad(b)) return WL_EINVAL;   // the quad form's (n <= 32 768)
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated || n_steps < 0) return WL_EINVAL;
+    if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     if (n_steps > 1 && obs_step_stride < (int64_t)b->n_envs * WL_VIS_OBS_DIM) return WL_EINVAL;   // the camera runs a step behind: rows must differ
-    if (b->metrics_slots > 1 && n_steps % b->metrics_slots == 0 && n_steps > 0) return WL_EINVAL;   // ring slot aliasing
+    if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
     // envs per block: one round of blocks on the 256 CUs (a block's thirteen-plus wavefronts at 128 VGPRs fill a CU)
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
     const int n = b->n_envs;
-#define WL_VIS_PERSIST(E)                                                                                                   \
-    if (lds_map_ok(m))                                                                                                      \
-        visual_rollout_persistent_kernel<E, true><<<(n + (E) - 1) / (E), kPersistThreads, 0, (hipStream_t)stream>>>(        \
-            *p, vd, *b, *m, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, ms);      \
-    else                                                                                                                    \
-        visual_rollout_persistent_kernel<E, false><<<(n + (E) - 1) / (E), kPersistThreads, 0, (hipStream_t)stream>>>(       \
-            *p, vd, *b, *m, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, ms)
-    if (n <= 1024) { WL_VIS_PERSIST(4); }
-    else if (n <= 2048) { WL_VIS_PERSIST(8); }
-    else { WL_VIS_PERSIST(16); }
-#undef WL_VIS_PERSIST
+    const hipStream_t hs = (hipStream_t)stream;
+    const auto launch = [&](auto envs) {   // envs per block: a std::integral_constant
+        constexpr int E = decltype(envs)::value;
+        if (lds_map_ok(m))
+            visual_rollout_persistent_kernel<E, true><<<(n + E - 1) / E, kPersistThreads, 0, hs>>>(
+                *p, vd, *b, *m, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, ms);
+        else
+            visual_rollout_persistent_kernel<E, false><<<(n + E - 1) / E, kPersistThreads, 0, hs>>>(
+                *p, vd, *b, *m, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, ms);
+    };
+    if (n <= 1024) launch(std::integral_constant<int, 4>{});
+    else if (n <= 2048) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
     return launch_status();
 }
 
@@ -714,7 +713,7 @@ int wl_visual_step_hf(const WlVisualParams* p, const WlEnvBuffers* b, const WlTr
     int rc = check_visual(p, b, m);
     if (rc == WL_OK) rc = heightfield_args_ok(hf, HF_PAIRS);   // pair: the contact sampler's table (wl_heightfield_pairs)
     if (rc != WL_OK) return rc;
-    if (!actions || !out || !out->obs || !out->reward || !out->terminated || !out->truncated) return WL_EINVAL;
+    if (!actions || !step_out_ok(out)) return WL_EINVAL;
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
     const HeightFieldGround g = make_ground(hf);
     const float2* a = (const float2*)actions;
