@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the fused drift env.step() hot path (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W           (N>1: launched by torch.distributed.run, one rank / GPU)
+  python bench.py --gpus 1 --steps K --warmup W [--full]  (N>1: launched by torch.distributed.run, one rank / GPU)
 
 A "step" is one env.step() of ALL envs of the shard: one launch of the fused HIP kernel (action term -> 4 physics
 sub-steps -> terminations -> rewards -> resets -> pushes -> 14-dim observation).  W warm-up steps and one untimed
-block of K steps are followed by ONE timed block of exactly K steps; `ms_per_step` is that block's wall time / K (the
-secondary figures -- events, kernel-only duration, other tasks -- are measured after it).  `--dump-outputs DIR` writes what the
+block of K steps are followed by ONE timed block of exactly K steps; `ms_per_step` is that block's wall time / K.  A plain
+run stops there: it prints the headline, the roofline fraction that follows from its own clock and the episode metrics of
+its steps.  `--full` goes on to the secondary figures -- events, kernel-only duration, the RCCL spread and latency, other
+tasks, the large-N sweep, the CPU baseline -- all measured after the timed block.  `--dump-outputs DIR` writes what the
 last timed step returned (observation, reward, terminated, truncated) as float32 .npy files; the inputs are seeded, so
 two builds run with the same arguments can be compared output for output.  Workload (config.workload): drift
 task, 4096 envs per GPU, flat terrain, synthetic U(-1,1) actions pre-staged in HBM, outputs written into a
@@ -14,9 +16,10 @@ task, 4096 envs per GPU, flat terrain, synthetic U(-1,1) actions pre-staged in H
 Env shards are independent (weak scaling); the only collective is the episode-metric all-reduce (RCCL) once per
 128-step rollout -- the reference's logging cadence (rsl_rl_ppo_cfg.py:6).
 
-The JSON line carries `roofline` (HBM-bound kernel: algorithmic bytes per launch / mean launch duration measured
-with HIP events on the launch stream) and `cpu_baseline` (the torch-CPU port of the reference's mdp path, timed on
-this box's host cores on a bounded sample; baseline, not target).
+With `--full` the JSON line also carries the event-timed side of `roofline` (algorithmic bytes per launch / mean launch
+duration measured with HIP events on the launch stream, beside the committed profile and counter digests) and
+`cpu_baseline` (the torch-CPU port of the reference's mdp path, timed on the host's cores on a bounded sample; baseline,
+not target).
 """
 import argparse
 import json
@@ -448,7 +451,7 @@ def compact_line(d, detail_path):
     c = d["config"]
     line["config"] = {"workload": f"drift task, {c['envs_per_gpu']} envs/GPU, flat terrain, fused step kernel, synthetic actions in HBM",
                       "envs_per_gpu": c["envs_per_gpu"], "total_envs": c["total_envs"], "parallelism": f"env-shard x{d['n_gpus']}"}
-    line["roofline"] = _pick(d["roofline"], _ROOF_KEYS)
+    line["roofline"] = {k: d["roofline"][k] for k in _ROOF_KEYS if k in d["roofline"]}    # a plain run has only the clock's part
     cb = d.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {**_pick(cb, ("value", "unit", "cores", "kind", "host_cores")),
@@ -461,7 +464,8 @@ def compact_line(d, detail_path):
     else:
         line["rccl"] = None
     line["episode_metrics"] = d["episode_metrics"]
-    line["gpu_event_ms_per_step"] = d["gpu_event_ms_per_step"]
+    if "gpu_event_ms_per_step" in d:
+        line["gpu_event_ms_per_step"] = d["gpu_event_ms_per_step"]
     ot = {}
     for name, o in (d.get("other_tasks") or {}).items():
         roof = o.get("roofline") or {}
@@ -490,6 +494,71 @@ def compact_line(d, detail_path):
     return out
 
 
+def headline_record(args, n, world, every, wall, reductions_in_timed_blocks, rccl, metric_sum):
+    """what a plain run reports: the timed block, the roofline fraction that follows from its clock alone (algorithmic bytes of
+    one launch / ms_per_step -- the wall time per step of the timed block, barrier + synchronise bracket included -- / peak)
+    and the episode metrics of its steps; --full adds to it"""
+    total_envs = n * world
+    step_us = wall * 1e6 / args.steps
+    achieved = BYTES_PER_ENV_STEP * n / (step_us * 1e-6) / 1e9
+    # which roofline binds: at the BASELINE size the state is L2 / Infinity-Cache resident and one wavefront per SIMD
+    # issues dependent instructions -- launch floor + instruction latency, not bandwidth; the HBM fraction is reported
+    # regardless (the contract's metric) and the --full sweep shows the regime where bandwidth and the VALU pipe bind
+    regime = "latency" if n <= 32768 else "valu+hbm"
+    return {
+        "metric": "env steps/sec (whole node), drift task @ 4096 envs/GPU",
+        "value": total_envs * args.steps / wall,
+        "unit": "env-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall * 1e3 / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"RSS_DRIFT_CONFIG drift task, {n} envs/GPU, flat terrain, fused dynamics+mdp HIP "
+                               f"kernel, U(-1,1) actions pre-staged in HBM, {ROLLOUT}-step rollout storage",
+                   "envs_per_gpu": n, "total_envs": total_envs, "decimation": 4, "sim_dt": 0.005,
+                   "parallelism": f"env-shard x{world}, metric all-reduce / {every} steps"},
+        "timing": {"repeats": 1, "statistic": "max-over-ranks wall time of the one timed block of --steps steps",
+                   "block_ms": [round(wall * 1e3, 4)],
+                   "metric_reductions_in_timed_blocks": reductions_in_timed_blocks, "allreduce_every": every},
+        "rccl": rccl,
+        # `bound` names the roofline `peak` belongs to (the contract: "hbm" | "mfma"); `regime` says what actually limits the
+        # launch at this size
+        "roofline": {"bound": "hbm", "regime": regime, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "hbm_frac": achieved / HBM_PEAK_GBS,
+                     "frac_is": "bytes_per_env_step x envs_per_launch / ms_per_step / peak",
+                     # SURVEY.md 8(d)'s own per-unit figure (270 B: it leaves out the episode-sum rows and the flag bytes the
+                     # kernel also moves) beside the 334 B this file counts row by row
+                     "bytes_per_env_step_survey": BYTES_PER_ENV_STEP_SURVEY,
+                     "frac_survey": BYTES_PER_ENV_STEP_SURVEY * n / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                     "kernel": "drift_step_kernel<FlatGround>",
+                     "frac_uses": "ms_per_step (wall clock of the timed block)",
+                     "bytes_per_env_step": BYTES_PER_ENV_STEP, "envs_per_launch": n},
+        "episode_metrics": {"resets": float(metric_sum[8]), "timeouts": float(metric_sum[9]),
+                            "out_of_bounds": float(metric_sum[10]), "nonfinite": float(metric_sum[14])},
+    }
+
+
+def emit(detail, args):
+    """rank 0's output: the side file (always with --full; in a plain run only when one is asked for) and the ONE JSON line"""
+    want_side = args.full or args.detail_out or os.environ.get("WL_BENCH_DETAIL")
+    detail_path = write_detail(detail, args.detail_out) if want_side else None
+    line = compact_line(detail, detail_path)
+    text = json.dumps(line, separators=(",", ":"))
+    # The driver parses the LAST stdout line; round 4's grew to 21.9 KB and was not parsed.  Everything measured goes to a side
+    # file (and, on request, to an earlier stdout line that does not start with `{`); the one JSON line is the compact digest of
+    # it.  Never lose the headline over a secondary section: should the line ever outgrow the limit, the optional digests go
+    # first (they stay in the side file), and the test suite fails on the size (tests/test_gpu_bench_contract.py)
+    for optional in ("other_tasks_large_n", "large_n_sweep", "other_tasks", "episode_metrics"):
+        if len(text) < MAX_LINE_BYTES:
+            break
+        print(f"[bench] line is {len(text)} bytes (limit {MAX_LINE_BYTES}): dropping `{optional}` from it", file=sys.stderr, flush=True)
+        line.pop(optional, None)
+        text = json.dumps(line, separators=(",", ":"))
+    if args.print_detail:
+        print("[bench detail] " + json.dumps(detail), flush=True)
+    print(text, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -500,11 +569,16 @@ def main():
     ap.add_argument("--allreduce-every", type=int, default=ROLLOUT,
                     help="steps between episode-metric all-reduces (default 128 = the reference's logging cadence; 1 = SURVEY 8(d) "
                          "config 4's worst case: one collective per env.step())")
-    ap.add_argument("--sweep", action="store_true", help="(default at N=1) large-N sweep of the same kernel: the HBM-bound regime")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed block, measure everything else too: event and kernel-only timings, the RCCL spread and "
+                         "latency (N>1), the secondary sections, the large-N sweep and the CPU baseline (N=1)")
+    ap.add_argument("--sweep", action="store_true", help="(default with --full at N=1) large-N sweep of the same kernel: the HBM-bound regime")
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--sweep-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--headline-only", action="store_true", help="only the timed headline workload: no secondary sections, no CPU baseline")
-    ap.add_argument("--detail-out", default=None, help="side file for everything measured (default gpurun_out/bench_detail.json)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: no secondary sections, no sweep, no CPU baseline (a plain run is leaner still)")
+    ap.add_argument("--detail-out", default=None,
+                    help="side file for everything measured (--full writes one by default, see write_detail; a plain run only to this path)")
     ap.add_argument("--print-detail", action="store_true", help="also print the full detail as an earlier stdout line prefixed `[bench detail] `")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB; per rank: <name>_rank<r>.npy)")
@@ -636,6 +710,13 @@ def main():
         dump_outputs(args.dump_outputs, {"obs": obs_buf[last], "reward": rew_buf[last], "terminated": term_buf[last],
                                          "truncated": trunc_buf[last]},
                      "" if world == 1 else f"_rank{rank}", DUMP_BYTES // world)
+    if not args.full:
+        drain()   # the episode metrics the steps left in the accumulators (outside the timing)
+        if rank == 0:
+            emit(headline_record(args, n, world, every, wall, reductions_in_timed_blocks, rccl, metric_sum), args)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # secondary figure: a block of the same shape between two events on the launch stream
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     barrier()
@@ -682,18 +763,11 @@ def main():
                      "metric_allreduce_us": {"median_max_over_ranks": float(lt.item()), "min_this_rank": lat[0], "max_this_rank": lat[-1],
                                              "bytes": int(m.numel() * m.element_size()), "samples": len(lat),
                                              "timing": "HIP events around one blocking all_reduce of the [16] metric vector on an idle stream"}})
-    # The line's own fraction follows from the line's own clock: algorithmic bytes of one launch / ms_per_step (the wall time per
-    # step of the timed blocks, barrier + synchronise bracket included) / peak.  The same bytes over the kernel's duration between
-    # two events on the launch stream are `frac_launch`; over its average in the committed rocprofv3 summary `frac_profile`.
-    step_us = wall * 1e6 / args.steps
-    achieved = BYTES_PER_ENV_STEP * n / (step_us * 1e-6) / 1e9
+    # The line's own fraction follows from the line's own clock (headline_record).  The same bytes over the kernel's duration
+    # between two events on the launch stream are `frac_launch`; over its average in the committed rocprofv3 summary `frac_profile`.
     achieved_launch = BYTES_PER_ENV_STEP * n / (launch_us * 1e-6) / 1e9
     traffic, traffic_src, traffic_stale = pmc_traffic(n)
     sq = pmc_sq(n)
-    # which roofline binds: at the BASELINE size the state is L2 / Infinity-Cache resident and one wavefront per SIMD
-    # issues dependent instructions -- launch floor + instruction latency, not bandwidth; the HBM fraction is reported
-    # regardless (the contract's metric) and the sweep below shows the regime where bandwidth and the VALU pipe bind
-    regime = "latency" if n <= 32768 else "valu+hbm"
 
     # secondary: the same K-step rollouts as ONE persistent launch each (state in registers across steps; only possible
     # with pre-staged actions, so it is NOT the headline; the policy-in-the-loop form follows)
@@ -1010,51 +1084,23 @@ def main():
             sweep = large_n_sweep(dev)
 
     if rank == 0:
-        total_envs = n * world
         # the same fraction from the committed artefacts: algorithmic bytes / the kernel's average duration in the rocprofv3
         # summary of this script (profiles/), and counter bytes / duration in the PMC passes
         prof = rocprof_avg_us("drift_step_kernel")
         frac_profile = BYTES_PER_ENV_STEP * n / (prof["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS if prof and n == ENVS_PER_GPU else None
         pe = pmc_entry("drift", n)
         frac_counters = pe.get("frac_counters") if pe and not pe["stale"] else None
-        detail = {
-            "metric": "env steps/sec (whole node), drift task @ 4096 envs/GPU",
-            "value": total_envs * args.steps / wall,
-            "unit": "env-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": wall * 1e3 / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"RSS_DRIFT_CONFIG drift task, {n} envs/GPU, flat terrain, fused dynamics+mdp HIP "
-                                   f"kernel, U(-1,1) actions pre-staged in HBM, {ROLLOUT}-step rollout storage",
-                       "envs_per_gpu": n, "total_envs": total_envs, "decimation": 4, "sim_dt": 0.005,
-                       "parallelism": f"env-shard x{world}, metric all-reduce / {every} steps"},
-            "gpu_event_ms_per_step": gpu_ms / args.steps,
-            "timing": {"repeats": 1, "statistic": "max-over-ranks wall time of the one timed block of --steps steps",
-                       "block_ms": [round(wall * 1e3, 4)],
-                       "metric_reductions_in_timed_blocks": reductions_in_timed_blocks, "allreduce_every": every},
-            "rccl": rccl,
-            # `bound` names the roofline `peak` belongs to (the contract: "hbm" | "mfma"); `regime` says what actually limits the
-            # launch at this size
-            "roofline": {"bound": "hbm", "regime": regime, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "hbm_frac": achieved / HBM_PEAK_GBS,
-                         "frac_is": "bytes_per_env_step x envs_per_launch / ms_per_step / peak",
-                         "frac_launch": achieved_launch / HBM_PEAK_GBS,
-                         # SURVEY.md 8(d)'s own per-unit figure (270 B: it leaves out the episode-sum rows and the flag bytes the
-                         # kernel also moves) beside the 334 B this file counts row by row
-                         "bytes_per_env_step_survey": BYTES_PER_ENV_STEP_SURVEY,
-                         "frac_survey": BYTES_PER_ENV_STEP_SURVEY * n / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                         "profile_us": prof["avg_us"] if prof else None,
-                         "valu_frac": sq.get("valu_pipe_frac") if sq else None, "sq_counters": sq,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
-                         "kernel": "drift_step_kernel<FlatGround>", "launch_us": launch_us,
-                         "frac_uses": "ms_per_step (wall clock of the timed block); frac_launch: launch_us (HIP events on the launch stream)",
-                         "rocprof_kernel_stats": prof, "frac_profile": frac_profile, "frac_counters": frac_counters,
-                         "wasted_traffic": traffic / (BYTES_PER_ENV_STEP * n) if traffic else None,
-                         "bytes_per_env_step": BYTES_PER_ENV_STEP, "envs_per_launch": n},
-            "episode_metrics": {"resets": float(metric_sum[8]), "timeouts": float(metric_sum[9]),
-                                "out_of_bounds": float(metric_sum[10]), "nonfinite": float(metric_sum[14])},
-        }
+        detail = headline_record(args, n, world, every, wall, reductions_in_timed_blocks, rccl, metric_sum)
+        detail["gpu_event_ms_per_step"] = gpu_ms / args.steps
+        detail["roofline"].update({
+            "frac_launch": achieved_launch / HBM_PEAK_GBS,
+            "profile_us": prof["avg_us"] if prof else None,
+            "valu_frac": sq.get("valu_pipe_frac") if sq else None, "sq_counters": sq,
+            "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": traffic_stale,
+            "launch_us": launch_us,
+            "frac_uses": "ms_per_step (wall clock of the timed block); frac_launch: launch_us (HIP events on the launch stream)",
+            "rocprof_kernel_stats": prof, "frac_profile": frac_profile, "frac_counters": frac_counters,
+            "wasted_traffic": traffic / (BYTES_PER_ENV_STEP * n) if traffic else None})
         detail["python_surface_env_steps_per_s"] = py_rate
         detail["persistent_rollout"] = persistent
         detail["policy_rollout"] = policy
@@ -1066,23 +1112,7 @@ def main():
             detail["other_tasks_large_n"] = other_sweep
         if world == 1 and not args.no_cpu_baseline:
             detail["cpu_baseline"] = cpu_baseline(n)
-        # The driver parses the LAST stdout line; round 4's grew to 21.9 KB and was not parsed.  Everything measured goes to a
-        # side file (and, on request, to an earlier stdout line that does not start with `{`); the one JSON line is the compact
-        # digest of it, asserted below to stay under 6 KB.
-        detail_path = write_detail(detail, args.detail_out)
-        line = compact_line(detail, detail_path)
-        text = json.dumps(line, separators=(",", ":"))
-        # never lose the headline over a secondary section: should the line ever outgrow the limit, the optional digests go first
-        # (they stay in the side file), and the test suite fails on the size (tests/test_gpu_bench_contract.py)
-        for optional in ("other_tasks_large_n", "large_n_sweep", "other_tasks", "episode_metrics"):
-            if len(text) < MAX_LINE_BYTES:
-                break
-            print(f"[bench] line is {len(text)} bytes (limit {MAX_LINE_BYTES}): dropping `{optional}` from it", file=sys.stderr, flush=True)
-            line.pop(optional, None)
-            text = json.dumps(line, separators=(",", ":"))
-        if args.print_detail:
-            print("[bench detail] " + json.dumps(detail), flush=True)
-        print(text, flush=True)
+        emit(detail, args)
     if dist is not None:
         dist.destroy_process_group()
 

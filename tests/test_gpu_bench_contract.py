@@ -11,7 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--steps", "20", "--warmup", "5", "--headline-only"]
+ARGS = ["--steps", "20", "--warmup", "5"]
 
 
 MAX_LINE = 6144      # bench.MAX_LINE_BYTES: round 4's line grew to 21.9 KB and the driver's record of it had `parsed: null`
@@ -29,12 +29,12 @@ def _run(cmd, env=None, detail=None):
     return json.loads(lines[0])
 
 
-def test_the_drivers_own_command_prints_one_short_line_with_roofline_and_cpu_baseline(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5`, every secondary section, sweep and CPU baseline included -- the command
-    BENCH_rNN.json records -- ends in ONE `{`-line under 6 KB that carries the contract keys, `roofline` and `cpu_baseline`;
-    everything else measured is in the side file the line names"""
+def test_the_full_run_prints_one_short_line_with_roofline_and_cpu_baseline(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, every secondary section, sweep and CPU baseline included, ends in
+    ONE `{`-line under 6 KB that carries the contract keys, `roofline` and `cpu_baseline`; everything else measured is in the side
+    file the line names"""
     side = tmp_path / "detail.json"
-    line = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], detail=side)
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], detail=side)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -79,6 +79,12 @@ def test_line_shape_and_torchrun_world_1_equals_the_plain_launch(tmp_path):
     r = plain["roofline"]
     assert r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and r["bound"] == "hbm" and r["regime"] == "latency"
     assert abs(plain["value"] - 4096 * 20 / (plain["ms_per_step"] * 20e-3)) < 1e-3 * plain["value"]
+    # a plain run measures nothing beside its timed block: what takes runs of its own is --full's
+    for k in ("cpu_baseline", "other_tasks", "large_n_sweep", "other_tasks_large_n", "gpu_event_ms_per_step",
+              "persistent_rollout_env_steps_per_s", "policy_rollout_env_steps_per_s", "training_iteration_env_steps_per_s",
+              "python_surface_env_steps_per_s"):
+        assert k not in plain, k
+    assert "launch_us" not in r and "frac_launch" not in r and plain["episode_metrics"]["resets"] > 0
     tr = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", "29541", "bench.py", "--gpus", "1", *ARGS, "--dump-outputs", str(tmp_path / "db")], detail=tmp_path / "b.json")
     assert set(tr) == set(plain) and tr["config"] == plain["config"] and tr["rccl"] is None
@@ -96,7 +102,7 @@ def test_line_shape_and_torchrun_world_1_equals_the_plain_launch(tmp_path):
 
 def test_two_ranks_reduce_their_metrics_every_step(tmp_path):
     short = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                  "--master-port", "29542", "bench.py", "--gpus", "2", *ARGS, "--allreduce-every", "1"], env={"WL_BENCH_BACKEND": "gloo"},
+                  "--master-port", "29542", "bench.py", "--gpus", "2", *ARGS, "--allreduce-every", "1", "--full"], env={"WL_BENCH_BACKEND": "gloo"},
                  detail=tmp_path / "c.json")
     assert short["n_gpus"] == 2 and short["config"]["total_envs"] == 8192
     assert short["rccl"]["world"] == 2 and short["rccl"]["ranks_seen"] == 2 and short["rccl"]["metric_allreduce_us"] > 0

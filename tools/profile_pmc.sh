@@ -1,6 +1,6 @@
 # Profiling pass (run through gpurun): per-task HBM traffic (FETCH_SIZE / WRITE_SIZE, separate passes) and SQ counters for the
 # drift / elevation / visual step kernels, the depth ray-cast and the visual-depth task at the BASELINE size and large N, the
-# calibration of the traffic counters on known bytes, and kernel statistics of bench.py itself (the driver's command).
+# calibration of the traffic counters on known bytes, and kernel statistics of bench.py --full itself.
 # Every rocprofv3 --pmc run is its own pass (no trace domains next to --pmc) and runs under `timeout`.
 #   usage: tools/profile_pmc.sh <tag>      (output gpurun_out/<tag>/, digest <tag>_pmc.json + <tag>_bench_kernel_stats.csv there)
 #   WL_PMC_WORK="task:envs:K ..." overrides the workload list, WL_FLAGS forces a kernel form (WlEnvBuffers.flags), WL_PMC_NO_STATS=1
@@ -27,7 +27,7 @@ if timeout 120 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 $R/tools/microbench
   pm calib_WRITE WRITE_SIZE $O/pmc_calib
 fi
 if [ -z "$WL_PMC_NO_STATS" ]; then
-  # the SAME command the driver runs (sweep children and CPU baseline included: their kernels land in their own process's summary)
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --detail-out $O/bench_under_rocprof_detail.json > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+  # the driver's K = 20 command with --full (sweep children and CPU baseline included: their kernels land in their own process's summary)
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-out $O/bench_under_rocprof_detail.json > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 fi
 cd $R && python tools/pmc_report.py $O $TAG
