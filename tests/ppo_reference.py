@@ -88,17 +88,27 @@ def _act(z, mz, activation):
     return h, mh, d, md
 
 
-def forward(net: dict, x, activation, mx=None):
-    """layer by layer, values and magnitudes: dict z1, h1, dh1, z2, h2, dh2, y (+ m_*)"""
+def forward(net: dict, x, activation, mx=None, kink=None):
+    """layer by layer, values and magnitudes: dict z1, h1, dh1, z2, h2, dh2, y (+ m_*).  kink = {"z1": tau1, "z2": tau2}
+    (forward-only callers, tests/policy_reference.py): where |z| <= tau m(z) the activation's magnitude is m(z) -- ReLU and
+    ELU are 1-Lipschitz -- instead of the learner's rule above (None: the learner's rule)"""
     w1, b1, w2, b2, w3, b3 = (net[f] for f in NET_FIELDS)
     mx = x.abs() if mx is None else mx
     f = {"x": x, "m_x": mx}
+
+    def act(k):
+        h, mh, d, md = _act(f["z" + k], f["m_z" + k], activation)
+        if kink is not None:
+            mz = f["m_z" + k]
+            mh = torch.where(f["z" + k].abs() <= kink["z" + k] * mz, torch.maximum(mh, mz), mh)
+        f["h" + k], f["m_h" + k], f["dh" + k], f["m_dh" + k] = h, mh, d, md
+
     f["z1"] = x @ w1.t() + b1
     f["m_z1"] = mx @ w1.abs().t() + b1.abs()
-    f["h1"], f["m_h1"], f["dh1"], f["m_dh1"] = _act(f["z1"], f["m_z1"], activation)
+    act("1")
     f["z2"] = f["h1"] @ w2.t() + b2
     f["m_z2"] = f["m_h1"] @ w2.abs().t() + b2.abs()
-    f["h2"], f["m_h2"], f["dh2"], f["m_dh2"] = _act(f["z2"], f["m_z2"], activation)
+    act("2")
     f["y"] = f["h2"] @ w3.t() + b3
     f["m_y"] = f["m_h2"] @ w3.abs().t() + b3.abs()
     return f
