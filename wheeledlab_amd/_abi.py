@@ -273,6 +273,25 @@ VIEWER_SIGNATURES = {
                                    _vp]),
 }
 
+# include/wheeledlab_amd_terrain.h: mesh terrains -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)
+WL_TERRAIN_VERSION = 1
+TERRAIN_TILE = 16
+TERRAIN_MAX_TILES_PER_FACE = 64
+TERRAIN_MAX_SIDE = 1 << 23
+TERRAIN_STATUS_WORDS = 4      # invalid faces, faces binned, faces on the big list, per-tile list entries
+
+
+class WlMeshRasterParams(C.Structure):
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("fill_z", C.c_float)]
+
+
+# every symbol include/wheeledlab_amd_terrain.h declares
+TERRAIN_SIGNATURES = {
+    "wl_terrain_version": (C.c_int, []),
+    "wl_mesh_raster_scratch_bytes": (C.c_int64, [_i32, _i32, _i32]),
+    "wl_mesh_raster": (C.c_int, [_P(WlMeshRasterParams), _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -295,7 +314,7 @@ def load(path: str | None = None):
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -306,6 +325,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has ABI version {v}, python expects {WL_ABI_VERSION}: rebuild")
     if lib.wl_viewer_version() != WL_VIEWER_VERSION:
         raise HipExtensionMissing(f"{path} has viewer version {lib.wl_viewer_version()}, python expects {WL_VIEWER_VERSION}: rebuild")
+    if lib.wl_terrain_version() != WL_TERRAIN_VERSION:
+        raise HipExtensionMissing(f"{path} has terrain version {lib.wl_terrain_version()}, python expects {WL_TERRAIN_VERSION}: rebuild")
     _lib = lib
     return lib
 

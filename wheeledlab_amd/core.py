@@ -122,6 +122,59 @@ class DeviceHeightField:
         return self.heights, self.x0, self.y0, self.cell
 
 
+def mesh_heightfield(vertices, faces, cell: float, device="cuda:0", lattice=None, fill_z: float = 0.0, stats: dict | None = None):
+    """Rasterise a triangle mesh into a height lattice on the device (include/wheeledlab_amd_terrain.h: wl_mesh_raster): at each
+    lattice point the highest triangle whose xy projection contains it, `fill_z` where none does -- what a height scanner casting
+    straight down returns.  `vertices` float [V, 3] (world, metres) and `faces` int [F, 3], arrays or tensors; `lattice` = (x0, y0,
+    nx, ny), or None for the mesh's xy bounds on multiples of `cell`.  -> (heights float32 [ny, nx] on `device`, x0, y0, cell): the
+    tuple DeviceHeightField, ElevBatch(heightfield=...), VisualDepthBatch(heightfield=...) and scene.terrain.heightfield take.
+    Raises ValueError for faces with an index outside [0, V) or a non-finite vertex (one synchronisation: the launch's status).
+    `stats`: a dict that receives the launch's status words (invalid, binned, big, entries: WL_TERRAIN_STATUS_WORDS)."""
+    dev = _canonical_device(device)
+    v = torch.as_tensor(vertices).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    f = torch.as_tensor(faces).to(dev).reshape(-1, 3)
+    if f.dtype.is_floating_point or f.dtype == torch.bool:
+        raise ValueError("faces must be integer vertex indices")
+    if f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) >= 2 ** 31):
+        raise ValueError("face indices beyond int32")
+    f = f.to(torch.int32).contiguous()
+    c32 = float(torch.tensor(cell, dtype=torch.float32))
+    if not (math.isfinite(c32) and c32 > 0):
+        raise ValueError("cell must be positive and finite")
+    if lattice is None:
+        if v.shape[0] == 0:
+            raise ValueError("an empty mesh has no bounds: pass lattice=(x0, y0, nx, ny)")
+        lo, hi = v[:, :2].double().min(0).values.tolist(), v[:, :2].double().max(0).values.tolist()
+        if not all(math.isfinite(a) for a in lo + hi):
+            raise ValueError("mesh with non-finite vertex coordinates")
+        x0, y0 = (float(torch.tensor(c32 * math.floor(a / c32), dtype=torch.float32)) for a in lo)
+        nx, ny = (max(2, math.ceil((b - a) / c32) + 1) for a, b in zip((x0, y0), hi))
+    else:
+        x0, y0, nx, ny = lattice
+        x0, y0, nx, ny = float(torch.tensor(x0, dtype=torch.float32)), float(torch.tensor(y0, dtype=torch.float32)), int(nx), int(ny)
+    lib = A.load()
+    if not math.isfinite(float(fill_z)):
+        raise ValueError("fill_z must be finite")
+    fits = max(abs(nx), abs(ny), f.shape[0], v.shape[0]) < 2 ** 31
+    need = lib.wl_mesh_raster_scratch_bytes(f.shape[0], nx, ny) if fits else -1
+    if need <= 0:
+        raise ValueError(f"a lattice of {nx} x {ny} points (2 .. {A.TERRAIN_MAX_SIDE - 1} each, at most 2^31 - 1 in all) for "
+                         f"{f.shape[0]} faces is out of range")
+    p = A.WlMeshRasterParams(x0, y0, c32, nx, ny, float(fill_z))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    heights = torch.empty((ny, nx), dtype=torch.float32, device=dev)
+    status = torch.zeros(A.TERRAIN_STATUS_WORDS, dtype=torch.int32, device=dev)
+    A.check(lib.wl_mesh_raster(C.byref(p), v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], scratch.data_ptr(), need, heights.data_ptr(),
+                               status.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wl_mesh_raster")
+    words = status.tolist()
+    if stats is not None:
+        stats.update(zip(("invalid", "binned", "big", "entries"), words))
+    bad = words[0]
+    if bad:
+        raise ValueError(f"{bad} of {f.shape[0]} faces have a vertex index outside [0, {v.shape[0]}) or a non-finite vertex")
+    return heights, x0, y0, c32
+
+
 def ring_plan(step0: int, n_steps: int, slots: int):
     """How a persistent launch of `n_steps` steps from step `step0` runs on a metric ring of `slots` slots.  The launch folds all
     its steps into slot step0 % R and clears slot (step0 + n) % R for its successor.  Returns (segments, zero):

@@ -390,8 +390,20 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     p.cmd_xy, p.cmd_heading = _sym(cmd.ranges.pos_x, "command x"), _sym(cmd.ranges.heading, "command heading")
     p.cmd_resample_s = float(cmd.resampling_time_range[1])
     flat.curriculum = _terms(cfg.curriculum)
-    flat.extra["heightfield"] = getattr(cfg.scene.terrain, "heightfield", None)
+    flat.extra.update(_terrain_source(cfg.scene.terrain))
     return flat
+
+
+def _terrain_source(t) -> dict:
+    """the terrain of a heightfield task: `heightfield` (an array), `mesh_path` (an OBJ rasterised at `mesh_cell`), or neither (the
+    synthetic field) -- never both"""
+    hf, mesh = getattr(t, "heightfield", None), getattr(t, "mesh_path", None)
+    if hf is not None and mesh is not None:
+        raise ValueError("scene.terrain: set `heightfield` or `mesh_path`, not both")
+    cell = float(getattr(t, "mesh_cell", 0.05))
+    if mesh is not None and not (math.isfinite(cell) and cell > 0):
+        raise ValueError("scene.terrain.mesh_cell must be positive and finite")
+    return dict(heightfield=hf, mesh_path=None if mesh is None else str(mesh), mesh_cell=cell)
 
 
 def flatten_visual_cfg(cfg) -> FlatTaskCfg:
@@ -453,7 +465,7 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     if depth_task:      # extension task: heightfield terrain + the depth image as observation (tasks/visual_depth)
         flat.task, flat.obs_dim = "visual_depth", A.VISDEPTH_OBS_DIM
         clip = getattr(cam.spawn, "clipping_range", None) or (0.01, 20.0)
-        flat.extra.update(heightfield=getattr(t, "heightfield", None), max_depth=float(clip[1]), augment=False)
+        flat.extra.update(_terrain_source(t), max_depth=float(clip[1]), augment=False)
     return flat
 
 

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from .. import _abi as A
-from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
+from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch, mesh_heightfield
+from ..terrain import load_obj
 from .configclass import fields_of
 from .flatten import flatten_cfg
 from .scene import SceneView
@@ -228,6 +229,8 @@ class ManagerBasedRLEnv:
         seed = 42 if cfg.seed is None else int(cfg.seed)
         common = dict(device=self.device, params=flat.params, seed=seed, env_offset=rank * self.num_envs,
                       metrics_slots=int(cfg.metrics_slots), startup=flat.startup)
+        if flat.extra.get("mesh_path") is not None:      # a mesh terrain: rasterised once, then a heightfield like any other
+            flat.extra["heightfield"] = mesh_heightfield(*load_obj(flat.extra["mesh_path"]), flat.extra["mesh_cell"], device=self.device)
         if flat.task == "elevation":
             self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), **common)
         elif flat.task in ("visual", "visual_depth"):

@@ -1,7 +1,8 @@
 """Elevation task configuration -- same config surface (class / term names, values) as the reference's
 wheeledlab_tasks/elevation/mushr_elevation_env_cfg.py; line citations inline.  Terms are the kernel-backed ones of
-`wheeledlab_amd.envs.mdp`.  The terrain is a heightfield (the reference's USD mesh is missing): pass your own
-`(height, x0, y0, cell)` in `scene.terrain.heightfield`, or leave None for the synthetic one."""
+`wheeledlab_amd.envs.mdp`.  The terrain is a heightfield: pass your own `(height, x0, y0, cell)` in `scene.terrain.heightfield`, or
+a triangle mesh as an OBJ file in `scene.terrain.mesh_path` (the reference's `huge_compact.usd`, exported, or your own: rasterised on
+the device at `mesh_cell` metres, core.mesh_heightfield), or leave both None for the synthetic field."""
 from ...assets import MUSHR_SUS_CFG
 from ...envs import mdp
 from ...envs.configclass import configclass
@@ -44,6 +45,8 @@ class ElevationTerrainImporterCfg(TerrainImporterCfg):
     height = 0.25
     terrain_type = "heightfield"
     heightfield = None                 # (height[ny][nx] float32, x0, y0, cell); None -> wheeledlab_amd.terrain.synthetic_heightfield
+    mesh_path = None                   # Wavefront OBJ of the terrain mesh (z up, metres); exclusive with `heightfield`
+    mesh_cell = 0.05                   # lattice spacing (m) the mesh is rasterised at
     physics_material = RigidBodyMaterialCfg(friction_combine_mode="multiply", restitution_combine_mode="multiply",
                                             static_friction=1.0, dynamic_friction=1.0)
 

@@ -1,9 +1,12 @@
 """Heightfield terrain for the elevation task and the depth camera: a regular grid of 16-bit height CODES, z = code * z_scale --
 the representation of IsaacLab's own height-field terrains (isaaclab.terrains.height_field: int16 x vertical_scale).  The
-reference's terrain mesh (`Terrains/huge_compact.usd`, elevation/mushr_elevation_env_cfg.py:95-108) is missing from the snapshot;
-SURVEY.md 8d config 3 prescribes a synthetic 800 x 800 grid at 0.05 m (40 x 40 m, ramps + sine hills, seed 0).  Users with a real
-heightfield pass their own array to the env / ElevBatch instead: `(height, x0, y0, cell)` with float heights (quantised here,
-`quantize_heights`) or `(codes int16, x0, y0, cell, z_scale)` as an IsaacLab generator produced them."""
+reference drives on a triangle mesh (`Terrains/huge_compact.usd`, elevation/mushr_elevation_env_cfg.py:95-108), which is missing from
+the snapshot; SURVEY.md 8d config 3 prescribes a synthetic 800 x 800 grid at 0.05 m (40 x 40 m, ramps + sine hills, seed 0) in its
+place.  Users with a real heightfield pass their own array to the env / ElevBatch instead: `(height, x0, y0, cell)` with float
+heights (quantised here, `quantize_heights`) or `(codes int16, x0, y0, cell, z_scale)` as an IsaacLab generator produced them.  Users
+with a triangle mesh (that terrain exported to OBJ, or their own) read it with `load_obj` and rasterise it on the device with
+`core.mesh_heightfield` -- what the reference's downward height scanner sees at each lattice point -- or set
+`scene.terrain.mesh_path` in the task config."""
 from __future__ import annotations
 
 import numpy as np
@@ -63,3 +66,30 @@ def synthetic_heightfield(n: int = 800, cell: float = 0.05, seed: int = 0):
     h = BASE_Z + np.maximum(h, 0) * edge
     codes, zs = quantize_heights(h, Z_SCALE)
     return decode_heights(codes, zs), -half, -half, cell
+
+
+def load_obj(path):
+    """Wavefront OBJ -> (vertices float32 [V, 3], faces int32 [F, 3]).  Reads `v x y z` lines and `f` lines whose corners are `v`,
+    `v/vt`, `v/vt/vn` or `v//vn` (1-based; negative = relative to the vertices read so far); a polygon of n corners is fanned into
+    n - 2 triangles (0, k, k + 1).  Every other line (comments, normals, texture coordinates, groups, materials) is ignored."""
+    verts, faces = [], []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: a vertex needs x y z")
+                verts.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "f":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: a face needs at least three corners")
+                idx = []
+                for t in tok[1:]:
+                    k = int(t.split("/", 1)[0])
+                    if k == 0:
+                        raise ValueError(f"{path}:{ln}: OBJ indices start at 1")
+                    idx.append(k - 1 if k > 0 else len(verts) + k)
+                faces.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+    return (np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3).astype(np.int32))
