@@ -616,6 +616,60 @@ class DepthCamera:
         return out
 
 
+class LidarScanner:
+    """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
+    (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
+    field and pyramid come from the batch's cached DepthCamera (one pyramid per field, rebuilt when the field changes in place).
+    render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
+    the terrain (what a miss reads in the scene is LidarData's business)."""
+
+    def __init__(self, cfg=None, device="cuda:0"):
+        from .envs.sensors_cfg import LidarCfg
+        self.lib = A.load()
+        self.device = _canonical_device(device)
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("LidarScanner needs a HIP device; there is no CPU path")
+        self.cfg = cfg = cfg if cfg is not None else LidarCfg()
+        dirs = cfg.pattern_cfg.directions()
+        self.n_beams = int(dirs.shape[0])
+        if not 1 <= self.n_beams <= A.LIDAR_MAX_BEAMS:
+            raise ValueError(f"a lidar pattern of {self.n_beams} beams (1 .. {A.LIDAR_MAX_BEAMS})")
+        self.beam_dirs = torch.as_tensor(dirs, dtype=torch.float32).contiguous().to(self.device)
+        self.max_range = float(cfg.max_range)
+        if not (math.isfinite(self.max_range) and self.max_range > 0):
+            raise ValueError(f"lidar max_range must be positive and finite, got {cfg.max_range}")
+        q = [float(v) for v in cfg.offset_rot]
+        qn = math.sqrt(sum(v * v for v in q))
+        if not (math.isfinite(qn) and qn > 0):
+            raise ValueError(f"lidar offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
+        self.params = A.WlLidarParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
+                                      self.n_beams, self.max_range, int(bool(cfg.attach_yaw_only)))
+        self._plane = None
+
+    _stream = _EnvBatch._stream
+
+    def camera_of(self, batch) -> DepthCamera:
+        """the terrain the batch's cars stand on, as CameraData does it: the visual-depth task's own camera, the elevation task's
+        heightfield, else the z = 0 plane (a 3 x 3 zero grid: beyond it the outside plane is z = 0 as well)"""
+        if getattr(batch, "camera", None) is not None:
+            return batch.camera
+        if hasattr(batch, "hf"):
+            return _cached_depth_camera(batch, batch.hf)
+        if self._plane is None:       # one tensor per scanner: the batch's camera cache keys on it
+            self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
+        return _cached_depth_camera(batch, self._plane)
+
+    def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
+        """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
+        cam = camera if camera is not None else self.camera_of(batch)
+        if out is None:
+            out = torch.empty(batch.n, self.n_beams, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch.n, self.n_beams)
+        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam.pyramid.data_ptr(),
+                                       self.beam_dirs.data_ptr(), out.data_ptr(), self._stream()), "wl_lidar_scan")
+        return out
+
+
 def _cached_depth_camera(batch, heightfield) -> DepthCamera:
     """one DepthCamera per (batch, heightfield): the pyramid is a SNAPSHOT of the field, built on first use and rebuilt when the
     array object, its placement (x0, y0, cell), its shape or -- for tensors -- its in-place version counter changes"""

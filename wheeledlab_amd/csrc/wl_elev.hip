@@ -778,7 +778,11 @@ struct PolicyIo {
 constexpr int kColWavesA = 8;                                                  // wavefronts sharing the actor's first layer
 constexpr int kColChunks = (WL_ELEV_OBS_DIM + 15) / 16;                        // 44 (the last holds one feature)
 constexpr int kColMaxA = (kColChunks + kColWavesA - 1) / kColWavesA;           // 6
-constexpr int kTilePitch = (WL_ELEV_OBS_DIM + 3) / 4 * 4;                      // 692 floats: 16-byte aligned LDS rows
+// LDS row of one env's observation: the 44 chunks' 704 floats (the last chunk's 15 features past the 689th read the row's own
+// zeroed pad -- with a 692-float row they read the next row, and row 15 read past the tile into part_a, where 0 x a NaN / Inf
+// left there is NaN), + 4 so that the 16 rows start 4 banks apart (a multiple of 64 floats would put them all on one bank)
+constexpr int kTilePitch = kColChunks * 16 + 4;                                 // 708 floats: 16-byte aligned LDS rows
+static_assert(kTilePitch % 4 == 0 && kTilePitch % 64 == 4 && kTilePitch >= kColChunks * 16, "row layout");
 constexpr int kPartFloats = kColWavesA * kMlpTiles * 64 * 4;                   // one net's partial accumulators
 constexpr int kTailFloats = (kMlpTiles * kMlpHidSteps + kMlpHidSteps) * 64;    // an MlpTail, [value][lane]
 constexpr int kCarryWords = 20 + 3 + WL_ER_NTERMS + 4 + 2;                      // wavefront 0's rows + bookkeeping (carry_io), [word][lane]

@@ -310,6 +310,109 @@ class CameraView:
         self.num_instances = batch.n
 
 
+def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Hamilton product of (w, x, y, z) quaternions, broadcast over leading dimensions"""
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def _quat_apply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """R(q) v, q = (w, x, y, z): v + 2 w (u x v) + 2 u x (u x v)"""
+    w, u = q[..., 0:1], q[..., 1:4]
+    c = torch.cross(u, v, dim=-1)
+    return v + 2.0 * (w * c + torch.cross(u, c, dim=-1))
+
+
+class LidarData:
+    """`sensor.data` of a scene lidar (envs.sensors_cfg.LidarCfg; an IsaacLab RayCaster with a lidar pattern, un-vendored):
+    `output["linear_depth"]` [N, B] -- the ranges `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized` read (mdp_sensors/
+    observations.py:25-58) -- rendered by the lidar kernel (core.LidarScanner, wl_lidar_scan) against the task's terrain;
+    `ray_hits_w` [N, B, 3] (+inf where a beam meets nothing within max_range, as Warp's ray caster reports a miss); `pos_w` [N, 3]
+    and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like CameraData."""
+
+    def __init__(self, batch, cfg):
+        self._b, self._cfg, self._scanner = batch, cfg, None
+        self._cached = (None, None)       # ((step_count, pose_epoch), ranges): see CameraData
+        self.caching = True               # the env's constructor switches it off around its shape probe of the custom terms
+        self.max_range = float(cfg.max_range)
+        self.beyond = {"max": None, "zero": 0.0, "none": float("inf")}[cfg.miss_value]
+
+    def scanner(self):
+        if self._scanner is None:
+            from ..core import LidarScanner
+            self._scanner = LidarScanner(self._cfg, self._b.device)
+        return self._scanner
+
+    def ranges(self) -> torch.Tensor:
+        """the raw scan of the current poses: max_range on a miss (cached per env step; do not write into it)"""
+        stamp = (getattr(self._b, "step_count", None), getattr(self._b, "pose_epoch", None))
+        if not self.caching or None in stamp:
+            return self.scanner().render(self._b)
+        if self._cached[0] != stamp:
+            self._cached = (stamp, self.scanner().render(self._b))
+        return self._cached[1]
+
+    @property
+    def output(self):
+        return _LidarOutputs(self)
+
+    def _body_quat(self):
+        b = self._b
+        q = b.state[A.S_QW:A.S_QW + 4, : b.n].T
+        if not self._cfg.attach_yaw_only:
+            return q
+        # the yaw alone (IsaacLab's yaw_quat): the heading of the body's x axis in the world xy plane
+        w, x, y, z = q.unbind(-1)
+        yaw = torch.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
+        zero = torch.zeros_like(yaw)
+        return torch.stack([torch.cos(0.5 * yaw), zero, zero, torch.sin(0.5 * yaw)], -1)
+
+    @property
+    def pos_w(self):
+        b = self._b
+        off = torch.tensor(self._cfg.offset_pos, dtype=torch.float32, device=b.device).expand(b.n, 3)
+        return b.state[A.S_PX:A.S_PX + 3, : b.n].T + _quat_apply(self._body_quat(), off)
+
+    @property
+    def quat_w(self):
+        mount = torch.tensor(self.scanner().params.offset_quat[:], dtype=torch.float32, device=self._b.device)
+        return _quat_mul(self._body_quat(), mount.expand(self._b.n, 4))
+
+    @property
+    def ray_hits_w(self):
+        r = self.ranges()
+        q = self.quat_w
+        d = _quat_apply(q[:, None, :].expand(-1, r.shape[1], -1), self.scanner().beam_dirs[None].expand(r.shape[0], -1, -1))
+        hits = self.pos_w[:, None, :] + r[..., None] * d
+        return torch.where((r >= self.max_range)[..., None], torch.full_like(hits, float("inf")), hits)
+
+
+class _LidarOutputs:
+    def __init__(self, data):
+        self._d = data
+
+    def __getitem__(self, key):
+        if key != "linear_depth":
+            raise KeyError(f"lidar data type {key!r} is not rendered here (the scan gives 'linear_depth')")
+        d = self._d
+        r = d.ranges()
+        if d.beyond is not None:      # what a miss reads is applied per read, the scan itself is cached
+            r = torch.where(r >= d.max_range, torch.full_like(r, d.beyond), r)
+        return r
+
+    def keys(self):
+        return ["linear_depth"]
+
+
+class LidarView:
+    def __init__(self, batch, cfg):
+        self.cfg = cfg
+        self.data = LidarData(batch, cfg)
+        self.num_instances = batch.n
+
+
 class SceneView:
     def __init__(self, batch, cfg=None, task: str = "drift"):
         self._b = batch
@@ -323,6 +426,10 @@ class SceneView:
             self.sensors["height_scanner"] = RayCasterView(batch, cfg.height_scanner)
         if getattr(cfg, "camera", None) is not None:
             self.sensors["camera"] = CameraView(batch, cfg.camera)
+        from .sensors_cfg import LidarCfg
+        for name, value in (vars(cfg).items() if cfg is not None else ()):     # every lidar of the scene, under its attribute name
+            if isinstance(value, LidarCfg):
+                self.sensors[name] = LidarView(batch, value)
         self.terrain = getattr(cfg, "terrain", None)
 
     def __getitem__(self, key):
