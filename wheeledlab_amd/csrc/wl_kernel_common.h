@@ -264,6 +264,8 @@ inline bool use_quad(const WlEnvBuffers* b) {
 // thread's HIP error slot: clear it before the launch so launch_status() reports only our own launch.
 inline void clear_error() { (void)hipGetLastError(); }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? WL_OK : WL_ELAUNCH; }
-
+inline bool finite_pos(float x) { return x > 0.f && x < INFINITY; }
+inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+inline bool aligned(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }   // a: a power of two
 
 }  // namespace
