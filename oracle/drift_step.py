@@ -4,14 +4,13 @@ SoA state matrix as the kernel (rows = include/wheeledlab_amd.h WlStateField).""
 import numpy as np
 
 from . import drift_mdp as M
+from . import env_step as ES
 from . import philox as PH
 from . import vehicle as V
-from .mathlib import F, f32, matrix_from_quat
-
-# row indices (include/wheeledlab_amd.h)
-PX, QW, VX, WX, WHEEL, STEER_POS, STEER_VEL, ACT0, TIMER_HF, TIMER_LF, MU_S, MU_D, DAMP, MASS, EPSUM0, S_COUNT = \
-    0, 3, 7, 10, 13, 17, 18, 19, 21, 22, 23, 24, 25, 26, 27, 35
-M_EPSUM0, M_RESETS, M_TIMEOUTS, M_TERM0, M_NONFINITE, M_EPLEN, M_COUNT = 0, 8, 9, 10, 14, 15, 16
+from .layout import ACT0, DAMP, DRIFT_ROWS, EPSUM0, MASS, MU_D, MU_S, PX, QW, TIMER_HF, TIMER_LF, VX, WX
+from .layout import (STEER_POS, STEER_VEL, WHEEL, M_COUNT, M_EPLEN, M_EPSUM0, M_NONFINITE, M_RESETS,  # noqa: F401 -- re-exported
+                     M_TERM0, M_TIMEOUTS)
+from .mathlib import F
 
 
 def targets(p, a_raw):
@@ -51,73 +50,26 @@ def reset_envs(p, state, episode_len, ref_table, ids, seed, step, env_offset=0):
 
 
 def observe(p, state, normals):
-    n = state.shape[1]
-    q = state[QW:QW + 4].T
-    R = matrix_from_quat(q)
-    v_b = np.einsum("nji,nj->ni", R, state[VX:VX + 3].T).astype(F)
-    w_b = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
-    return M.blind_obs(p, state[PX:PX + 3].T, q, v_b, w_b, state[ACT0:ACT0 + 2].T, normals)
+    v_b, w_b = ES.body_velocities(state)
+    return M.blind_obs(p, state[PX:PX + 3].T, state[QW:QW + 4].T, v_b, w_b, state[ACT0:ACT0 + 2].T, normals)
 
 
 def step(p, state, episode_len, ref_table, actions, seed, step_count, metrics=None, noise=None, env_offset=0,
          ground=V.flat_ground):
-    """state [S_COUNT, n] float32 and episode_len [n] int32 are updated IN PLACE.
+    """state [DRIFT_ROWS, n] float32 and episode_len [n] int32 are updated IN PLACE.
     -> obs [n,14], reward [n], terminated [n] bool, truncated [n] bool, info dict"""
     n = state.shape[1]
-    vp = p.vehicle
-    a_raw = M.clip_action(actions) if p.action.clip_wrapper else f32(actions)
-    state[ACT0:ACT0 + 2] = a_raw.T
-    steer_t, wheel_t = targets(p, a_raw)
+    steer_t, wheel_t = targets(p, ES.apply_action(p, state, actions))
+    b = ES.integrate(p, state, steer_t, wheel_t, ground)
+    truncated, finite = ES.count_step(p, state, episode_len)
+    terminated = np.logical_or(M.cart_off_track(b.pos, p.straight, p.r_in, p.r_out), ~finite)
 
-    q = state[QW:QW + 4].T.copy()
-    R = matrix_from_quat(q)
-    c = f32([0, 0, vp.cg_z])
-    x = (state[PX:PX + 3].T + R @ c).astype(F)
-    v = state[VX:VX + 3].T.copy()
-    wb = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
-    wheel = state[WHEEL:WHEEL + 4].T.copy()
-    th, om = state[STEER_POS].copy(), state[STEER_VEL].copy()
-    mass, mu_s, mu_d, damp = state[MASS], state[MU_S], state[MU_D], state[DAMP]
-    h = F(p.sim_dt) / F(vp.substeps)
-    for _ in range(p.decimation * vp.substeps):
-        x, q, v, wb, wheel, th, om = V.substep(x, q, v, wb, wheel, th, om, steer_t, wheel_t, mass, mu_s, mu_d, damp,
-                                               vp, h, ground)
-    R = matrix_from_quat(q)
-    ww = np.einsum("nij,nj->ni", R, wb).astype(F)
-    pos = (x - R @ c).astype(F)
-    state[PX:PX + 3] = pos.T
-    state[QW:QW + 4] = q.T
-    state[VX:VX + 3] = v.T
-    state[WX:WX + 3] = ww.T
-    state[WHEEL:WHEEL + 4] = wheel.T
-    state[STEER_POS], state[STEER_VEL] = th, om
-
-    episode_len += 1
-    truncated = M.time_out(episode_len, p.max_episode_length)
-    finite = np.isfinite(state[:19]).all(0)
-    terminated = np.logical_or(M.cart_off_track(pos, p.straight, p.r_in, p.r_out), ~finite)
-
-    v_b = np.einsum("nji,nj->ni", R, v).astype(F)
-    steer2 = np.stack([th, th], -1)
-    terms = M.drift_terms(p, pos, v_b, wb, ww, steer2, terminated, truncated)
-    terms = np.where(finite[None, :], terms, F(0)).astype(F)
-    reward, contrib = M.reward_sum(p, terms)
-    if p.log_episode_sums:
-        state[EPSUM0:EPSUM0 + 7] += contrib
+    terms = M.drift_terms(p, b.pos, b.v_b, b.wb, b.ww, np.stack([b.th, b.th], -1), terminated, truncated)
+    terms, reward = ES.book_rewards(p, state, terms, finite)
 
     done = np.logical_or(terminated, truncated)
-    ids = np.nonzero(done)[0]
-    if metrics is not None and len(ids):
-        metrics[M_EPSUM0:M_EPSUM0 + 8] += state[EPSUM0:EPSUM0 + 8, ids].astype(np.float64).sum(1)
-        metrics[M_RESETS] += len(ids)
-        metrics[M_TIMEOUTS] += truncated.sum()
-        metrics[M_TERM0] += terminated.sum()
-        metrics[M_NONFINITE] += (~finite).sum()
-        metrics[M_EPLEN] += episode_len[ids].sum()
-    if (~finite).any():  # scrub so the reset below starts from clean rows
-        bad = np.nonzero(~finite)[0]
-        state[:19, bad] = 0
-        state[QW, bad] = 1
+    # M_TERM0: every terminated car, the non-finite ones included
+    ids = ES.end_episodes(state, episode_len, metrics, done, truncated, finite, [terminated.sum()])
     reset_envs(p, state, episode_len, ref_table, ids, seed, step_count, env_offset)
 
     step_dt = F(p.sim_dt) * F(p.decimation)
@@ -126,16 +78,15 @@ def step(p, state, episode_len, ref_table, actions, seed, step_count, metrics=No
         state[TIMER_HF] -= step_dt
         fire = state[TIMER_HF] < F(1e-6)
         u = PH.uniform8(gid, step_count, PH.S_NOISE1, seed)[4:]       # words z, w of the block whose x, y are normals 8..11
-        sym = lambda uu, a: (F(2) * uu - F(1)) * F(a)
-        state[VX] += np.where(fire, sym(u[0], p.hf_vel_x), F(0))
-        state[VX + 1] += np.where(fire, sym(u[1], p.hf_vel_y), F(0))
-        state[WX + 2] += np.where(fire, sym(u[2], p.hf_vel_yaw), F(0))
+        state[VX] += np.where(fire, ES.sym(u[0], p.hf_vel_x), F(0))
+        state[VX + 1] += np.where(fire, ES.sym(u[1], p.hf_vel_y), F(0))
+        state[WX + 2] += np.where(fire, ES.sym(u[2], p.hf_vel_yaw), F(0))
         state[TIMER_HF] = np.where(fire, F(p.hf_interval[0]) + u[3] * (F(p.hf_interval[1]) - F(p.hf_interval[0])),
                                    state[TIMER_HF])
         state[TIMER_LF] -= step_dt
         fire = state[TIMER_LF] < F(1e-6)
         u = PH.uniform8(gid, step_count, PH.S_DRIFT_EVENTS, seed)[6:]  # word w of the event block
-        state[WX + 2] += np.where(fire, sym(u[0], p.lf_vel_yaw), F(0))
+        state[WX + 2] += np.where(fire, ES.sym(u[0], p.lf_vel_yaw), F(0))
         state[TIMER_LF] = np.where(fire, F(p.lf_interval[0]) + u[1] * (F(p.lf_interval[1]) - F(p.lf_interval[0])),
                                    state[TIMER_LF])
 
@@ -152,7 +103,7 @@ def init_state(p, n, seed=0, stride=None, env_offset=0):
     env id (oracle/startup.py), like the product's wl_startup_randomize."""
     from . import startup
     stride = stride or ((n + 63) // 64) * 64
-    s = np.zeros((S_COUNT, stride), F)
+    s = np.zeros((DRIFT_ROWS, stride), F)
     s[QW] = 1
     s[MU_S, :n], s[MU_D, :n], s[DAMP, :n], s[MASS, :n], _ = startup.draw(n, seed, env_offset, **startup.DRIFT)
     return s

@@ -3,17 +3,16 @@ order of IsaacLab's ManagerBasedRLEnv.step() with the reference's elevation plug
 (wheeledlab_tasks/elevation/mushr_elevation_env_cfg.py)."""
 import numpy as np
 
-from . import drift_mdp as M
 from . import elev_mdp as E
+from . import env_step as ES
 from . import heightfield as H
 from . import philox as PH
-from . import vehicle as V
-from .drift_step import ACT0, DAMP, EPSUM0, MASS, MU_D, MU_S, PX, QW, STEER_POS, STEER_VEL, VX, WHEEL, WX
-from .mathlib import F, f32, matrix_from_quat, euler_xyz_from_quat
+from .env_step import sym
+from .layout import ACT0, CMD_BX, CMD_BY, CMD_TIMER, DAMP, EPSUM0, MASS, MU_D, MU_S, PX, QW, S_COUNT, TGT_H, TGT_X, TGT_Y, VX
+from .layout import M_EPLEN, M_EPSUM0, M_NONFINITE, M_RESETS, M_TERM0, M_TIMEOUTS  # noqa: F401 -- re-exported
+from .mathlib import F, f32, euler_xyz_from_quat
 from .params import NS, mushr_action, mushr_vehicle
 
-CMD_BX, CMD_BY, TGT_X, TGT_Y, TGT_H, CMD_TIMER, S_COUNT = 35, 36, 37, 38, 39, 40, 41
-M_EPSUM0, M_RESETS, M_TIMEOUTS, M_TERM0, M_NONFINITE, M_EPLEN = 0, 8, 9, 10, 14, 15
 S_RESET, S_CMD_RESET, S_CMD_RESAMPLE = 0, 1, 2
 N_RAYS = 26
 OBS_DIM = 13 + N_RAYS * N_RAYS
@@ -71,10 +70,6 @@ def update_command(state, ids=slice(None)):
     state[CMD_BY, ids] = -s * dx + c * dy
 
 
-def sym(u, a):
-    return (F(2) * u - F(1)) * F(a)
-
-
 def reset_envs(p, state, episode_len, hf, ids, seed, step, env_offset=0):
     if len(ids) == 0:
         return
@@ -121,9 +116,7 @@ def height_map(p, state, hf):
 
 def observe(p, state, hf):
     q = state[QW:QW + 4].T
-    R = matrix_from_quat(q)
-    v_b = np.einsum("nji,nj->ni", R, state[VX:VX + 3].T).astype(F)
-    w_b = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
+    v_b, w_b = ES.body_velocities(state)
     goal = E.goal_relative_xyz(state[PX:PX + 3].T, state[CMD_BX:CMD_BX + 2].T)
     c = F(p.obs_clip)
     return np.concatenate([goal, np.stack(euler_xyz_from_quat(q), -1), np.clip(v_b, -c, c), np.clip(w_b, -c, c),
@@ -132,75 +125,28 @@ def observe(p, state, hf):
 
 def step(p, state, episode_len, hf, actions, seed, step_count, metrics=None, env_offset=0, probe=None):
     n = state.shape[1]
-    vp = p.vehicle
-    a_raw = M.clip_action(actions) if p.action.clip_wrapper else f32(actions)
-    state[ACT0:ACT0 + 2] = a_raw.T
-    proc = M.process_actions(a_raw, p.action)
-    steer2, wheel_t = M.fwd_targets(proc[:, 0], proc[:, 1], p.action)
-    steer_t = steer2[:, 0]
-    q = state[QW:QW + 4].T.copy()
-    R = matrix_from_quat(q)
-    cvec = f32([0, 0, vp.cg_z])
-    x = (state[PX:PX + 3].T + R @ cvec).astype(F)
-    v = state[VX:VX + 3].T.copy()
-    wb = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
-    wheel = state[WHEEL:WHEEL + 4].T.copy()
-    th, om = state[STEER_POS].copy(), state[STEER_VEL].copy()
-    h = F(p.sim_dt) / F(vp.substeps)
-    g = ground_fn(hf, probe)
-    for _ in range(p.decimation * vp.substeps):
-        x, q, v, wb, wheel, th, om = V.substep(x, q, v, wb, wheel, th, om, steer_t, wheel_t.astype(F), state[MASS],
-                                               state[MU_S], state[MU_D], state[DAMP], vp, h, g, probe)
-    R = matrix_from_quat(q)
-    ww = np.einsum("nij,nj->ni", R, wb).astype(F)
-    pos = (x - R @ cvec).astype(F)
-    state[PX:PX + 3], state[QW:QW + 4], state[VX:VX + 3], state[WX:WX + 3] = pos.T, q.T, v.T, ww.T
-    state[WHEEL:WHEEL + 4] = wheel.T
-    state[STEER_POS], state[STEER_VEL] = th, om
-
-    episode_len += 1
-    truncated = episode_len >= p.max_episode_length
-    finite = np.isfinite(state[:19]).all(0)
-    v_b = np.einsum("nji,nj->ni", R, v).astype(F)
+    steer_t, wheel_t = ES.fwd_targets(p, ES.apply_action(p, state, actions))
+    b = ES.integrate(p, state, steer_t, wheel_t, ground_fn(hf, probe), probe)
+    truncated, finite = ES.count_step(p, state, episode_len)
+    pos, v_b = b.pos, b.v_b
     cmd = state[CMD_BX:CMD_BX + 2].T                     # command as left by the PREVIOUS step's command update
     t_low = E.root_height_below_minimum(pos, p.min_height)
     t_stuck = np.logical_and(np.minimum(v_b[:, 0], F(p.stuck_vel_cap)) < F(p.stuck_min_vel),
-                             wheel.sum(-1) > F(p.stuck_wheel_spin))
-    t_roll = R[:, 2, 2] <= F(p.upright_cos)   # the fp32 tie at cos 60 deg is rolled over (elev_mdp.upright_penalty)
+                             b.wheel.sum(-1) > F(p.stuck_wheel_spin))
+    t_roll = b.R[:, 2, 2] <= F(p.upright_cos)   # the fp32 tie at cos 60 deg is rolled over (elev_mdp.upright_penalty)
     t_goal = E.close_to_goal(pos, cmd, p.goal_dist)
+    flags = (t_low, t_stuck, t_roll, t_goal)
     terminated = t_low | t_stuck | t_roll | t_goal | ~finite
     with np.errstate(invalid="ignore", divide="ignore"):
-        terms = np.stack([E.goal_progress_rate(pos, v, cmd), E.higher_elevation(pos, v_b),
+        terms = np.stack([E.goal_progress_rate(pos, b.v, cmd), E.higher_elevation(pos, v_b),
                           E.is_falling_penalty(v_b, p.fall_vel).astype(F),
                           (t_stuck & ~truncated).astype(F)]).astype(F)
-    terms = np.where(finite[None], terms, F(0)).astype(F)
-    step_dt = F(p.sim_dt) * F(p.decimation)
-    reward = np.zeros(n, F)
-    for i in range(4):
-        w = F(p.weight[i])
-        if w == 0:
-            continue
-        c = terms[i] * w * step_dt
-        reward += c
-        if p.log_episode_sums:
-            state[EPSUM0 + i] += c
-    done = terminated | truncated
-    ids = np.nonzero(done)[0]
-    if metrics is not None and len(ids):
-        metrics[M_EPSUM0:M_EPSUM0 + 8] += state[EPSUM0:EPSUM0 + 8, ids].astype(np.float64).sum(1)
-        metrics[M_RESETS] += len(ids)
-        metrics[M_TIMEOUTS] += truncated.sum()
-        for k, t in enumerate((t_low, t_stuck, t_roll, t_goal)):
-            metrics[M_TERM0 + k] += t.sum()
-        metrics[M_NONFINITE] += (~finite).sum()
-        metrics[M_EPLEN] += episode_len[ids].sum()
-    if (~finite).any():
-        bad = np.nonzero(~finite)[0]
-        state[:19, bad] = 0
-        state[QW, bad] = 1
+    terms, reward = ES.book_rewards(p, state, terms, finite)
+    # M_TERM0..3: each flag over ALL envs, whatever else ended the episode
+    ids = ES.end_episodes(state, episode_len, metrics, terminated | truncated, truncated, finite, [t.sum() for t in flags])
     reset_envs(p, state, episode_len, hf, ids, seed, step_count, env_offset)
     # command manager: count down, resample expired targets, re-express every target in the base frame
-    state[CMD_TIMER] -= step_dt
+    state[CMD_TIMER] -= F(p.sim_dt) * F(p.decimation)
     exp = state[CMD_TIMER] <= 0
     if exp.any():
         u = PH.uniform4(np.arange(n) + env_offset, step_count, S_CMD_RESAMPLE, seed)
@@ -210,8 +156,7 @@ def step(p, state, episode_len, hf, actions, seed, step_count, metrics=None, env
         state[CMD_TIMER] = np.where(exp, F(p.cmd_resample_s), state[CMD_TIMER])
     update_command(state)
     obs = observe(p, state, hf)
-    return obs, reward.astype(F), terminated, truncated, dict(terms=terms, terms_flags=(t_low, t_stuck, t_roll, t_goal),
-                                                              finite=finite)
+    return obs, reward, terminated, truncated, dict(terms=terms, terms_flags=flags, finite=finite)
 
 
 def init_state(p, n, seed=0, stride=None, env_offset=0):

@@ -8,19 +8,18 @@ import math
 
 import numpy as np
 
-from . import drift_mdp as M
+from . import env_step as ES
 from . import philox as PH
 from . import vehicle as V
 from . import visual_mdp as VM
-from .drift_step import ACT0, DAMP, EPSUM0, MASS, MU_D, MU_S, PX, QW, STEER_POS, STEER_VEL, VX, WHEEL, WX
+from .layout import ACT0, DAMP, EPSUM0, MASS, MU_D, MU_S, PX, QW, S_COUNT, VX
+from .layout import M_EPLEN, M_EPSUM0, M_NONFINITE, M_RESETS, M_TERM0, M_TIMEOUTS  # noqa: F401 -- re-exported
 from .mathlib import F, f32, matrix_from_quat
 from .params import NS, mushr_action, mushr_vehicle
 
-S_COUNT = 41
 IMG_H, IMG_W, CROP = 60, 80, 20
 N_PIX = (IMG_H - CROP) * IMG_W
 OBS_DIM = N_PIX + 8
-M_EPSUM0, M_RESETS, M_TIMEOUTS, M_TERM0, M_NONFINITE, M_EPLEN = 0, 8, 9, 10, 14, 15
 
 
 def visual_params():
@@ -120,9 +119,7 @@ def camera(p, state, trav):
 
 
 def observe(p, state, trav):
-    R = matrix_from_quat(state[QW:QW + 4].T)
-    v_b = np.einsum("nji,nj->ni", R, state[VX:VX + 3].T).astype(F)
-    w_b = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
+    v_b, w_b = ES.body_velocities(state)
     return np.concatenate([camera(p, state, trav), v_b, w_b, np.clip(state[ACT0:ACT0 + 2].T, F(-1), F(1))], -1).astype(F)
 
 
@@ -131,9 +128,7 @@ def observe_depth(p, state, hf, max_depth):
     (oracle/depth.c) | base_lin_vel | base_ang_vel | last_action.  hf: a 5-tuple carries the field's outside_z"""
     from . import depth as D
     from . import heightfield as H
-    R = matrix_from_quat(state[QW:QW + 4].T)
-    v_b = np.einsum("nji,nj->ni", R, state[VX:VX + 3].T).astype(F)
-    w_b = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
+    v_b, w_b = ES.body_velocities(state)
     img = D.depth(p, state[PX:PX + 3].T.copy(), state[QW:QW + 4].T.copy(), H.unpack(hf)[:4], max_depth,
                   H.unpack(hf)[4]).reshape(state.shape[1], -1)
     return np.concatenate([img, v_b, w_b, np.clip(state[ACT0:ACT0 + 2].T, F(-1), F(1))], -1).astype(F)
@@ -143,69 +138,25 @@ def step(p, state, episode_len, trav, cells, actions, seed, step_count, metrics=
     """hf / max_depth: the visual-depth extension task -- the same step on the heightfield terrain `hf` (wheel contacts through
     heightfield.sample, reset onto the terrain), observation = observe_depth"""
     n = state.shape[1]
-    vp = p.vehicle
-    a_raw = M.clip_action(actions) if p.action.clip_wrapper else f32(actions)
-    state[ACT0:ACT0 + 2] = a_raw.T
-    proc = M.process_actions(a_raw, p.action)
-    steer2, wheel_t = M.fwd_targets(proc[:, 0], proc[:, 1], p.action)
-    q = state[QW:QW + 4].T.copy()
-    R = matrix_from_quat(q)
-    cvec = f32([0, 0, vp.cg_z])
-    x = (state[PX:PX + 3].T + R @ cvec).astype(F)
-    v = state[VX:VX + 3].T.copy()
-    wb = np.einsum("nji,nj->ni", R, state[WX:WX + 3].T).astype(F)
-    wheel = state[WHEEL:WHEEL + 4].T.copy()
-    th, om = state[STEER_POS].copy(), state[STEER_VEL].copy()
-    h = F(p.sim_dt) / F(vp.substeps)
+    steer_t, wheel_t = ES.fwd_targets(p, ES.apply_action(p, state, actions))
     ground = V.flat_ground
     if hf is not None:
         from .elev_step import ground_fn
         ground = ground_fn(hf, probe)
-    for _ in range(p.decimation * vp.substeps):
-        x, q, v, wb, wheel, th, om = V.substep(x, q, v, wb, wheel, th, om, steer2[:, 0], wheel_t.astype(F), state[MASS],
-                                               state[MU_S], state[MU_D], state[DAMP], vp, h, ground, probe)
-    R = matrix_from_quat(q)
-    ww = np.einsum("nij,nj->ni", R, wb).astype(F)
-    pos = (x - R @ cvec).astype(F)
-    state[PX:PX + 3], state[QW:QW + 4], state[VX:VX + 3], state[WX:WX + 3] = pos.T, q.T, v.T, ww.T
-    state[WHEEL:WHEEL + 4] = wheel.T
-    state[STEER_POS], state[STEER_VEL] = th, om
-    episode_len += 1
-    truncated = episode_len >= p.max_episode_length
-    finite = np.isfinite(state[:19]).all(0)
+    b = ES.integrate(p, state, steer_t, wheel_t, ground, probe)
+    truncated, finite = ES.count_step(p, state, episode_len)
     width, height = p.map_rows * p.row_spacing, p.map_cols * p.col_spacing
-    oom = VM.out_of_map(pos, width, height)
+    oom = VM.out_of_map(b.pos, width, height)
     terminated = oom | ~finite
-    v_b = np.einsum("nji,nj->ni", R, v).astype(F)
-    safe = np.where(finite[:, None], pos, 0).astype(F)
+    safe = np.where(finite[:, None], b.pos, 0).astype(F)
     kw = dict(num_rows=p.map_rows, num_cols=p.map_cols, row_spacing=p.row_spacing, col_spacing=p.col_spacing)
-    terms = np.stack([np.where(VM.get_traversability(trav, safe[:, :2], **kw), F(1), F(-1)), v_b[:, 0]]).astype(F)
-    terms = np.where(finite[None], terms, F(0)).astype(F)
-    step_dt = F(p.sim_dt) * F(p.decimation)
-    reward = np.zeros(n, F)
-    for i in range(2):
-        w = F(p.weight[i])
-        if w == 0:
-            continue
-        c = terms[i] * w * step_dt
-        reward += c
-        if p.log_episode_sums:
-            state[EPSUM0 + i] += c
-    ids = np.nonzero(terminated | truncated)[0]
-    if metrics is not None and len(ids):
-        metrics[M_EPSUM0:M_EPSUM0 + 8] += state[EPSUM0:EPSUM0 + 8, ids].astype(np.float64).sum(1)
-        metrics[M_RESETS] += len(ids)
-        metrics[M_TIMEOUTS] += truncated.sum()
-        metrics[M_TERM0] += (oom & finite).sum()
-        metrics[M_NONFINITE] += (~finite).sum()
-        metrics[M_EPLEN] += episode_len[ids].sum()
-    if (~finite).any():
-        bad = np.nonzero(~finite)[0]
-        state[:19, bad] = 0
-        state[QW, bad] = 1
+    terms = np.stack([np.where(VM.get_traversability(trav, safe[:, :2], **kw), F(1), F(-1)), b.v_b[:, 0]]).astype(F)
+    terms, reward = ES.book_rewards(p, state, terms, finite)
+    # M_TERM0: cars that left the map, the non-finite ones not among them
+    ids = ES.end_episodes(state, episode_len, metrics, terminated | truncated, truncated, finite, [(oom & finite).sum()])
     reset_envs(p, state, episode_len, cells, ids, seed, step_count, env_offset, hf)
     obs = observe(p, state, trav) if hf is None else observe_depth(p, state[:, :n], hf, max_depth)
-    return obs, reward.astype(F), terminated, truncated, dict(terms=terms, finite=finite)
+    return obs, reward, terminated, truncated, dict(terms=terms, finite=finite)
 
 
 def init_state(p, n, seed=0, stride=None, wheel_mu=(0.5, 0.5), mass=3.0):

@@ -52,6 +52,17 @@ def test_struct_layout_matches_header(tmp_path):
     assert got == want
 
 
+def test_oracle_layout_equals_the_abi():
+    """every row and metric slot the oracle indexes by (oracle/layout.py) is the product's (_abi, held to the header above)"""
+    from oracle import layout as L
+    other = {"WHEEL": A.S_WHEEL_BL, "S_COUNT": A.S_COUNT, "DRIFT_ROWS": A.S_EPSUM0 + A.WL_MAX_REW_TERMS}
+    names = [k for k in vars(L) if k.isupper()]
+    assert len(names) == 30 and {"PX", "EPSUM0", "CMD_BX", "CMD_TIMER", "S_COUNT", "M_EPLEN", "M_COUNT"} <= set(names)
+    for k in names:
+        want = other[k] if k in other else getattr(A, k if k.startswith("M_") else "S_" + k)
+        assert getattr(L, k) == want, k
+
+
 def _cmp(prod, orc, path=""):
     for k, v in prod.items():
         o = getattr(orc, k)
