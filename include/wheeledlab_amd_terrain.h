@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define WL_TERRAIN_VERSION 1
+#define WL_TERRAIN_VERSION 2
 #define WL_TERRAIN_TILE 16               /* the raster pass fills 16 x 16-point tiles of the lattice, one workgroup each   */
 #define WL_TERRAIN_MAX_TILES_PER_FACE 64 /* a face whose lattice rectangle spans more tiles goes to the big list every tile filters */
 #define WL_TERRAIN_MAX_SIDE (1 << 23)    /* nx and ny: 2 .. WL_TERRAIN_MAX_SIDE - 1, nx * ny <= 2^31 - 1              */
@@ -47,6 +47,73 @@ int64_t wl_mesh_raster_scratch_bytes(int32_t n_faces, int32_t nx, int32_t ny);
  *   status_out   int32 [WL_TERRAIN_STATUS_WORDS], written by the launch (read it after the stream has run it) */
 int wl_mesh_raster(const WlMeshRasterParams* p, const float* vertices, int32_t n_vertices, const int32_t* faces, int32_t n_faces,
                    void* scratch, int64_t scratch_bytes, float* heights_out, int32_t* status_out, void* stream);
+
+/* ---- procedural terrains: a grid of sub-terrains generated straight into 16-bit height codes (wl_terrain_gen.hip) -------------------
+ *
+ * The lattice is rows x cols tiles of tile_nx x tile_ny points inside a frame of `border` points: nx = rows * tile_nx + 2 * border,
+ * ny = cols * tile_ny + 2 * border (rows advance along x: IsaacLab's difficulty axis; columns along y: its terrain types).  Point
+ * (i, j) with (i - border, j - border) inside the grid belongs to tile t = r * cols + c, r = (i - border) / tile_nx, c = (j - border) /
+ * tile_ny, at local (u, v) = (i - border - r * tile_nx, j - border - c * tile_ny); every other point is border and gets base_code.
+ * codes_out[j][i] = clamp(base_code + off, -32767, 32767), `off` the tile's height in CODES at (u, v), by type (d = min(u, tile_nx -
+ * 1 - u, v, tile_ny - 1 - v, d_plat), d_plat = max((min(tile_nx, tile_ny) - platform) / 2, 0): the ring distance from the tile's edge
+ * up to the platform; sgn = -1 with WL_TF_INVERTED, else +1):
+ *   WL_TT_RANDOM_UNIFORM    L(a, b) = code_lo + step_codes * (W(a, b) mod n_levels), W = word 0 of Philox(t, a, b, WL_TS_UNIFORM);
+ *                           step_cells == 1: off = L(u, v); else with a = u / step_cells, fu = (float)(u mod step_cells) /
+ *                           (float)step_cells (b, fv alike from v), bilinear in fp32: p = fma(fu, L(a+1, b) - L(a, b), L(a, b)),
+ *                           q = the same on row b + 1, off = rint(fma(fv, q - p, p))
+ *   WL_TT_PYRAMID_SLOPED    off = sgn * rint(slope * (float)d)                                  (slope: codes per cell, fp32)
+ *   WL_TT_PYRAMID_STAIRS    off = sgn * step_codes * (d / step_cells)
+ *   WL_TT_DISCRETE_OBSTACLES  rectangles k = 0 .. n_obstacles - 1 from X = Philox(t, k, 0, WL_TS_OBSTACLES): sides w = size_lo +
+ *                           (X[0] & 0xffff) mod (size_hi - size_lo + 1), l alike from X[0] >> 16; corner pu = X[1] mod (tile_nx - w + 1),
+ *                           pv = X[2] mod (tile_ny - l + 1); height code_lo + step_codes * (X[3] mod n_levels).  off = the height of
+ *                           the LAST rectangle containing (u, v), 0 if none -- and 0 on the platform, the centred square of
+ *                           `platform` points: (tile_nx - platform) / 2 <= u < (tile_nx - platform) / 2 + platform, v alike
+ *   WL_TT_WAVE              off = rint(amplitude * (sinpi(xu) + cospi(xv))), xu = (float)(2 * ((num_waves * u) mod tile_nx)) /
+ *                           (float)tile_nx, xv alike: num_waves whole periods across the tile   (amplitude: codes, fp32)
+ * Philox(c0, c1, c2, c3) is the library's Philox4x32 (7 rounds) with key (seed low word, seed high word).  Every point is a
+ * function of (i, j) and the arguments alone: the output is the same byte for byte from run to run. */
+enum { WL_TT_RANDOM_UNIFORM = 0, WL_TT_PYRAMID_SLOPED = 1, WL_TT_PYRAMID_STAIRS = 2, WL_TT_DISCRETE_OBSTACLES = 3, WL_TT_WAVE = 4,
+       WL_TT_COUNT = 5 };
+#define WL_TF_INVERTED 1                 /* WlTerrainTile.flags: the pyramid descends (sloped, stairs)                      */
+#define WL_TS_UNIFORM 11                 /* Philox stream ids (counter word 3)                                              */
+#define WL_TS_OBSTACLES 12
+#define WL_TERRAIN_MAX_OBSTACLES 64
+#define WL_TERRAIN_MAX_OFFSET 32767      /* |code_lo|, |step_codes| * n_levels, |slope| * side, |amplitude| stay below this  */
+
+typedef struct WlTerrainTile {
+    int32_t type, flags;
+    int32_t platform;      /* points: side of the flat square in the middle (sloped, stairs, obstacles); 0 .. min(tile_nx, tile_ny) */
+    int32_t step_cells;    /* stairs: step width; uniform: spacing of the coarse grid (1 = a draw per point); >= 1                */
+    int32_t step_codes;    /* stairs: step height; uniform / obstacles: spacing of the height levels                              */
+    int32_t code_lo;       /* uniform / obstacles: the lowest level                                                               */
+    int32_t n_levels;      /* uniform / obstacles: number of levels (>= 1)                                                        */
+    int32_t n_obstacles;   /* obstacles: 0 .. WL_TERRAIN_MAX_OBSTACLES                                                            */
+    int32_t size_lo, size_hi; /* obstacles: rectangle sides, points: 1 <= size_lo <= size_hi <= min(tile_nx, tile_ny)              */
+    int32_t num_waves;     /* wave: periods across the tile (>= 0)                                                                */
+    float slope;           /* sloped: codes per cell (finite)                                                                     */
+    float amplitude;       /* wave: codes (finite)                                                                                */
+    float difficulty;      /* what the host resolved the descriptor from, in [0, 1]: carried for the caller, never read by the kernel */
+    int32_t pad[2];
+} WlTerrainTile;           /* 64 bytes */
+
+typedef struct WlTerrainGenParams {
+    int32_t nx, ny;            /* lattice points: nx = rows * tile_nx + 2 * border, ny = cols * tile_ny + 2 * border              */
+    int32_t tile_nx, tile_ny;  /* points per tile (>= 2)                                                                          */
+    int32_t border;            /* points of base_code around the grid (>= 0)                                                      */
+    int32_t rows, cols;        /* tiles along x and along y (>= 1)                                                                */
+    int32_t base_code;         /* the code of flat ground (|base_code| <= 32767)                                                  */
+    uint64_t seed;
+} WlTerrainGenParams;
+
+/* Validate the arguments as wl_terrain_generate does, without a launch and without reading device memory: `tiles_host` is a HOST
+ * copy of the rows * cols descriptors (NULL: the descriptors are not checked).  WL_OK or WL_EINVAL. */
+int wl_terrain_gen_check(const WlTerrainGenParams* p, const WlTerrainTile* tiles_host);
+
+/* Generate the codes: `tiles` WlTerrainTile [rows * cols] and `codes_out` int16 [ny][nx], device pointers (4- and 2-byte aligned:
+ * WL_EALIGN otherwise).  The parameters are validated before any launch (WL_EINVAL); the descriptors live in device memory, so the
+ * caller validates them with wl_terrain_gen_check -- the kernel itself clamps what it reads from them (loop counts, divisors), so
+ * that no descriptor can send it out of bounds.  Allocates nothing, keeps no state. */
+int wl_terrain_generate(const WlTerrainGenParams* p, const WlTerrainTile* tiles, int16_t* codes_out, void* stream);
 
 /* WL_TERRAIN_VERSION of the library */
 int wl_terrain_version(void);

@@ -11,7 +11,8 @@ F1TENTH_DRIFT_CONFIG); the remaining arguments are Hydra-style `key=value` overr
 (the task's env cfg) and `agent` (its rsl_rl cfg).  For the drift tasks the rollout of every iteration is one fused launch
 (actor MLP on the matrix pipe + env.step, csrc/wl_policy.hip) and the PPO update runs in csrc/wl_ppo.hip;
 `--stepwise` forces the generic one-launch-per-env.step() collector (the only one for the elevation / visual tasks,
-whose observations are 689 / 3208 wide)."""
+whose observations are 689 / 3208 wide).  `train.terrain_resample_interval=K` redraws a procedural terrain (the elevation and
+visual-depth tasks with `scene.terrain.terrain_type = "generator"`) every K iterations."""
 import argparse
 import json
 import os
@@ -39,6 +40,26 @@ def checkpoint_path(logs_dir: str, load_run: str, load_run_checkpoint: int = 0) 
     if not files:
         raise FileNotFoundError(f"no checkpoint matching '{pat.pattern}' in {models}")
     return os.path.join(models, max(files)[1])
+
+
+def terrain_resampler(env, interval: int):
+    """`train.terrain_resample_interval=K`: the runner's before_iteration hook that draws a procedural terrain again every K
+    iterations (seed = the config's + the iteration) in place on the device and resets every env -- the usual guard against a
+    policy that memorises one field.  None for K = 0."""
+    if int(interval or 0) <= 0:
+        return None
+    hf = getattr(env._batch, "hf", None)
+    if hf is None or hf.generator is None:
+        raise ValueError('train.terrain_resample_interval needs env.scene.terrain.terrain_type = "generator"')
+    base_seed, done = int(hf.generator.seed), [0]
+
+    def before_iteration(it: int) -> bool:
+        done[0] += 1                                         # iterations finished since learn() began
+        if done[0] % int(interval):
+            return False
+        env.regenerate_terrain(base_seed + it)
+        return True
+    return before_iteration
 
 
 def main():
@@ -107,7 +128,8 @@ def main():
         runner.load(resume_path)
     env.seed(agent_cfg.seed)
     env.unwrapped.common_step_counter = train_cfg.set_env_step       # for continuing curriculums (train_rl.py:113)
-    hist = runner.learn(train_cfg.num_iterations, verbose=not args.quiet)
+    hist = runner.learn(train_cfg.num_iterations, verbose=not args.quiet,
+                        before_iteration=terrain_resampler(env.unwrapped, train_cfg.terrain_resample_interval))
     if log_dir:
         with open(os.path.join(log_dir, "history.json"), "w") as f:
             json.dump(hist, f)

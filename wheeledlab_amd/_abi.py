@@ -274,7 +274,7 @@ VIEWER_SIGNATURES = {
 }
 
 # include/wheeledlab_amd_terrain.h: mesh terrains -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)
-WL_TERRAIN_VERSION = 1
+WL_TERRAIN_VERSION = 2
 TERRAIN_TILE = 16
 TERRAIN_MAX_TILES_PER_FACE = 64
 TERRAIN_MAX_SIDE = 1 << 23
@@ -285,11 +285,33 @@ class WlMeshRasterParams(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("fill_z", C.c_float)]
 
 
+# procedural terrains (the same header): sub-terrain types, flags, Philox stream ids, limits
+TT_RANDOM_UNIFORM, TT_PYRAMID_SLOPED, TT_PYRAMID_STAIRS, TT_DISCRETE_OBSTACLES, TT_WAVE, TT_COUNT = 0, 1, 2, 3, 4, 5
+TF_INVERTED = 1
+TS_UNIFORM, TS_OBSTACLES = 11, 12
+TERRAIN_MAX_OBSTACLES = 64
+TERRAIN_MAX_OFFSET = 32767
+
+
+class WlTerrainTile(C.Structure):
+    _fields_ = [("type", C.c_int32), ("flags", C.c_int32), ("platform", C.c_int32), ("step_cells", C.c_int32), ("step_codes", C.c_int32),
+                ("code_lo", C.c_int32), ("n_levels", C.c_int32), ("n_obstacles", C.c_int32), ("size_lo", C.c_int32), ("size_hi", C.c_int32),
+                ("num_waves", C.c_int32), ("slope", C.c_float), ("amplitude", C.c_float), ("difficulty", C.c_float),
+                ("pad", C.c_int32 * 2)]
+
+
+class WlTerrainGenParams(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("tile_nx", C.c_int32), ("tile_ny", C.c_int32), ("border", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("base_code", C.c_int32), ("seed", C.c_uint64)]
+
+
 # every symbol include/wheeledlab_amd_terrain.h declares
 TERRAIN_SIGNATURES = {
     "wl_terrain_version": (C.c_int, []),
     "wl_mesh_raster_scratch_bytes": (C.c_int64, [_i32, _i32, _i32]),
     "wl_mesh_raster": (C.c_int, [_P(WlMeshRasterParams), _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "wl_terrain_gen_check": (C.c_int, [_P(WlTerrainGenParams), _vp]),
+    "wl_terrain_generate": (C.c_int, [_P(WlTerrainGenParams), _vp, _vp, _vp]),
 }
 
 # include/wheeledlab_amd_lidar.h: lidar range scans -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)

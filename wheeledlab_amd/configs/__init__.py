@@ -76,6 +76,7 @@ class RLTrainConfig(TrainConfig):
     rl_algo_lib: str = MISSING
     rl_algo_class: str = MISSING
     set_env_step: int = 0
+    terrain_resample_interval: int = 0     # iterations between redraws of a procedural terrain (env.regenerate_terrain); 0: never
 
 
 @configclass

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 
 import torch
 
@@ -68,7 +69,8 @@ class DeviceHeightField:
     quantize_heights' rule, z_scale 2^-13 m unless the range needs more) or `(codes int16, x0, y0, cell, z_scale)`, arrays or
     tensors; or another DeviceHeightField on the same device (shared).  `.heights`: the decoded fp32 grid -- exactly the values
     every kernel sees (what tests hand to the oracle).  `outside_z`: the height of the plane beyond the grid (what the contact samplers
-    and the depth walk meet there); None keeps a shared field's own, else 0."""
+    and the depth walk meet there); None keeps a shared field's own, else 0.  A field made by generate_heightfield remembers its
+    TerrainGeneratorCfg (`generator`) and can be drawn again in place: regenerate()."""
 
     def __init__(self, heightfield, device, outside_z: float | None = None):
         from .terrain import default_z_scale
@@ -79,6 +81,7 @@ class DeviceHeightField:
                 raise ValueError(f"a DeviceHeightField lives on {src.device}; it cannot be shared with {self.device}")
             self.codes, self.z_scale, self.heights, self.pairs = src.codes, src.z_scale, src.heights, src.pairs
             self.x0, self.y0, self.cell = src.x0, src.y0, src.cell
+            self._shared = src._shared
             outside_z = src.outside_z if outside_z is None else outside_z
         else:
             h, x0, y0, cell, *rest = heightfield
@@ -104,6 +107,9 @@ class DeviceHeightField:
             self.heights = self.codes.to(torch.float32) * torch.tensor(self.z_scale, dtype=torch.float32, device=self.device)
             self.x0, self.y0, self.cell = float(x0), float(y0), float(cell)
             self.pairs = None
+            # what every object sharing these buffers agrees on: the generator's config (None: not a generated field) and the
+            # depth cameras whose pyramids are snapshots of the codes (weak: a camera lives as long as its batch or cache keeps it)
+            self._shared = {"generator": None, "cameras": weakref.WeakSet()}
         self.outside_z = float(0.0 if outside_z is None else outside_z)
         ny, nx = self.codes.shape
         self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, None)
@@ -111,15 +117,94 @@ class DeviceHeightField:
             # the row-pair table the height scan gathers from (WlHeightField.pair, ABI 23): built on the device by the library
             if self.device.type == "cuda":
                 self.pairs = torch.empty((ny, nx), dtype=torch.int32, device=self.device)
-                A.check(A.load().wl_heightfield_pairs(C.byref(self.struct), self.pairs.data_ptr(),
-                                                      C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "wl_heightfield_pairs")
+                self._build_pairs()
             else:
                 self.pairs = pair_table(self.codes)
         self.struct.pair = self.pairs.data_ptr()
 
+    def _build_pairs(self):
+        A.check(A.load().wl_heightfield_pairs(C.byref(self.struct), self.pairs.data_ptr(),
+                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "wl_heightfield_pairs")
+
     def as_tuple(self):
         """(decoded heights, x0, y0, cell): the form the oracle's functions take"""
         return self.heights, self.x0, self.y0, self.cell
+
+    @property
+    def generator(self):
+        """the TerrainGeneratorCfg the codes were last generated from (None: not a generated field)"""
+        return self._shared["generator"]
+
+    def regenerate(self, cfg_or_seed=None):
+        """Draw the field again IN PLACE from a TerrainGeneratorCfg, or from the current one under another seed (an int; None: the
+        same seed): new codes into the same device buffers (wl_terrain_generate), the pair table rebuilt, `heights` refreshed and
+        the pyramid of every depth camera on this field rebuilt -- every WlHeightField a batch holds stays valid, and nothing
+        that reads the field afterwards sees the old one.  The new config must give the same lattice (points, placement, vertical
+        scale).  Cars stand where they stood: reset them (env.regenerate_terrain does)."""
+        from .envs import terrain_gen_cfg as G
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("regenerate needs a field on a HIP device (device='cuda:N'); there is no CPU path")
+        cfg = self.generator
+        if isinstance(cfg_or_seed, int) and not isinstance(cfg_or_seed, bool):
+            if cfg is None:
+                raise ValueError("regenerate(seed) needs a generated field (core.generate_heightfield); pass a TerrainGeneratorCfg")
+            cfg = cfg.replace(seed=int(cfg_or_seed))
+        elif cfg_or_seed is not None:
+            cfg = cfg_or_seed
+        if cfg is None:
+            raise ValueError("regenerate() of a field that was not generated needs a TerrainGeneratorCfg")
+        geo = G.lattice(cfg)
+        ny, nx = self.codes.shape
+        if (geo["nx"], geo["ny"]) != (nx, ny) or (geo["x0"], geo["y0"], geo["cell"], geo["z_scale"]) != (self.x0, self.y0, self.cell, self.z_scale):
+            raise ValueError(f"regenerate: the config gives a lattice of {geo['nx']} x {geo['ny']} points at ({geo['x0']:g}, {geo['y0']:g}), "
+                             f"cell {geo['cell']:g} m, z_scale {geo['z_scale']:g} m; the field is {nx} x {ny} at ({self.x0:g}, {self.y0:g}), "
+                             f"cell {self.cell:g} m, z_scale {self.z_scale:g} m -- build a new field instead")
+        _launch_terrain_generator(cfg, self.codes)
+        self._build_pairs()
+        torch.mul(self.codes.to(torch.float32), torch.tensor(self.z_scale, dtype=torch.float32, device=self.device), out=self.heights)
+        self._shared["generator"] = cfg
+        # _cached_depth_camera keys its snapshots on the codes tensor's version counter, which a kernel write through data_ptr()
+        # does not touch: bump it by hand, so that a snapshot nobody rebuilds here (a camera built from a TUPLE holding this tensor)
+        # is rebuilt on its next use.  Every camera built on this field itself (a batch's own, the cached ones) registered with it:
+        # their pyramids are rebuilt in place now, and remember the version they were built at, so that the cache keeps them.
+        torch.autograd.graph.increment_version(self.codes)
+        for cam in list(self._shared["cameras"]):
+            cam.build_pyramid()
+        return self
+
+
+def _launch_terrain_generator(cfg, codes: torch.Tensor):
+    """validate the config's descriptor table on the host (wl_terrain_gen_check), upload it and generate into `codes`"""
+    import numpy as np
+
+    from .envs import terrain_gen_cfg as G
+    lib = A.load()
+    p, table = G.gen_params(cfg), np.ascontiguousarray(G.tile_table(cfg))
+    if lib.wl_terrain_gen_check(C.byref(p), table.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("TerrainGeneratorCfg resolves to a grid or a sub-terrain outside the generator's range "
+                         "(include/wheeledlab_amd_terrain.h: sizes, level ranges within +-32767 codes, at most 64 obstacles)")
+    if codes.device.type != "cuda" or codes.dtype != torch.int16 or not codes.is_contiguous() or tuple(codes.shape) != (p.ny, p.nx):
+        raise ValueError(f"the generator writes contiguous int16 codes [{p.ny}, {p.nx}] on a HIP device")
+    tiles = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(codes.device)
+    A.check(lib.wl_terrain_generate(C.byref(p), tiles.data_ptr(), codes.data_ptr(),
+                                    C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)), "wl_terrain_generate")
+
+
+def generate_heightfield(cfg, device="cuda:0", outside_z: float | None = None) -> DeviceHeightField:
+    """A procedural terrain (envs.terrain_gen_cfg.TerrainGeneratorCfg) generated on the device: the codes are allocated there and
+    written by wl_terrain_generate, the pair table by wl_heightfield_pairs -- nothing but the tile descriptors (64 bytes each)
+    crosses the bus.  -> a DeviceHeightField that ElevBatch / VisualDepthBatch / DepthCamera take as `heightfield`, and whose
+    regenerate() draws it again in place.  `outside_z`: the plane beyond the lattice, 0 unless given (as for every other field)."""
+    from .envs import terrain_gen_cfg as G
+    dev = _canonical_device(device)
+    if dev.type != "cuda":
+        raise A.HipExtensionMissing("generate_heightfield needs a HIP device (device='cuda:N'); there is no CPU path")
+    geo = G.lattice(cfg)
+    codes = torch.empty((geo["ny"], geo["nx"]), dtype=torch.int16, device=dev)
+    _launch_terrain_generator(cfg, codes)
+    hf = DeviceHeightField((codes, geo["x0"], geo["y0"], geo["cell"], geo["z_scale"]), dev, outside_z)
+    hf._shared["generator"] = cfg
+    return hf
 
 
 def mesh_heightfield(vertices, faces, cell: float, device="cuda:0", lattice=None, fill_z: float = 0.0, stats: dict | None = None):
@@ -602,10 +687,16 @@ class DepthCamera:
         if n_f <= 0:
             raise A.WlError(f"heightfield of {nx} x {ny} points is outside the pyramid's range")
         self.pyramid = torch.empty(n_f, dtype=torch.float32, device=self.device)
-        A.check(self.lib.wl_heightfield_build_pyramid(C.byref(self._hf), self.pyramid.data_ptr(), self._stream()),
-                "wl_heightfield_build_pyramid")
+        self.build_pyramid()
+        self.hf._shared["cameras"].add(self)      # DeviceHeightField.regenerate rebuilds the pyramid with the codes
 
     _stream = _EnvBatch._stream
+
+    def build_pyramid(self):
+        """the max-pyramid of the field as it is now, into this camera's buffer"""
+        self._built_version = getattr(self.hf.codes, "_version", None)
+        A.check(self.lib.wl_heightfield_build_pyramid(C.byref(self._hf), self.pyramid.data_ptr(), self._stream()),
+                "wl_heightfield_build_pyramid")
 
     def render(self, batch, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
@@ -683,7 +774,11 @@ def _cached_depth_camera(batch, heightfield) -> DepthCamera:
     cam = cache.get(key)
     if cam is None or cam._src is not h:
         for k in [k for k in cache if k[0] == id(h)]:      # an older snapshot of the same array
-            del cache[k]
+            old = cache.pop(k)
+            # ... unless DeviceHeightField.regenerate has already rebuilt it in place at this very version: keep it, under the new key
+            if old._src is h and k[:5] + k[6:] == key[:5] + key[6:] and old._built_version == key[5] is not None:
+                cam = cache[key] = old
+    if cam is None or cam._src is not h:
         cam = DepthCamera(heightfield, batch.device, batch.p if isinstance(batch.p, A.WlVisualParams) else None)
         cam._src = h    # keeps the key's object alive: an id is only unique among live objects
         cache[key] = cam

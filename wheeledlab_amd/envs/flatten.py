@@ -390,20 +390,38 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     p.cmd_xy, p.cmd_heading = _sym(cmd.ranges.pos_x, "command x"), _sym(cmd.ranges.heading, "command heading")
     p.cmd_resample_s = float(cmd.resampling_time_range[1])
     flat.curriculum = _terms(cfg.curriculum)
-    flat.extra.update(_terrain_source(cfg.scene.terrain))
+    flat.extra.update(_terrain_source(cfg.scene.terrain, reset_range=(-p.reset_xy, p.reset_xy)))
     return flat
 
 
-def _terrain_source(t) -> dict:
-    """the terrain of a heightfield task: `heightfield` (an array), `mesh_path` (an OBJ rasterised at `mesh_cell`), or neither (the
-    synthetic field) -- never both"""
+def _terrain_source(t, reset_range=None, reset_range_y=None) -> dict:
+    """the terrain of a heightfield task: `heightfield` (an array), `mesh_path` (an OBJ rasterised at `mesh_cell`), a procedural
+    terrain (`terrain_type = "generator"` with `terrain_generator` a TerrainGeneratorCfg, generated on the device), or none of
+    them (the synthetic field) -- never two.  `reset_range` (lo, hi) in metres (x; y: `reset_range_y` or the same): where the task
+    puts cars at reset, which a generated terrain must cover."""
     hf, mesh = getattr(t, "heightfield", None), getattr(t, "mesh_path", None)
     if hf is not None and mesh is not None:
         raise ValueError("scene.terrain: set `heightfield` or `mesh_path`, not both")
     cell = float(getattr(t, "mesh_cell", 0.05))
     if mesh is not None and not (math.isfinite(cell) and cell > 0):
         raise ValueError("scene.terrain.mesh_cell must be positive and finite")
-    return dict(heightfield=hf, mesh_path=None if mesh is None else str(mesh), mesh_cell=cell)
+    gen = None
+    if getattr(t, "terrain_type", None) != "generator" and getattr(t, "terrain_generator", None) is not None:
+        raise ValueError('scene.terrain.terrain_generator is set but terrain_type is not "generator": set terrain_type = "generator" '
+                         "to drive on the generated terrain, or leave terrain_generator None")
+    if getattr(t, "terrain_type", None) == "generator":
+        gen = getattr(t, "terrain_generator", None)
+        if gen is None:
+            raise ValueError('scene.terrain.terrain_type = "generator" needs scene.terrain.terrain_generator (a TerrainGeneratorCfg)')
+        if hf is not None or mesh is not None:
+            raise ValueError('scene.terrain: terrain_type = "generator" excludes `heightfield` and `mesh_path`')
+        from .terrain_gen_cfg import TerrainGeneratorCfg, check_covers, tile_table
+        if isinstance(gen, dict):                           # a command-line override: the fields that differ from the defaults
+            gen = TerrainGeneratorCfg(**gen)
+        tile_table(gen)                                     # a config that does not resolve fails here, before any device work
+        if reset_range is not None:
+            check_covers(gen, reset_range, reset_range_y)
+    return dict(heightfield=hf, mesh_path=None if mesh is None else str(mesh), mesh_cell=cell, terrain_generator=gen)
 
 
 def flatten_visual_cfg(cfg) -> FlatTaskCfg:
@@ -465,7 +483,10 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     if depth_task:      # extension task: heightfield terrain + the depth image as observation (tasks/visual_depth)
         flat.task, flat.obs_dim = "visual_depth", A.VISDEPTH_OBS_DIM
         clip = getattr(cam.spawn, "clipping_range", None) or (0.01, 20.0)
-        flat.extra.update(_terrain_source(t), max_depth=float(clip[1]), augment=False)
+        # reset_traversable puts cars on the map's cell centres: (index - n // 2) * spacing
+        span = lambda n, s: (-(n // 2) * s, (n - 1 - n // 2) * s)
+        flat.extra.update(_terrain_source(t, span(t.num_cols, t.row_spacing), span(t.num_rows, t.col_spacing)), max_depth=float(clip[1]),
+                          augment=False)
     return flat
 
 

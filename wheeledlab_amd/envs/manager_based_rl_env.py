@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _abi as A
-from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch, mesh_heightfield
+from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch, generate_heightfield, mesh_heightfield
 from ..terrain import load_obj
 from .configclass import fields_of
 from .flatten import flatten_cfg
@@ -231,6 +231,8 @@ class ManagerBasedRLEnv:
                       metrics_slots=int(cfg.metrics_slots), startup=flat.startup)
         if flat.extra.get("mesh_path") is not None:      # a mesh terrain: rasterised once, then a heightfield like any other
             flat.extra["heightfield"] = mesh_heightfield(*load_obj(flat.extra["mesh_path"]), flat.extra["mesh_cell"], device=self.device)
+        if flat.extra.get("terrain_generator") is not None:      # a procedural terrain: generated on the device, redrawn in place
+            flat.extra["heightfield"] = generate_heightfield(flat.extra["terrain_generator"], self.device)
         if flat.task == "elevation":
             self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), **common)
         elif flat.task in ("visual", "visual_depth"):
@@ -342,6 +344,16 @@ class ManagerBasedRLEnv:
             t.zero_()
         self.obs_buf = {"policy": self._with_custom_obs(self._batch.observe())}
         return self.obs_buf, self.extras
+
+    def regenerate_terrain(self, seed=None):
+        """Draw the procedural terrain again (scene.terrain.terrain_type = "generator") under `seed` -- None: the current seed + 1
+        -- in place on the device (core.DeviceHeightField.regenerate), then reset every env: the cars would otherwise sit inside
+        or above the new ground.  -> (observations, extras) of the reset."""
+        hf = getattr(self._batch, "hf", None)
+        if hf is None or hf.generator is None:
+            raise ValueError('regenerate_terrain needs a generated terrain: scene.terrain.terrain_type = "generator"')
+        hf.regenerate(int(hf.generator.seed) + 1 if seed is None else int(seed))
+        return self.reset()
 
     def step(self, action: torch.Tensor):
         b = self._batch

@@ -415,7 +415,9 @@ class OnPolicyRunner:
         return out[3:3 + m], out[3 + m:3 + 2 * m], out[0] / (K * n), out[1] == 0.0
 
     # ---- the learning loop (modified_rsl_rl_runner.py:34-128) ----------------------------------------------
-    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False, verbose: bool = True):
+    def learn(self, num_learning_iterations: int, init_at_random_ep_len: bool = False, verbose: bool = True, before_iteration=None):
+        """`before_iteration(it) -> bool`: called before every iteration but the first; True says it reset every env (a terrain
+        redraw: scripts/train_rl.py), so the observation is read again and the running episodes' sums start over"""
         env = self.env
         if init_at_random_ep_len:
             env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
@@ -426,6 +428,10 @@ class OnPolicyRunner:
         cur_episode_length = torch.zeros(n, device=self.device)
         start_iter = self.current_learning_iteration
         for it in range(start_iter, start_iter + num_learning_iterations):
+            if before_iteration is not None and it > start_iter and before_iteration(it):
+                obs, _ = env.get_observations()
+                cur_reward_sum.zero_()
+                cur_episode_length.zero_()
             t0 = time.time()
             # a video recorder on the env (video.RecordVideo) that wants frames of this rollout: the per-step collector, whose
             # every step runs the env's frame hooks; otherwise the path is chosen as without a recorder

@@ -37,7 +37,8 @@ class VisualDepthObsCfg:
 class VisualDepthTerrainCfg(VisualTerrainImporterCfg):
     """the traversability map over a heightfield: 80 x 80 cells of 0.5 m = the 40 m square of the synthetic 800 x 800 field at
     0.05 m (wheeledlab_amd/terrain.py, SURVEY 8(d) config 3); `heightfield`: (height [ny, nx], x0, y0, cell) or None = that field;
-    `mesh_path`: a Wavefront OBJ terrain mesh rasterised at `mesh_cell` metres instead (exclusive with `heightfield`)"""
+    `mesh_path`: a Wavefront OBJ terrain mesh rasterised at `mesh_cell` metres instead (exclusive with `heightfield`);
+    `terrain_type = "generator"` with `terrain_generator` a TerrainGeneratorCfg: a procedural terrain generated on the device"""
     terrain_type = "traversability_heightfield"
     num_rows, num_cols = 80, 80
     env_num_rows, env_num_cols = 40, 40
@@ -45,6 +46,7 @@ class VisualDepthTerrainCfg(VisualTerrainImporterCfg):
     heightfield = None
     mesh_path = None
     mesh_cell = 0.05
+    terrain_generator = None
 
 
 @configclass
