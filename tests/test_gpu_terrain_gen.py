@@ -169,14 +169,14 @@ def test_env_ids_with_a_generator_step_like_the_reference_codes(task):
 
 
 def _addresses(batch):
-    """every device address a kernel reaches the field through: the buffers, what the batch's WlHeightField points at, its own pyramid"""
+    """every device address a kernel reaches the field through: the buffers, what the batch's WlHeightField points at, the field's pyramid"""
     return (batch.hf.codes.data_ptr(), batch.hf.pairs.data_ptr(), batch.hf.heights.data_ptr(), batch._hf.height, batch._hf.pair,
-            batch.camera.pyramid.data_ptr() if hasattr(batch, "camera") else None)
+            batch.hf.pyramid.data_ptr(), batch.camera.pyramid.data_ptr() if hasattr(batch, "camera") else None)
 
 
 def _sensors(batch, lidar):
     batch.observe()
-    # the pyramids that outlive a regenerate(): the visual-depth batch's own camera, else the batch's cached one (the lidar's too)
+    # the cameras that outlive a regenerate(): the visual-depth batch's own, else the batch's cached one (the lidar's too), on the field's pyramid
     depth = lidar.camera_of(batch).render(batch, 20.0) if not hasattr(batch, "camera") else batch.depth()
     return batch.obs.clone(), depth.clone(), lidar.render(batch).clone()
 

@@ -240,7 +240,7 @@ def test_device_heightfield_refuses_scales_that_cannot_hold_the_heights_and_shar
     import torch
 
     from wheeledlab_amd import terrain
-    from wheeledlab_amd.core import DeviceHeightField, _cached_depth_camera, _canonical_device
+    from wheeledlab_amd.core import DeviceHeightField, _cached_depth_camera, _canonical_device, _field_key
     h = np.linspace(0.0, 4.0, 64 * 64, dtype=np.float32).reshape(64, 64)
     with pytest.raises(ValueError, match="do not fit"):
         DeviceHeightField((h, 0.0, 0.0, 0.1, 1e-4), "cpu")
@@ -262,6 +262,64 @@ def test_device_heightfield_refuses_scales_that_cannot_hold_the_heights_and_shar
     with pytest.raises(ValueError, match="cannot be shared"):
         DeviceHeightField(a, "cpu")
     # the cache key of the scene's depth camera: the same codes under another vertical scale are another field
-    import inspect
-    src = inspect.getsource(_cached_depth_camera)
-    assert "zs)" in src and "heightfield.z_scale" in src and "heightfield[4]" in src
+    assert callable(_cached_depth_camera)
+    codes = torch.zeros(8, 8, dtype=torch.int16)
+    key = _field_key((codes, -1.0, -1.0, 0.5, 2.0 ** -13))
+    assert key != _field_key((codes, -1.0, -1.0, 0.5, 2.0 ** -11))
+    assert _field_key(DeviceHeightField((codes, -1.0, -1.0, 0.5, 2.0 ** -13), "cpu")) != _field_key(DeviceHeightField((codes, -1.0, -1.0, 0.5, 2.0 ** -11), "cpu"))
+
+
+def test_field_key_tells_fields_apart_and_spellings_of_one_field_together():
+    """_cached_depth_camera's key, without a device: a tuple is a snapshot (array object, placement, shape, vertical scale, a tensor's
+    in-place version); a DeviceHeightField is its shared buffers (refreshed in place: no version) and the view's outside plane"""
+    import torch
+
+    from wheeledlab_amd.core import DeviceHeightField, _field_key
+    h = torch.zeros(8, 8)
+    key = _field_key((h, -1.0, -1.0, 0.5))
+    assert key == _field_key((h, -1.0, -1.0, 0.5)) == _field_key([h, -1, np.float64(-1.0), 0.5])       # spellings of one field
+    assert _field_key((h, -1.0, -1.0, 0.5, 2.0 ** -13)) == _field_key((h, -1, -1, 0.5, np.float32(2.0 ** -13)))
+    others = [(h, -1.5, -1.0, 0.5), (h, -1.0, -1.5, 0.5), (h, -1.0, -1.0, 0.25), (h.clone(), -1.0, -1.0, 0.5), (h[:4], -1.0, -1.0, 0.5),
+              (h, -1.0, -1.0, 0.5, 2.0 ** -13)]
+    keys = [key] + [_field_key(o) for o in others]
+    assert len(set(keys)) == len(keys)
+    assert _field_key((h, -1.0, -1.0, 0.5, 2.0 ** -13)) != _field_key((h, -1.0, -1.0, 0.5, 2.0 ** -11))
+    assert _field_key((h.view(4, 16), -1.0, -1.0, 0.5)) != _field_key((h.view(16, 4), -1.0, -1.0, 0.5))      # shape alone
+    h.add_(1.0)
+    assert _field_key((h, -1.0, -1.0, 0.5)) != key                                                        # edited in place: another snapshot
+    a_np = np.zeros((8, 8), np.float32)
+    assert _field_key((a_np, 0.0, 0.0, 0.1)) == _field_key((a_np, 0, 0, 0.1)) != _field_key((a_np, 0.0, 0.0, 0.1, 1e-3))
+    codes = torch.zeros(8, 8, dtype=torch.int16)
+    a = DeviceHeightField((codes, -1.0, -1.0, 0.5, 2.0 ** -13), "cpu")
+    fields = [a, DeviceHeightField((codes, -1.0, -1.0, 0.5, 2.0 ** -11), "cpu"), DeviceHeightField((codes, -1.5, -1.0, 0.5, 2.0 ** -13), "cpu"),
+              DeviceHeightField((codes[:4], -1.0, -1.0, 0.5, 2.0 ** -13), "cpu"), DeviceHeightField(a, "cpu", outside_z=-5.0)]
+    assert len({_field_key(f) for f in fields}) == len(fields)
+    assert _field_key(DeviceHeightField(a, torch.device("cpu"))) == _field_key(a)                        # a view of the same buffers and plane
+    before = _field_key(a)
+    a.codes.add_(1)
+    assert _field_key(a.refresh()) == before                                                              # refreshed in place: the same field
+
+
+def test_device_heightfield_owns_its_pyramid_lazily_and_refreshes_its_tables():
+    """a CPU field constructs (nothing allocates a pyramid) and refuses the pyramid; views share what the field owns; refresh() brings
+    pairs and heights in line with codes edited in place, at the same addresses"""
+    import torch
+
+    from wheeledlab_amd import _abi as A
+    from wheeledlab_amd.core import DeviceHeightField, pair_table
+    g = torch.Generator().manual_seed(3)
+    a = DeviceHeightField((torch.rand(9, 7, generator=g), 0.0, 0.0, 0.1), "cpu")
+    assert a._shared["pyramid"] is None and "cameras" not in a._shared
+    with pytest.raises(A.HipExtensionMissing):
+        a.pyramid
+    view = DeviceHeightField(a, "cpu", outside_z=-5.0)
+    assert view._shared is a._shared and view.pairs is a.pairs and view.heights is a.heights
+    assert view.outside_z == -5.0 and a.outside_z == 0.0 and view.struct.outside_z == -5.0 and a.struct.outside_z == 0.0
+    with pytest.raises(A.HipExtensionMissing):
+        view.pyramid
+    addr = (a.pairs.data_ptr(), a.heights.data_ptr(), a.struct.pair)
+    a.codes[2:5, 1:4] += 100
+    assert not torch.equal(a.pairs, pair_table(a.codes))                   # stale until refresh(): nothing detects the edit
+    assert a.refresh() is a
+    assert torch.equal(view.pairs, pair_table(a.codes)) and torch.equal(view.heights, a.codes.float() * torch.tensor(a.z_scale, dtype=torch.float32))
+    assert addr == (view.pairs.data_ptr(), view.heights.data_ptr(), view.struct.pair)

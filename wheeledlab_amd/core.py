@@ -6,7 +6,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import weakref
 
 import torch
 
@@ -69,8 +68,9 @@ class DeviceHeightField:
     quantize_heights' rule, z_scale 2^-13 m unless the range needs more) or `(codes int16, x0, y0, cell, z_scale)`, arrays or
     tensors; or another DeviceHeightField on the same device (shared).  `.heights`: the decoded fp32 grid -- exactly the values
     every kernel sees (what tests hand to the oracle).  `outside_z`: the height of the plane beyond the grid (what the contact samplers
-    and the depth walk meet there); None keeps a shared field's own, else 0.  A field made by generate_heightfield remembers its
-    TerrainGeneratorCfg (`generator`) and can be drawn again in place: regenerate()."""
+    and the depth walk meet there); None keeps a shared field's own, else 0.  The field owns every table derived from the codes,
+    one of each for all its views: `pairs`, `heights` and `pyramid`; after editing `codes` in place, refresh() them.  A field made by
+    generate_heightfield remembers its TerrainGeneratorCfg (`generator`) and can be drawn again in place: regenerate()."""
 
     def __init__(self, heightfield, device, outside_z: float | None = None):
         from .terrain import default_z_scale
@@ -104,27 +104,50 @@ class DeviceHeightField:
                     math.isfinite(self.z_scale) and self.z_scale > 0) else torch.zeros((0,), dtype=torch.int16)
             if not (math.isfinite(self.z_scale) and self.z_scale > 0) or self.codes.dim() != 2:
                 raise ValueError("heightfield: a [ny, nx] grid and a positive, finite z_scale")
-            self.heights = self.codes.to(torch.float32) * torch.tensor(self.z_scale, dtype=torch.float32, device=self.device)
             self.x0, self.y0, self.cell = float(x0), float(y0), float(cell)
-            self.pairs = None
-            # what every object sharing these buffers agrees on: the generator's config (None: not a generated field) and the
-            # depth cameras whose pyramids are snapshots of the codes (weak: a camera lives as long as its batch or cache keeps it)
-            self._shared = {"generator": None, "cameras": weakref.WeakSet()}
+            # the decoded grid and the row-pair table the height scan gathers from (WlHeightField.pair, ABI 23): filled by refresh()
+            self.heights = torch.empty(self.codes.shape, dtype=torch.float32, device=self.device)
+            self.pairs = torch.empty(self.codes.shape, dtype=torch.int32, device=self.device)
+            # what every view of these buffers shares: the generator's config (None: not generated), the bound pyramid (None: no ray cast yet)
+            self._shared = {"generator": None, "pyramid": None}
         self.outside_z = float(0.0 if outside_z is None else outside_z)
         ny, nx = self.codes.shape
-        self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, None)
-        if self.pairs is None:
-            # the row-pair table the height scan gathers from (WlHeightField.pair, ABI 23): built on the device by the library
-            if self.device.type == "cuda":
-                self.pairs = torch.empty((ny, nx), dtype=torch.int32, device=self.device)
-                self._build_pairs()
-            else:
-                self.pairs = pair_table(self.codes)
-        self.struct.pair = self.pairs.data_ptr()
+        self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, self.pairs.data_ptr())
+        if not isinstance(heightfield, DeviceHeightField):
+            self.refresh()
 
-    def _build_pairs(self):
-        A.check(A.load().wl_heightfield_pairs(C.byref(self.struct), self.pairs.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "wl_heightfield_pairs")
+    def _build(self, fn: str, table: torch.Tensor):
+        """a derived table from the codes, on the current stream"""
+        A.check(getattr(A.load(), fn)(C.byref(self.struct), table.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), fn)
+
+    @property
+    def pyramid(self) -> torch.Tensor:
+        """the bound pyramid the depth walk, the lidar scan and the viewer descend (float32 [wl_heightfield_pyramid_floats], packed
+        words): built at the first access, ONE for all views -- the builder reads no outside_z, the walks apply their view's own"""
+        if self._shared["pyramid"] is None:
+            if self.device.type != "cuda":
+                raise A.HipExtensionMissing("the bound pyramid needs a field on a HIP device (device='cuda:N'); there is no CPU path")
+            ny, nx = self.codes.shape
+            n_f = int(A.load().wl_heightfield_pyramid_floats(nx, ny))
+            if n_f <= 0:
+                raise A.WlError(f"heightfield of {nx} x {ny} points is outside the pyramid's range")
+            # (zeros: the builder leaves the padding between the levels alone -- equal fields give equal buffers, word for word)
+            pyr = torch.zeros(n_f, dtype=torch.float32, device=self.device)
+            self._build("wl_heightfield_build_pyramid", pyr)
+            self._shared["pyramid"] = pyr
+        return self._shared["pyramid"]
+
+    def refresh(self):
+        """Bring every derived table in line with `codes` as they are now, in place (no address moves): `pairs`, `heights` and, once
+        built, the pyramid.  Run it after editing `codes` in place: nothing detects such an edit, and the kernels read the tables."""
+        if self.device.type == "cuda":
+            self._build("wl_heightfield_pairs", self.pairs)
+        else:
+            self.pairs.copy_(pair_table(self.codes))
+        torch.mul(self.codes.to(torch.float32), torch.tensor(self.z_scale, dtype=torch.float32, device=self.device), out=self.heights)
+        if self._shared["pyramid"] is not None:
+            self._build("wl_heightfield_build_pyramid", self._shared["pyramid"])
+        return self
 
     def as_tuple(self):
         """(decoded heights, x0, y0, cell): the form the oracle's functions take"""
@@ -137,10 +160,9 @@ class DeviceHeightField:
 
     def regenerate(self, cfg_or_seed=None):
         """Draw the field again IN PLACE from a TerrainGeneratorCfg, or from the current one under another seed (an int; None: the
-        same seed): new codes into the same device buffers (wl_terrain_generate), the pair table rebuilt, `heights` refreshed and
-        the pyramid of every depth camera on this field rebuilt -- every WlHeightField a batch holds stays valid, and nothing
-        that reads the field afterwards sees the old one.  The new config must give the same lattice (points, placement, vertical
-        scale).  Cars stand where they stood: reset them (env.regenerate_terrain does)."""
+        same seed): new codes into the same device buffers (wl_terrain_generate), then refresh() -- every WlHeightField and pyramid
+        pointer a batch holds stays valid, and nothing that reads the field afterwards sees the old one.  The new config must give
+        the same lattice (points, placement, vertical scale).  Cars stand where they stood: reset them (env.regenerate_terrain does)."""
         from .envs import terrain_gen_cfg as G
         if self.device.type != "cuda":
             raise A.HipExtensionMissing("regenerate needs a field on a HIP device (device='cuda:N'); there is no CPU path")
@@ -160,17 +182,11 @@ class DeviceHeightField:
                              f"cell {geo['cell']:g} m, z_scale {geo['z_scale']:g} m; the field is {nx} x {ny} at ({self.x0:g}, {self.y0:g}), "
                              f"cell {self.cell:g} m, z_scale {self.z_scale:g} m -- build a new field instead")
         _launch_terrain_generator(cfg, self.codes)
-        self._build_pairs()
-        torch.mul(self.codes.to(torch.float32), torch.tensor(self.z_scale, dtype=torch.float32, device=self.device), out=self.heights)
         self._shared["generator"] = cfg
-        # _cached_depth_camera keys its snapshots on the codes tensor's version counter, which a kernel write through data_ptr()
-        # does not touch: bump it by hand, so that a snapshot nobody rebuilds here (a camera built from a TUPLE holding this tensor)
-        # is rebuilt on its next use.  Every camera built on this field itself (a batch's own, the cached ones) registered with it:
-        # their pyramids are rebuilt in place now, and remember the version they were built at, so that the cache keeps them.
+        # _field_key tells snapshots of this tensor (fields from a TUPLE holding it, which nobody refreshes) apart by its version
+        # counter, which a kernel write through data_ptr() does not touch: bump it by hand
         torch.autograd.graph.increment_version(self.codes)
-        for cam in list(self._shared["cameras"]):
-            cam.build_pyramid()
-        return self
+        return self.refresh()
 
 
 def _launch_terrain_generator(cfg, codes: torch.Tensor):
@@ -628,12 +644,12 @@ class VisualDepthBatch(VisualBatch):
         self.height = self.hf.heights
         self.max_depth = float(max_depth)
         self.camera = DepthCamera(self.hf, self.device, self.p)
-        self._hf = self.camera._hf
+        self._hf, self._pyr = self.camera._hf, self.camera._pyr
         self._args = (C.byref(self._bufs), C.byref(self._map), C.byref(self._hf))
 
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         out = self.obs if out is None else out
-        A.check(self.lib.wl_visual_depth_observe(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), self.camera.pyramid.data_ptr(),
+        A.check(self.lib.wl_visual_depth_observe(C.byref(self.p), C.byref(self._bufs), C.byref(self._hf), self._pyr,
                                                  self.max_depth, out.data_ptr(), self._stream()), "wl_visual_depth_observe")
         return out
 
@@ -645,7 +661,7 @@ class VisualDepthBatch(VisualBatch):
         return self.obs, self.reward, self.terminated, self.truncated
 
     def _step_into(self, actions_ptr, out):
-        A.check(self.lib.wl_visual_depth_step(C.byref(self.p), *self._args, self.camera.pyramid.data_ptr(), self.max_depth, actions_ptr,
+        A.check(self.lib.wl_visual_depth_step(C.byref(self.p), *self._args, self._pyr, self.max_depth, actions_ptr,
                                               C.byref(out), self.seed, self.step_count, self._stream()), "wl_visual_depth_step")
         self.step_count += 1
 
@@ -667,9 +683,10 @@ class VisualDepthBatch(VisualBatch):
 
 
 class DepthCamera:
-    """The visual task's pinhole camera rendering distance_to_image_plane against a heightfield (wl_visual_depth): owns the
-    device copy of the field and its max-pyramid (built once), renders the poses of ANY batch (rows WL_S_PX.. / WL_S_QW.. of
-    its state matrix).  Reference hook: mdp_sensors/observations.py:89-95; camera visual/mushr_visual_env_cfg.py:230-246."""
+    """The visual task's pinhole camera rendering distance_to_image_plane against a heightfield (wl_visual_depth): its parameters
+    and a view of the field (`hf`: its own outside plane, the field's buffers and its one bound pyramid), renders the poses of ANY
+    batch (rows WL_S_PX.. / WL_S_QW.. of its state matrix).  Reference hook: mdp_sensors/observations.py:89-95; camera
+    visual/mushr_visual_env_cfg.py:230-246."""
 
     IMG_H, IMG_W = 60, 80
 
@@ -682,27 +699,20 @@ class DepthCamera:
         self.p = params if params is not None else visual_params()
         self.hf = DeviceHeightField(heightfield, self.device, outside_z)     # a tuple (quantised here) or a batch's own `.hf` (shared)
         self.height, self._hf = self.hf.heights, self.hf.struct
-        ny, nx = self.hf.codes.shape
-        n_f = int(self.lib.wl_heightfield_pyramid_floats(nx, ny))
-        if n_f <= 0:
-            raise A.WlError(f"heightfield of {nx} x {ny} points is outside the pyramid's range")
-        self.pyramid = torch.empty(n_f, dtype=torch.float32, device=self.device)
-        self.build_pyramid()
-        self.hf._shared["cameras"].add(self)      # DeviceHeightField.regenerate rebuilds the pyramid with the codes
+        self._pyr = self.hf.pyramid.data_ptr()    # resolved once: the field rebuilds its pyramid in place (refresh), never moves it
 
     _stream = _EnvBatch._stream
+    pyramid = property(lambda self: self.hf.pyramid)
 
     def build_pyramid(self):
-        """the max-pyramid of the field as it is now, into this camera's buffer"""
-        self._built_version = getattr(self.hf.codes, "_version", None)
-        A.check(self.lib.wl_heightfield_build_pyramid(C.byref(self._hf), self.pyramid.data_ptr(), self._stream()),
-                "wl_heightfield_build_pyramid")
+        """the field's derived tables (the pyramid among them) from its codes as they are now"""
+        self.hf.refresh()
 
     def render(self, batch, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
             out = torch.empty(batch.n, self.IMG_H, self.IMG_W, dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == batch.n * self.IMG_H * self.IMG_W
-        A.check(self.lib.wl_visual_depth(C.byref(self.p), C.byref(batch._bufs), C.byref(self._hf), self.pyramid.data_ptr(),
+        A.check(self.lib.wl_visual_depth(C.byref(self.p), C.byref(batch._bufs), C.byref(self._hf), self._pyr,
                                          float(max_depth), out.data_ptr(), self._stream()), "wl_visual_depth")
         return out
 
@@ -710,7 +720,7 @@ class DepthCamera:
 class LidarScanner:
     """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
     (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
-    field and pyramid come from the batch's cached DepthCamera (one pyramid per field, rebuilt when the field changes in place).
+    field and pyramid come from the batch's cached DepthCamera, i.e. from the batch's DeviceHeightField (which owns the one pyramid).
     render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
     the terrain (what a miss reads in the scene is LidarData's business)."""
 
@@ -756,30 +766,29 @@ class LidarScanner:
         if out is None:
             out = torch.empty(batch.n, self.n_beams, dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch.n, self.n_beams)
-        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam.pyramid.data_ptr(),
+        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr,
                                        self.beam_dirs.data_ptr(), out.data_ptr(), self._stream()), "wl_lidar_scan")
         return out
 
 
-def _cached_depth_camera(batch, heightfield) -> DepthCamera:
-    """one DepthCamera per (batch, heightfield): the pyramid is a SNAPSHOT of the field, built on first use and rebuilt when the
-    array object, its placement (x0, y0, cell), its shape or -- for tensors -- its in-place version counter changes"""
-    cache = batch.__dict__.setdefault("_depth_cameras", {})
+def _field_key(heightfield) -> tuple:
+    """What tells one `heightfield` argument from another (pure: needs no device).  A DeviceHeightField: its shared buffers' identity and
+    the view's outside plane -- it refreshes its tables in place, so no version.  A tuple is a SNAPSHOT: the array object, placement,
+    shape, vertical scale (the same codes under another one are another field) and -- for tensors -- the in-place version counter."""
     if isinstance(heightfield, DeviceHeightField):
-        h, x0, y0, cell, zs = heightfield.codes, heightfield.x0, heightfield.y0, heightfield.cell, heightfield.z_scale
-    else:
-        h, x0, y0, cell = heightfield[:4]
-        zs = float(heightfield[4]) if len(heightfield) > 4 else None       # the same codes under another vertical scale: another field
-    key = (id(h), float(x0), float(y0), float(cell), tuple(h.shape), getattr(h, "_version", None), zs)
-    cam = cache.get(key)
-    if cam is None or cam._src is not h:
-        for k in [k for k in cache if k[0] == id(h)]:      # an older snapshot of the same array
-            old = cache.pop(k)
-            # ... unless DeviceHeightField.regenerate has already rebuilt it in place at this very version: keep it, under the new key
-            if old._src is h and k[:5] + k[6:] == key[:5] + key[6:] and old._built_version == key[5] is not None:
-                cam = cache[key] = old
-    if cam is None or cam._src is not h:
-        cam = DepthCamera(heightfield, batch.device, batch.p if isinstance(batch.p, A.WlVisualParams) else None)
-        cam._src = h    # keeps the key's object alive: an id is only unique among live objects
-        cache[key] = cam
-    return cam
+        return id(heightfield._shared), heightfield.outside_z
+    h, x0, y0, cell = heightfield[:4]
+    return (id(h), float(x0), float(y0), float(cell), tuple(h.shape), getattr(h, "_version", None),
+            float(heightfield[4]) if len(heightfield) > 4 else None)
+
+
+def _cached_depth_camera(batch, heightfield) -> DepthCamera:
+    """one DepthCamera per batch and array (or shared buffers): built on first use, and again when _field_key tells the argument
+    from the last one -- a newer snapshot of an array replaces the older (a tuple becomes a DeviceHeightField of its own)"""
+    cache = batch.__dict__.setdefault("_depth_cameras", {})
+    key = _field_key(heightfield)
+    hit = cache.get(key[0])
+    if hit is None or hit[0] != key:
+        # (the entry holds the argument alive: an id is only unique among live objects)
+        hit = cache[key[0]] = (key, heightfield, DepthCamera(heightfield, batch.device, batch.p if isinstance(batch.p, A.WlVisualParams) else None))
+    return hit[2]

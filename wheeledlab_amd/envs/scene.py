@@ -213,10 +213,7 @@ class CameraData:
         if self._cam is None:
             from ..core import DepthCamera
             b = self._b
-            if getattr(b, "camera", None) is not None:      # visual-depth task: the batch's own camera (its terrain, its pyramid)
-                self._cam = b.camera
-                return self._cam
-            if hasattr(b, "hf"):            # elevation task: its own heightfield (already on the device: shared, not re-quantised)
+            if hasattr(b, "hf"):            # elevation and visual-depth tasks: the batch's own field (shared: its buffers, its pyramid)
                 hf = b.hf
             else:                           # flat ground: any grid at z = 0 (beyond it the outside plane is z = 0 as well)
                 hf = (torch.zeros(3, 3, dtype=torch.float32, device=b.device), -1.0, -1.0, 1.0)

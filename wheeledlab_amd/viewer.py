@@ -94,8 +94,8 @@ def viewer_params(width, height, eye, lookat, vehicle=None, hfov_deg=DEFAULT_HFO
 
 
 class Viewer:
-    """Owns the frame's scratch and one bound pyramid per heightfield (built on first use); renders any batch of this package
-    (DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch) from a look-at camera."""
+    """Owns the frame's scratch; renders any batch of this package (DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch) from a
+    look-at camera.  A heightfield ground is the batch's DeviceHeightField and its own bound pyramid (built on first use)."""
 
     def __init__(self, device="cuda:0", resolution=(1280, 720), hfov_deg: float = DEFAULT_HFOV_DEG, far_clip: float = DEFAULT_FAR_CLIP):
         self.lib = A.load()
@@ -105,7 +105,6 @@ class Viewer:
         self.width, self.height = int(resolution[0]), int(resolution[1])
         self.hfov_deg, self.far_clip = float(hfov_deg), float(far_clip)
         self._scratch = None
-        self._pyramids = {}
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -119,16 +118,7 @@ class Viewer:
         return self._scratch, need
 
     def _pyramid(self, batch):
-        cam = getattr(batch, "camera", None)
-        if cam is not None and getattr(cam, "hf", None) is not None and cam.hf.codes is batch.hf.codes:
-            return cam._hf, cam.pyramid          # the visual-depth batch's own depth camera: its pyramid is this field's
-        from .core import DepthCamera
-        key = id(batch.hf)
-        hit = self._pyramids.get(key)
-        if hit is None or hit[0] is not batch.hf:
-            hit = (batch.hf, DepthCamera(batch.hf, self.device, outside_z=batch.hf.outside_z))
-            self._pyramids[key] = hit
-        return hit[1]._hf, hit[1].pyramid
+        return batch.hf.struct, batch.hf.pyramid
 
     def params(self, batch, eye, lookat, env_index: int = 0) -> A.WlViewerParams:
         hf = getattr(batch, "hf", None)
