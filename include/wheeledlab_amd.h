@@ -26,6 +26,8 @@ extern "C" {
 #endif
 
 #define WL_ABI_VERSION 24
+/* Counts layout changes INSIDE an ABI version (wl_revision(); the python loader checks both).  1: WlElevParams.levels. */
+#define WL_ABI_REVISION 1
 
 enum WlStatus { WL_OK = 0, WL_EINVAL = -1, WL_ELAUNCH = -2, WL_EALIGN = -3, WL_ENODEV = -4 };
 
@@ -189,6 +191,7 @@ typedef struct WlStepOut {
 } WlStepOut;
 
 int wl_version(void);
+int wl_revision(void);          /* WL_ABI_REVISION the library was built with */
 /* number of HIP devices visible, or WL_ENODEV */
 int wl_device_count(void);
 const char* wl_strerror(int code);
@@ -508,6 +511,25 @@ enum WlElevTermTerm { WL_ET_BELOW_MIN_HEIGHT = 0, WL_ET_STUCK, WL_ET_ROLLOVER, W
 #define WL_ELEV_SCAN_N 26                      /* GridPatternCfg(size 2.5, resolution 0.1) -> 26 x 26 rays (:139)   */
 #define WL_ELEV_OBS_DIM (13 + WL_ELEV_SCAN_N * WL_ELEV_SCAN_N)   /* 689 (:61-86)                                  */
 
+/* Terrain curriculum (IsaacLab TerrainImporter terrain_levels / terrain_types / terrain_origins + the terrain_levels curriculum
+ * term), decided inside the step kernels where the resets are.  Per env e: level[e] in [0, rows) (the row of tiles, difficulty)
+ * and type[e] in [0, cols) (the column, sub-terrain type); origins[rows * cols][2] holds every tile's centre (x, y) in metres,
+ * tile = row * cols + col.  When an episode ends inside a step, BEFORE the spawn is drawn: at_goal -> level + 1; else a failure
+ * (below_min_height, stuck, rollover, non-finite state) -> max(level - 1, 0); else (time-out) the level stays; a level that
+ * reaches `rows` is replaced by mulhi(word 0 of Philox(gid, step, stream 3, seed), rows), uniform in [0, rows).  The spawn is then
+ * origin + sym(u, reset_xy) (z from the terrain there), the goal origin + sym(c, cmd_xy) -- at a reset and whenever the command
+ * timer resamples -- with every Philox word where it was.  wl_elev_reset spawns at the env's current level and leaves it alone.
+ * The kernels read level[] / type[] only in those two branches and write level[] only at a reset (the env's lead lane).
+ * All zero = off.  A non-NULL `level` needs `type`, `origins`, rows >= 1, cols >= 1 (else WL_EINVAL) and 4-byte alignment of the
+ * three (else WL_EALIGN); a NULL `level` with anything else set is WL_EINVAL.  Nothing is launched on a refusal.  Values outside
+ * their ranges are clamped where they are read. */
+typedef struct WlTerrainLevels {
+    int32_t* level;           /* [n_envs], read and written                                                   */
+    const int32_t* type;      /* [n_envs]                                                                     */
+    const float* origins;     /* [rows * cols][2]                                                             */
+    int32_t rows, cols;
+} WlTerrainLevels;
+
 typedef struct WlElevParams {
     float sim_dt;             /* 0.01 (:461)                                                                  */
     int32_t decimation;       /* 10   (:462)                                                                  */
@@ -526,6 +548,7 @@ typedef struct WlElevParams {
     float cmd_xy, cmd_heading, cmd_resample_s;                           /* :425-435                           */
     float scan_size, scan_res, scan_offset, obs_clip;                    /* :74-82, :139                       */
     int32_t log_episode_sums;
+    WlTerrainLevels levels;   /* revision 1: the terrain curriculum, all zero = off (then every entry point is what it was)   */
 } WlElevParams;
 
 /*

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 
 WL_ABI_VERSION = 24
+WL_ABI_REVISION = 1     # layout changes inside the ABI version (1: WlElevParams.levels)
 WL_MAX_REW_TERMS = 8
 
 # WlStateField
@@ -79,6 +80,10 @@ class WlHeightField(C.Structure):
                 ("cell", C.c_float), ("outside_z", C.c_float), ("z_scale", C.c_float), ("pair", C.c_void_p)]
 
 
+class WlTerrainLevels(C.Structure):
+    _fields_ = [("level", C.c_void_p), ("type", C.c_void_p), ("origins", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
 class WlElevParams(C.Structure):
     _fields_ = [
         ("sim_dt", C.c_float), ("decimation", C.c_int32), ("max_episode_length", C.c_int32),
@@ -89,7 +94,7 @@ class WlElevParams(C.Structure):
         ("reset_xy", C.c_float), ("reset_yaw", C.c_float), ("reset_vel", C.c_float * 2), ("reset_z", C.c_float),
         ("spawn_clearance", C.c_float), ("cmd_xy", C.c_float), ("cmd_heading", C.c_float),
         ("cmd_resample_s", C.c_float), ("scan_size", C.c_float), ("scan_res", C.c_float), ("scan_offset", C.c_float),
-        ("obs_clip", C.c_float), ("log_episode_sums", C.c_int32),
+        ("obs_clip", C.c_float), ("log_episode_sums", C.c_int32), ("levels", WlTerrainLevels),
     ]
 
 
@@ -185,6 +190,7 @@ _vp, _u64, _i32, _i64 = C.c_void_p, C.c_uint64, C.c_int32, C.c_int64
 # every symbol include/wheeledlab_amd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "wl_version": (C.c_int, []),
+    "wl_revision": (C.c_int, []),
     "wl_device_count": (C.c_int, []),
     "wl_strerror": (C.c_char_p, [C.c_int]),
     "wl_drift_step": (C.c_int, [_P(WlDriftParams), _P(WlEnvBuffers), _vp, _vp, _P(WlStepOut), _u64, _u64, _vp]),
@@ -361,6 +367,8 @@ def load(path: str | None = None):
     v = lib.wl_version()
     if v != WL_ABI_VERSION:
         raise HipExtensionMissing(f"{path} has ABI version {v}, python expects {WL_ABI_VERSION}: rebuild")
+    if lib.wl_revision() != WL_ABI_REVISION:
+        raise HipExtensionMissing(f"{path} has ABI revision {lib.wl_revision()}, python expects {WL_ABI_REVISION}: rebuild")
     if lib.wl_viewer_version() != WL_VIEWER_VERSION:
         raise HipExtensionMissing(f"{path} has viewer version {lib.wl_viewer_version()}, python expects {WL_VIEWER_VERSION}: rebuild")
     if lib.wl_terrain_version() != WL_TERRAIN_VERSION:

@@ -513,6 +513,49 @@ class DriftBatch(_EnvBatch):
         return storage
 
 
+class TerrainLevels:
+    """The terrain curriculum's device tables (WlTerrainLevels): `level` / `type` int32 [n] -- the row and column of every env's
+    tile, LIVE: the step kernels move `level` at episode ends -- and `origins` float32 [rows * cols, 2], the tile centres.  Built
+    from the TerrainGeneratorCfg of a generated field for envs env_offset .. env_offset + n of a world of `world_envs` envs (a
+    shard holds its slice of the one big batch's assignment: envs.terrain_levels.initial_assignment), or from ready tables
+    (from_tables).  Hand it to ElevBatch(terrain_levels=...)."""
+
+    def __init__(self, cfg, n_envs: int, device="cuda:0", env_offset: int = 0, world_envs: int | None = None,
+                 max_init_terrain_level: int | None = None, seed: int = 42):
+        from .envs import terrain_levels as TL
+        level, types = TL.initial_assignment(cfg, n_envs, env_offset, world_envs, max_init_terrain_level, seed)
+        self._set(level, types, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device)
+        self.max_init_terrain_level = TL.clamp_max_init(cfg, max_init_terrain_level)
+
+    @classmethod
+    def from_tables(cls, level, types, origins, rows: int, cols: int, device="cuda:0"):
+        """level / types [n] integers in [0, rows) / [0, cols), origins [rows * cols, 2] metres"""
+        self = cls.__new__(cls)
+        self._set(level, types, origins, rows, cols, device)
+        self.max_init_terrain_level = int(rows) - 1
+        return self
+
+    def _set(self, level, types, origins, rows, cols, device):
+        self.device, self.rows, self.cols = _canonical_device(device), int(rows), int(cols)
+        self.level = torch.as_tensor(level).to(self.device, torch.int32).contiguous().clone()
+        self.type = torch.as_tensor(types).to(self.device, torch.int32).contiguous().clone()
+        self.origins = torch.as_tensor(origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
+        if self.rows < 1 or self.cols < 1 or self.origins.shape[0] != self.rows * self.cols or self.level.shape != self.type.shape or self.level.dim() != 1:
+            raise ValueError(f"terrain levels: {self.rows} x {self.cols} tiles need origins [{self.rows * self.cols}, 2] and level / type of one length")
+        if self.level.numel() and (int(self.level.min()) < 0 or int(self.level.max()) >= self.rows or int(self.type.min()) < 0
+                                   or int(self.type.max()) >= self.cols):
+            raise ValueError(f"terrain levels outside [0, {self.rows}) or types outside [0, {self.cols})")
+        self.struct = A.WlTerrainLevels(self.level.data_ptr(), self.type.data_ptr(), self.origins.data_ptr(), self.rows, self.cols)
+
+    def env_origins_xy(self) -> torch.Tensor:
+        """[n, 2]: the centre of every env's tile as the levels stand"""
+        return self.origins[self.level.long() * self.cols + self.type.long()]
+
+    def mean_level(self) -> torch.Tensor:
+        """0-dim device tensor: what the terrain_levels curriculum term reports"""
+        return self.level.float().mean()
+
+
 class ElevBatch(_EnvBatch):
     """n elevation-task envs on one GPU (same SoA state matrix; rows WL_S_CMD_* carry the goal command)."""
 
@@ -520,10 +563,11 @@ class ElevBatch(_EnvBatch):
     _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_elev_reset", "wl_elev_step", "wl_elev_rollout", "wl_elev_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params: A.WlElevParams | None = None, seed: int = 42,
-                 env_offset: int = 0, heightfield=None, metrics_slots: int = 1, startup=None):
+                 env_offset: int = 0, heightfield=None, metrics_slots: int = 1, startup=None, terrain_levels: TerrainLevels | None = None):
         from .params import elev_params
         from .terrain import synthetic_heightfield
         super().__init__(n_envs, device, params if params is not None else elev_params(), seed, env_offset, metrics_slots)
+        self.set_terrain_levels(terrain_levels)
         self.hf = DeviceHeightField(heightfield if heightfield is not None else synthetic_heightfield(), self.device)
         self.height, self._hf = self.hf.heights, self.hf.struct       # the DECODED fp32 grid (what the kernels see); the ABI struct
         self._args = (C.byref(self._bufs), C.byref(self._hf))
@@ -533,6 +577,18 @@ class ElevBatch(_EnvBatch):
             startup = StartupSpec(wheel_mu_s=(2.0, 2.0), wheel_mu_d=(1.0, 1.0), mu_buckets=5, mu_consistent=False,
                                   damping=(1000.0, 1000.0), mass_add=(0.2, 0.5))
         apply_startup_events(self.lib, self._bufs, startup, self.seed, self._stream())
+
+    def set_terrain_levels(self, levels: TerrainLevels | None):
+        """switch the terrain curriculum on (a TerrainLevels of this batch's envs, on its device) or off (None): the batch's
+        params carry the tables from here on (WlElevParams.levels; the struct is this batch's own copy when it changes)"""
+        if levels is not None and (levels.level.shape[0] != self.n or levels.device != _canonical_device(self.device)):
+            raise ValueError(f"terrain levels of {levels.level.shape[0]} envs on {levels.device} for a batch of {self.n} on {self.device}")
+        if levels is not None or self.p.levels.level:
+            q = type(self.p)()
+            C.pointer(q)[0] = self.p            # a copy: a params struct shared with other batches keeps its own tables
+            q.levels = levels.struct if levels is not None else A.WlTerrainLevels()
+            self.p = q
+        self.levels = levels
 
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """observation of the current state into self.obs (or a caller's [n, 689] buffer)"""

@@ -254,6 +254,7 @@ __global__ void philox_uniform_kernel(int n, uint64_t seed, uint64_t step, uint3
 extern "C" {
 
 int wl_version(void) { return WL_ABI_VERSION; }
+int wl_revision(void) { return WL_ABI_REVISION; }
 
 int wl_device_count(void) {
     int n = 0;

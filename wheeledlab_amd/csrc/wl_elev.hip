@@ -43,7 +43,7 @@ __device__ unsigned long long wl_timeline[2048][16];
 
 namespace {
 
-enum ElevStream : uint32_t { ES_RESET = 0, ES_CMD_RESET = 1, ES_CMD_RESAMPLE = 2 };
+enum ElevStream : uint32_t { ES_RESET = 0, ES_CMD_RESET = 1, ES_CMD_RESAMPLE = 2, ES_LEVEL = 3 /* the terrain curriculum's wrap draw */ };
 
 // cos / sin of the yaw of IsaacLab's yaw_quat(q) without the atan2 round trip
 WL_DEV void yaw_cs(Quat q, float& c, float& s) {
@@ -122,6 +122,70 @@ struct ElevReset {
     Quat q;
     float vx, vy, tgt_x, tgt_y, tgt_h;
 };
+
+// ---- terrain curriculum (WlTerrainLevels; IsaacLab TerrainImporter.update_env_origins + mdp.terrain_levels) -------------------------
+// a + b as an addition of its own: under -ffp-contract=fast `origin + (2 u - 1) a` becomes an fma at one inlining site and not at
+// the next (see yaw_cs), and every form must place a spawn on the same bits
+WL_DEV float add_unfused(float a, float b) {
+    float r;
+    {
+#pragma clang fp contract(off)
+        r = a + b;
+    }
+    return r;
+}
+struct TileOrigin {
+    float x, y;
+};
+// the centre of tile (level, type[e]); both indices clamped to the table
+WL_DEV TileOrigin tile_origin(const WlTerrainLevels& tl, int e, int level) {
+    const int row = min(max(level, 0), tl.rows - 1), col = min(max(tl.type[e], 0), tl.cols - 1);
+    const float* o = tl.origins + 2 * (row * tl.cols + col);
+    return TileOrigin{o[0], o[1]};
+}
+// the env's level as its lead lane sees it (a quad's other lanes take the lead's value: the lead is the one that writes level[])
+template <int LANES>
+WL_DEV int load_level(const WlTerrainLevels& tl, int e) {
+    int lv = tl.level[e];
+    if constexpr (LANES == 4) lv = __builtin_amdgcn_update_dpp(0, lv, 0, 0xF, 0xF, true);   // quad_perm [0, 0, 0, 0]
+    return lv;
+}
+// the level an env moves to when its episode ends: up at the goal, down (not below 0) after a failure, unchanged after a time-out;
+// past the top row: a uniform row
+WL_DEV int next_level(const WlTerrainLevels& tl, int level, bool at_goal, bool failed, uint32_t gid, uint64_t step, uint64_t seed) {
+    int lv = min(max(level, 0), tl.rows - 1);
+    if (at_goal) lv += 1;
+    else if (failed) lv = max(lv - 1, 0);
+    if (lv >= tl.rows) lv = (int)__umulhi(philox_block(gid, step, ES_LEVEL, seed).x, (uint32_t)tl.rows);
+    return lv;
+}
+
+// the part of a reset's draw that does not depend on where the env's tile is: pos.x / pos.y hold the OFFSETS from the tile's centre,
+// tgt_x / tgt_y the goal's; place_elev_reset adds the centre and stands the car on the terrain
+WL_DEV ElevReset draw_elev_reset_local(const WlElevParams& p, uint32_t gid, uint64_t step, uint64_t seed) {
+    const F4 u = philox_uniform4(gid, step, ES_RESET, seed);
+    const F4 c = philox_uniform4(gid, step, ES_CMD_RESET, seed);
+    ElevReset r;
+    r.pos = v3(sym(u.x, p.reset_xy), sym(u.y, p.reset_xy), 0.f);
+    float s, cc;
+    sincos_fast(0.5f * sym(u.z, p.reset_yaw), s, cc);
+    r.q = Quat{cc, 0.f, 0.f, s};
+    r.vx = fmaf(u.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
+    r.vy = fmaf(c.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
+    r.tgt_x = sym(c.x, p.cmd_xy);
+    r.tgt_y = sym(c.y, p.cmd_xy);
+    r.tgt_h = sym(c.z, p.cmd_heading);
+    return r;
+}
+WL_DEV void place_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, TileOrigin o) {
+    const float x = add_unfused(o.x, r.pos.x), y = add_unfused(o.y, r.pos.y);
+    float zt;
+    V3 n;
+    g.sample(x, y, zt, n);
+    r.pos = v3(x, y, fmaxf(p.reset_z, zt + p.spawn_clearance));
+    r.tgt_x = add_unfused(o.x, r.tgt_x);
+    r.tgt_y = add_unfused(o.y, r.tgt_y);
+}
 
 // isaaclab reset_root_state_uniform with the ranges of :409-419 + UniformPose2dCommand resample (:425-435)
 WL_DEV ElevReset draw_elev_reset(const WlElevParams& p, const HeightFieldGround& g, uint32_t gid, uint64_t step, uint64_t seed) {
@@ -331,13 +395,36 @@ WL_DEV ElevBook load_elev_book(const WlElevParams& p, const WlEnvBuffers& b, con
 // rows are written -- so that the launch can hand the height scan its lattice frames and let the other wavefronts start while this one
 // finishes its bookkeeping.  `reset_src` supplies a resetting env's draw (wl_implicit_task.h): drawn here by default, by the fused
 // launch's helper wavefront there.
+static_assert(sizeof(WlElevParams) % alignof(VehDerived) == 0, "VehDerived follows WlElevParams in the argument block without a gap");
+// What the step kernels take as their first argument: WlElevParams WITHOUT its trailing `levels` member, so that a launch without
+// terrain levels has the argument block -- and, with LEVELS = false, the code -- it had before the member existed.  The member
+// travels as the kernels' LAST argument and is read (scalar loads) only by the LEVELS = true instantiations, at resets.
+constexpr int kElevHeadBytes = (int)offsetof(WlElevParams, log_episode_sums) + 4;
+struct ElevHead {
+    uint32_t w[kElevHeadBytes / 4];
+};
+static_assert(offsetof(WlElevParams, levels) >= (size_t)kElevHeadBytes && alignof(ElevHead) == 4, "levels is the trailing member");
+inline ElevHead elev_head(const WlElevParams* p) {
+    ElevHead h;
+    __builtin_memcpy(&h, p, sizeof(h));
+    return h;
+}
+// the argument read as the parameter struct: every field but `levels` is there
+WL_DEV const WlElevParams& elev_args(const ElevHead& h) { return reinterpret_cast<const WlElevParams&>(h); }
+// the vector copy of the head and of the derived block behind it (kernarg_vector_copy2), as a parameter struct in registers
+WL_DEV void elev_kernarg_copy(WlElevParams& p, VehDerived& vd) {
+    ElevHead h;
+    kernarg_vector_copy2(0, h, vd);
+    __builtin_memcpy(&p, &h, sizeof(h));
+}
 struct NoPose {
     WL_DEV void operator()(const V3&, const Quat&) const {}
 };
-template <int LANES, bool PERSIST = false, class RESET = InlineReset, class POSE = NoPose>
+template <int LANES, bool LEVELS, bool PERSIST = false, class RESET = InlineReset, class POSE = NoPose>
 WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const WlEnvBuffers& b, const HeightFieldGround& ground,
                               const float2 action, VehRows<LANES>& rows, const WlStepOut& out, const uint64_t seed,
                               const uint64_t step, const Rows& S, const int e, const int wid, const bool lead, float* blk_metrics,
+                              const WlTerrainLevels& tl /* the kernel's scalar argument: read at resets only, when LEVELS */,
                               ElevBook* carry = nullptr, float* prop2 = nullptr, const RESET& reset_src = RESET(), const POSE& pose = POSE()) {
     const WlVehicleParams& vp = p.vehicle;
     const uint32_t gid = (uint32_t)(b.env_offset + e);
@@ -395,8 +482,18 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
     // block's one s_barrier: keep it that way.
     const bool reset_now = terminated || truncated;
     ElevReset rd{};
+    [[maybe_unused]] int level_now = 0;      // LEVELS and reset_now: the level the env leaves this step on
     if (reset_now) {
-        rd = reset_src(e, [&] { return draw_elev_reset(p, ground, gid, step, seed); });
+        if constexpr (LEVELS) {
+            // the curriculum first (IsaacLab _reset_idx: curriculum terms before the reset events), then the spawn on the new tile.
+            // The origin-free draw may come from the helper wavefront; the level needs this step's outcome, so it is decided here.
+            level_now = next_level(tl, load_level<LANES>(tl, e), tm.flag[WL_ET_AT_GOAL], terminated, gid, step, seed);
+            if (lead) tl.level[e] = level_now;
+            rd = reset_src(e, [&] { return draw_elev_reset_local(p, gid, step, seed); });
+            place_elev_reset(p, ground, rd, tile_origin(tl, e, level_now));
+        } else {
+            rd = reset_src(e, [&] { return draw_elev_reset(p, ground, gid, step, seed); });
+        }
         v.pos = rd.pos;
     }
     pose(v.pos, reset_now ? rd.q : s.q);
@@ -422,6 +519,11 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
         const F4 u = philox_uniform4(gid, step, ES_CMD_RESAMPLE, seed);
         tgt_x = sym(u.x, p.cmd_xy);
         tgt_y = sym(u.y, p.cmd_xy);
+        if constexpr (LEVELS) {      // the goal square sits on the env's tile
+            const TileOrigin o = tile_origin(tl, e, reset_now ? level_now : load_level<LANES>(tl, e));
+            tgt_x = add_unfused(o.x, tgt_x);
+            tgt_y = add_unfused(o.y, tgt_y);
+        }
         tgt_h = sym(u.z, p.cmd_heading);
         cmd_timer = p.cmd_resample_s;
     }
@@ -458,18 +560,21 @@ WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const
 #ifndef WL_ELEV_LANE_WAVES
 #define WL_ELEV_LANE_WAVES 1
 #endif
-template <int LANES>
-__global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) elev_step_kernel(const WlElevParams p_arg, const VehDerived vd_arg, const WlEnvBuffers b,
+template <int LANES, bool LEVELS>
+__global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) elev_step_kernel(const ElevHead h_arg, const VehDerived vd_arg, const WlEnvBuffers b,
                                                            const HeightFieldGround ground, const float2* __restrict__ actions,
-                                                           const WlStepOut out, const uint64_t seed, const uint64_t step) {
+                                                           const WlStepOut out, const uint64_t seed, const uint64_t step,
+                                                           const WlTerrainLevels tl_arg) {
     __shared__ float blk_metrics[WL_M_COUNT];
-    WlElevParams p = p_arg;
+    const WlElevParams& p_arg = elev_args(h_arg);
+    WlElevParams p_quad;
     VehDerived vd = vd_arg;
     if constexpr (LANES == 4) {   // latency form: one batch of vector loads instead of dependent scalar-load round trips
-        kernarg_vector_copy2(0, p, vd);
-        keep_scalar_common(p, p_arg);
+        elev_kernarg_copy(p_quad, vd);
+        keep_scalar_common(p_quad, p_arg);
         vd.n_sub = vd_arg.n_sub;
     }
+    const WlElevParams& p = LANES == 4 ? p_quad : p_arg;
     constexpr int kEnvs = kBlock / LANES;
     const int wid = LANES == 1 ? 0 : (threadIdx.x & 3);
     const bool lead = LANES == 1 || wid == 0;
@@ -481,7 +586,7 @@ __global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) e
     const Rows S = make_rows(b.state, b.stride);
     if (e < b.n_envs) {
         VehRows<LANES> rows = load_veh_rows<LANES>(S, e, wid);
-        (void)elev_env_step<LANES>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics);
+        (void)elev_env_step<LANES, LEVELS>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics, tl_arg);
     }
     __syncthreads();
     if (threadIdx.x < WL_M_COUNT) {
@@ -534,10 +639,12 @@ inline void launch_elev_scan(const WlElevParams* p, const WlEnvBuffers* b, const
 // spreads the step over 256 CUs instead of 64 (4096 envs).
 constexpr int kFusedThreads = 512, kFusedEnvs = 16;
 
-__global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlElevParams p_arg, const VehDerived vd_arg,
+template <bool LEVELS>
+__global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const ElevHead h_arg, const VehDerived vd_arg,
                                                                        const WlEnvBuffers b, const HeightFieldGround ground,
                                                                        const float2* __restrict__ actions, const WlStepOut out,
-                                                                       const uint64_t seed, const uint64_t step) {
+                                                                       const uint64_t seed, const uint64_t step, const WlTerrainLevels tl_arg) {
+    const WlElevParams& p_arg = elev_args(h_arg);
     __shared__ float blk_metrics[WL_M_COUNT];
     __shared__ ScanFrame frame[kFusedEnvs];
     __shared__ ResetHelper<ElevReset, kFusedEnvs> resets;     // the block's 16 reset draws, by wavefront 1 while wavefront 0 integrates
@@ -568,7 +675,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
             VehRows<4> rows = load_veh_rows<4>(S, e, wid);
             WlElevParams p;
             VehDerived vd;
-            kernarg_vector_copy2(0, p, vd);
+            elev_kernarg_copy(p, vd);
             int go = 1;
             asm volatile("" : "+s"(go) : : "memory");
             if (go) {
@@ -590,7 +697,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 };
                 const HelperReset<ElevReset, kFusedEnvs> reset_src{&resets, e0, true};
-                (void)elev_env_step<4>(p, vd, b, ground, a, rows, out, seed, step, S, e, wid, wid == 0, blk_metrics, nullptr, nullptr, reset_src, pose);
+                (void)elev_env_step<4, LEVELS>(p, vd, b, ground, a, rows, out, seed, step, S, e, wid, wid == 0, blk_metrics, tl_arg, nullptr, nullptr, reset_src, pose);
             }
         }
         WL_TL(4);
@@ -602,8 +709,10 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
     } else {
         if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics
             const int j = tid - 64;
-            resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs,
-                           [&] { return draw_elev_reset(p_arg, ground, (uint32_t)(b.env_offset + e0 + j), step, seed); });
+            // (levels on: the origin-free part -- the tile is known only once the stepping wavefront has the episode's outcome)
+            const uint32_t gid = (uint32_t)(b.env_offset + e0 + j);
+            if constexpr (LEVELS) resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs, [&] { return draw_elev_reset_local(p_arg, gid, step, seed); });
+            else resets.publish(j, j < kFusedEnvs && e0 + j < b.n_envs, [&] { return draw_elev_reset(p_arg, ground, gid, step, seed); });
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();
@@ -668,14 +777,16 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const WlE
 // s_barrier per step and wavefront: at barrier k wavefront 0 has finished step k, the others the scan of step k - 1.
 // Episode metrics of all K steps go to ring slot `slots.cur`, `slots.next` is cleared for the next launch.
 constexpr int kScanLanes = kFusedThreads - 64;
-__global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(const WlElevParams p_arg, const VehDerived vd_arg,
+template <bool LEVELS>
+__global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(const ElevHead h_arg, const VehDerived vd_arg,
                                                                                 const WlEnvBuffers b, const HeightFieldGround ground,
                                                                                 const float2* __restrict__ actions, const WlStepOut out,
                                                                                 const int64_t obs_step_stride, const int64_t vec_step_stride,
                                                                                 const int n_steps, const uint64_t seed, const uint64_t step0,
-                                                                                const MetricSlots slots) {
+                                                                                const MetricSlots slots, const WlTerrainLevels tl_arg) {
     __shared__ float blk_metrics[WL_M_COUNT];
     __shared__ ScanFrame frame[2][kFusedEnvs];
+    const WlElevParams& p_arg = elev_args(h_arg);
     const int tid = threadIdx.x;
     if (tid < WL_M_COUNT) blk_metrics[tid] = 0.f;
     if (b.metrics_slots > 1) clear_metric_slot(b, slots.next);
@@ -691,7 +802,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
         VehDerived vd;
         if (valid) {
             rows = load_veh_rows<4>(S, e, wid);
-            kernarg_vector_copy2(0, p, vd);
+            elev_kernarg_copy(p, vd);
             keep_scalar_common(p, p_arg);
             vd.n_sub = vd_arg.n_sub;
             book = load_elev_book<4>(p, b, S, e);
@@ -700,8 +811,8 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
             if (valid) {
                 const WlStepOut o = step_out_at(out, k, obs_step_stride, vec_step_stride);
                 const float2 a = actions[(int64_t)k * b.n_envs + e];
-                const ScanPose sp = elev_env_step<4, true>(p, vd, b, ground, a, rows, o, seed, step0 + (uint64_t)k, S, e, wid, wid == 0,
-                                                           blk_metrics, &book);
+                const ScanPose sp = elev_env_step<4, LEVELS, true>(p, vd, b, ground, a, rows, o, seed, step0 + (uint64_t)k, S, e, wid, wid == 0,
+                                                           blk_metrics, tl_arg, &book);
                 if (wid == 0) frame[k & 1][tid >> 2] = scan_frame(p, ground, sp);
             }
             __syncthreads();   // barrier k: the poses of step k are published
@@ -831,11 +942,12 @@ WL_DEV void carry_io(float* base, int lane, VehRows<4>& r, ElevBook& k) {
     col_io<PUT>(c, k.act[0]), col_io<PUT>(c, k.act[1]);
 }
 
-template <int ACT>
-__global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(const WlElevParams p, const VehDerived vd, const WlEnvBuffers b,
+template <int ACT, bool LEVELS>
+__global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(const ElevHead h_arg, const VehDerived vd, const WlEnvBuffers b,
                                                                              const HeightFieldGround ground, const WlStepOut out,
                                                                              const int n_steps, const uint64_t seed, const uint64_t step0,
-                                                                             const PolicyIo pio, const MetricSlots slots) {
+                                                                             const PolicyIo pio, const MetricSlots slots, const WlTerrainLevels tl_arg) {
+    const WlElevParams& p = elev_args(h_arg);
     extern __shared__ __attribute__((aligned(16))) float col_lds[];
     float* obs_tile = col_lds;                                   // [16][kTilePitch]
     float* part_a = obs_tile + kFusedEnvs * kTilePitch;          // [8][4][64][4]
@@ -945,7 +1057,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
                 VehRows<4> rows;
                 ElevBook book;
                 carry_io<false>(carry, lane, rows, book);
-                const ScanPose sp = elev_env_step<4, true>(p, vd, b, ground, a, rows, o, seed, step, S, e, wid, wid == 0, blk_metrics, &book,
+                const ScanPose sp = elev_env_step<4, LEVELS, true>(p, vd, b, ground, a, rows, o, seed, step, S, e, wid, wid == 0, blk_metrics, tl_arg, &book,
                                                            prop + (tid >> 2) * 13);
                 carry_io<true>(carry, lane, rows, book);
                 if (wid == 0) frame[tid >> 2] = scan_frame(p, ground, sp);
@@ -1022,7 +1134,14 @@ __global__ void __launch_bounds__(kBlock) elev_reset_kernel(const WlElevParams p
     if (e >= b.n_envs) return;
     if (mask && !mask[e]) return;
     const Rows S = make_rows(b.state, b.stride);
-    const ElevReset rd = draw_elev_reset(p, ground, (uint32_t)(b.env_offset + e), step, seed);
+    const uint32_t gid = (uint32_t)(b.env_offset + e);
+    ElevReset rd;
+    if (p.levels.level) {      // on the env's tile as it stands: a masked reset is no episode end, the level stays
+        rd = draw_elev_reset_local(p, gid, step, seed);
+        place_elev_reset(p, ground, rd, tile_origin(p.levels, e, p.levels.level[e]));
+    } else {
+        rd = draw_elev_reset(p, ground, gid, step, seed);
+    }
     st3(S, WL_S_PX, e, rd.pos);
     S.st(WL_S_QW, e, rd.q.w);
     S.st(WL_S_QX, e, rd.q.x);
@@ -1077,9 +1196,17 @@ __global__ void __launch_bounds__(kBlock) elev_mdp_kernel(const WlElevParams p, 
     }
 }
 
+// WlTerrainLevels: all zero (off), or all of it
+int check_levels(const WlTerrainLevels& tl) {
+    if (!tl.level) return (tl.type || tl.origins || tl.rows != 0 || tl.cols != 0) ? WL_EINVAL : WL_OK;
+    if (!tl.type || !tl.origins || tl.rows < 1 || tl.cols < 1 || (int64_t)tl.rows * tl.cols > 0x3fffffffLL) return WL_EINVAL;
+    if (((uintptr_t)tl.level & 3u) || ((uintptr_t)tl.type & 3u) || ((uintptr_t)tl.origins & 3u)) return WL_EALIGN;
+    return WL_OK;
+}
 int check_elev(const WlElevParams* p, const WlEnvBuffers* b, const WlHeightField* hf) {
-    const int rc = check_implicit_env(p, b);
-    return rc != WL_OK ? rc : heightfield_args_ok(hf, HF_PAIRS);
+    int rc = check_implicit_env(p, b);
+    if (rc == WL_OK) rc = heightfield_args_ok(hf, HF_PAIRS);
+    return rc != WL_OK ? rc : check_levels(p->levels);
 }
 
 // pair[j][i] = code[j][i] | code[min(j + 1, ny - 1)][i] << 16
@@ -1126,14 +1253,19 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
     // two launches, profiles/r06_fused_crossover.txt: 8192 envs 30.9 / 43.8, 12 288: 44.8 / 48.5, 16 384: 58.9 / 52.4, 32 768: 114.5 / 72.2;
     // round 4: 8192 envs 48.5 fused; 16 384 envs 92.5 / 75.4)
     const bool quad = use_quad(b) && (b->lanes == 4 || b->n_envs <= WL_ELEV_FUSED_MAX_ENVS);
+    const ElevHead h = elev_head(p);
+    const bool levels = p->levels.level != nullptr;      // which instantiation: without levels, the code that never knew of them
+    const dim3 fused_grid((b->n_envs + kFusedEnvs - 1) / kFusedEnvs), lane_grid(grid_for(b->n_envs));
     clear_error();
     for (int k = 0; k < n_steps; ++k) {
         const WlStepOut o = step_out_at(*out, k, obs_step_stride, vec_step_stride);
         const float2* a = (const float2*)(actions + (int64_t)k * b->n_envs * 2);
         if (quad) {   // step + scan in one launch
-            elev_step_scan_kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k);
+            if (levels) elev_step_scan_kernel<true><<<fused_grid, kFusedThreads, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            else elev_step_scan_kernel<false><<<fused_grid, kFusedThreads, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
         } else {
-            elev_step_kernel<1><<<grid_for(b->n_envs), kBlock, 0, (hipStream_t)stream>>>(*p, vd, *b, g, a, o, seed, step0 + (uint64_t)k);
+            if (levels) elev_step_kernel<1, true><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            else elev_step_kernel<1, false><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
             launch_elev_scan(p, b, g, o.obs, (hipStream_t)stream);
         }
     }
@@ -1162,18 +1294,19 @@ int wl_elev_collect_rollout(const WlElevParams* p, const WlEnvBuffers* b, const 
     const PolicyIo pio{*actor, *critic, std, io->obs_in, io->actions, io->mu, io->log_prob, io->values, deterministic};
     const int grid = (b->n_envs + kFusedEnvs - 1) / kFusedEnvs;
     const size_t lds_bytes = (size_t)kColLdsFloats * 4;
+    using Kernel = void (*)(ElevHead, VehDerived, WlEnvBuffers, HeightFieldGround, WlStepOut, int, uint64_t, uint64_t, PolicyIo, MetricSlots, WlTerrainLevels);
+    static const Kernel kernels[2][2] = {{elev_collect_rollout_kernel<WL_ACT_RELU, false>, elev_collect_rollout_kernel<WL_ACT_RELU, true>},
+                                         {elev_collect_rollout_kernel<WL_ACT_ELU, false>, elev_collect_rollout_kernel<WL_ACT_ELU, true>}};
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)elev_collect_rollout_kernel<WL_ACT_ELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        (void)hipFuncSetAttribute((const void*)elev_collect_rollout_kernel<WL_ACT_RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        for (const auto& row : kernels)
+            for (const Kernel k : row) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         attr_set = true;
     }
     const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
     clear_error();
-    if (actor->activation == WL_ACT_ELU)
-        elev_collect_rollout_kernel<WL_ACT_ELU><<<grid, kFusedThreads, lds_bytes, (hipStream_t)stream>>>(*p, vd, *b, g, *out, n_steps, seed, step0, pio, ms);
-    else
-        elev_collect_rollout_kernel<WL_ACT_RELU><<<grid, kFusedThreads, lds_bytes, (hipStream_t)stream>>>(*p, vd, *b, g, *out, n_steps, seed, step0, pio, ms);
+    const Kernel k = kernels[actor->activation == WL_ACT_ELU][p->levels.level != nullptr];
+    k<<<grid, kFusedThreads, lds_bytes, (hipStream_t)stream>>>(elev_head(p), vd, *b, g, *out, n_steps, seed, step0, pio, ms, p->levels);
     return launch_status();
 }
 
@@ -1187,9 +1320,10 @@ int wl_elev_rollout_persistent(const WlElevParams* p, const WlEnvBuffers* b, con
     if (n_steps > 1 && obs_step_stride < (int64_t)b->n_envs * WL_ELEV_OBS_DIM) return WL_EINVAL;   // the scan runs a step behind: rows must differ
     if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
-    elev_rollout_persistent_kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(
-        *p, derive_vehicle(p->vehicle, p->sim_dt, p->decimation), *b, make_ground(hf), (const float2*)actions, *out, obs_step_stride,
-        vec_step_stride, n_steps, seed, step0, metric_slots(b, step0, (uint64_t)n_steps));
+    const auto kernel = p->levels.level ? elev_rollout_persistent_kernel<true> : elev_rollout_persistent_kernel<false>;
+    kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(
+        elev_head(p), derive_vehicle(p->vehicle, p->sim_dt, p->decimation), *b, make_ground(hf), (const float2*)actions, *out, obs_step_stride,
+        vec_step_stride, n_steps, seed, step0, metric_slots(b, step0, (uint64_t)n_steps), p->levels);
     return launch_status();
 }
 

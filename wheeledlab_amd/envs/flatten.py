@@ -389,8 +389,21 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     cmd = cfg.commands.goal_pose
     p.cmd_xy, p.cmd_heading = _sym(cmd.ranges.pos_x, "command x"), _sym(cmd.ranges.heading, "command heading")
     p.cmd_resample_s = float(cmd.resampling_time_range[1])
-    flat.curriculum = _terms(cfg.curriculum)
-    flat.extra.update(_terrain_source(cfg.scene.terrain, reset_range=(-p.reset_xy, p.reset_xy)))
+    # the terrain_levels term is the kernels' own (WlElevParams.levels): it runs inside every step, not at curriculum boundaries
+    slot = getattr(cfg.curriculum, "terrain_levels", None)
+    if isinstance(slot, str):                 # the term by name (a command-line override): mdp.<name> must be the levels term
+        if getattr(mdp, slot, None) is not mdp.terrain_levels_goal:
+            raise ValueError(f"curriculum.terrain_levels = '{slot}': the terrain-levels term is 'terrain_levels_goal'")
+        from .managers_cfg import CurriculumTermCfg
+        cfg.curriculum.terrain_levels = CurriculumTermCfg(func=mdp.terrain_levels_goal)
+    terms = _terms(cfg.curriculum)
+    level_terms = [name for name, term in terms if term.func is mdp.terrain_levels_goal]
+    flat.curriculum = [(name, term) for name, term in terms if term.func is not mdp.terrain_levels_goal]
+    flat.extra.update(_terrain_source(cfg.scene.terrain, reset_range=None if level_terms else (-p.reset_xy, p.reset_xy)))
+    if level_terms:
+        from .terrain_levels import check_curriculum
+        check_curriculum(flat.extra["terrain_generator"], p.reset_xy, p.cmd_xy)
+        flat.extra["terrain_levels"] = dict(name=level_terms[0], max_init_terrain_level=getattr(cfg.scene.terrain, "max_init_terrain_level", None))
     return flat
 
 

@@ -187,6 +187,9 @@ class EpisodeLog(dict):
         if kind == "x":
             self[key] = i
             return i
+        if kind == "f":                        # a device scalar computed on demand (the terrain curriculum's mean level)
+            self[key] = v = i()
+            return v
         m = self._metrics if self._idx is None else self._metrics[self._idx]
         if m.dim() == 2:                       # raw accumulator [WL_M_SHARDS][WL_M_COUNT]: fold the shards once
             m = m.sum(0)
@@ -234,7 +237,13 @@ class ManagerBasedRLEnv:
         if flat.extra.get("terrain_generator") is not None:      # a procedural terrain: generated on the device, redrawn in place
             flat.extra["heightfield"] = generate_heightfield(flat.extra["terrain_generator"], self.device)
         if flat.task == "elevation":
-            self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), **common)
+            levels = None
+            if flat.extra.get("terrain_levels") is not None:      # each rank builds its slice of the world's assignment
+                from ..core import TerrainLevels
+                world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+                levels = TerrainLevels(flat.extra["terrain_generator"], self.num_envs, self.device, rank * self.num_envs, world * self.num_envs,
+                                       flat.extra["terrain_levels"]["max_init_terrain_level"], seed)
+            self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), terrain_levels=levels, **common)
         elif flat.task in ("visual", "visual_depth"):
             x = flat.extra
             kw = dict(trav_map=x["map"], spacing=x["spacing"], map_kwargs=dict(map_size=x["map_size"], env_size=x["env_size"],
@@ -275,6 +284,8 @@ class ManagerBasedRLEnv:
         self.extras = {}
         self.obs_buf = {}
         self._log_keys = episode_log_keys(self.reward_manager._slots, flat.termination_names)
+        if getattr(self._batch, "levels", None) is not None:      # the mean level: one reduction, run when the log is read
+            self._log_keys["Curriculum/" + flat.extra["terrain_levels"]["name"]] = ("f", self._batch.levels.mean_level)
         # "torch terms run between the kernel launches": the fused collectors (one launch per rollout / writing straight
         # into the runner's storage) are off whenever any kind of custom term is registered
         self._has_custom_rewards = bool(self._custom_rew or self._custom_term or self._custom_obs)
@@ -477,6 +488,13 @@ class ManagerBasedRLEnv:
         resets = max(m[A.M_RESETS], 1.0)
         out = {}
         for key, (kind, i) in self._log_keys.items():
+            if kind == "f":
+                v = i().to(torch.float32)
+                if reduce_ranks and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                    torch.distributed.all_reduce(v)
+                    v = v / torch.distributed.get_world_size()
+                out[key] = float(v)
+                continue
             out[key] = m[i] if kind == "c" else m[A.M_EPSUM0 + i] / resets / self.max_episode_length_s
         if self._custom_log:      # terms that run as torch behind the kernel: their latest episode means / counts -- ONE stacked copy
             keys = list(self._custom_log)

@@ -237,6 +237,21 @@ def increase_reward_weight_over_time(env, env_ids, reward_term_name: str, increa
         env.reward_manager.set_term_cfg(reward_term_name, term_cfg)
 
 
+def terrain_levels_goal(env, env_ids=None, asset_cfg=_ROBOT):
+    """IsaacLab's `terrain_levels` curriculum for the goal task: an env that ends its episode at the goal moves a row of tiles up,
+    one that fails (below the minimum height, stuck, rolled over, non-finite) a row down, a time-out stays; past the last row it
+    draws a uniform row.  The move itself is made INSIDE the step kernels, where the resets are (csrc/wl_elev.hip next_level;
+    flatten.py switches it on when a CurrTerm names this function); the term's value -- logged as Curriculum/terrain_levels -- is the
+    mean level, a 0-dim device tensor."""
+    levels = getattr(env._batch, "levels", None)
+    if levels is None:
+        raise ValueError("terrain_levels_goal: this env carries no terrain levels (register it as a CurrTerm on a generator terrain)")
+    return levels.mean_level()
+
+
+terrain_levels_goal.wl_kind = "curriculum"
+
+
 # =====================================================================================================================
 # Elevation task terms (reference: wheeledlab_tasks/elevation/mushr_elevation_env_cfg.py) -- kernel-backed markers.
 # Direct calls evaluate through `wl_elev_mdp` on the env's current state.

@@ -410,12 +410,58 @@ class LidarView:
         self.num_instances = batch.n
 
 
+class TerrainLevelsView:
+    """`env.scene.terrain` of an env that carries terrain levels: the terrain's config (every attribute of it reads through) plus
+    IsaacLab's TerrainImporter tensors -- `terrain_levels` / `terrain_types` int32 [n], LIVE (the tensors the step kernels read and
+    write), `terrain_origins` [rows, cols, 3] (tile centres, z = the terrain's height there) and `env_origins` [n, 3]."""
+
+    def __init__(self, cfg, batch):
+        self.__dict__.update(_cfg=cfg, _b=batch)
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["_cfg"], name)
+
+    def __setattr__(self, name, value):
+        setattr(self._cfg, name, value)
+
+    @property
+    def terrain_levels(self):
+        return self._b.levels.level
+
+    @property
+    def terrain_types(self):
+        return self._b.levels.type
+
+    @property
+    def terrain_origins(self):
+        lv, hf = self._b.levels, self._b.hf
+        u, v = (lv.origins[:, 0] - hf.x0) / hf.cell, (lv.origins[:, 1] - hf.y0) / hf.cell
+        ny, nx = hf.heights.shape
+        i, j = u.floor().long().clamp(0, nx - 2), v.floor().long().clamp(0, ny - 2)
+        fu, fv = (u - i).clamp(0, 1), (v - j).clamp(0, 1)
+        h = hf.heights
+        z = (h[j, i] * (1 - fu) + h[j, i + 1] * fu) * (1 - fv) + (h[j + 1, i] * (1 - fu) + h[j + 1, i + 1] * fu) * fv
+        return torch.cat([lv.origins, z[:, None]], 1).reshape(lv.rows, lv.cols, 3)
+
+    @property
+    def env_origins(self):
+        lv = self._b.levels
+        return self.terrain_origins[lv.level.long(), lv.type.long()]
+
+
 class SceneView:
+    @property
+    def env_origins(self):
+        """[n, 3]: zeros (env_spacing = 0, mushr_drift_env_cfg.py:373) unless the batch carries terrain levels -- then every env's tile centre"""
+        if getattr(self._b, "levels", None) is not None:
+            return self.terrain.env_origins
+        return self._zero_origins
+
     def __init__(self, batch, cfg=None, task: str = "drift"):
         self._b = batch
         self.cfg = cfg
         self.num_envs = batch.n
-        self.env_origins = torch.zeros(batch.n, 3, device=batch.device)  # env_spacing = 0 (mushr_drift_env_cfg.py:373)
+        self._zero_origins = torch.zeros(batch.n, 3, device=batch.device)
         names = getattr(getattr(cfg, "robot", None), "joint_names", None) or MUSHR_JOINT_NAMES
         self.articulations = {"robot": ArticulationView(batch, names)}
         self.sensors = {}
@@ -428,6 +474,8 @@ class SceneView:
             if isinstance(value, LidarCfg):
                 self.sensors[name] = LidarView(batch, value)
         self.terrain = getattr(cfg, "terrain", None)
+        if getattr(batch, "levels", None) is not None:
+            self.terrain = TerrainLevelsView(self.terrain, batch)
 
     def __getitem__(self, key):
         if key in self.articulations:

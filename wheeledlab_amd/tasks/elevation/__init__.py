@@ -1,1 +1,1 @@
-from .mushr_elevation_env_cfg import MushrElevationPlayEnvCfg, MushrElevationRLEnvCfg  # noqa: F401
+from .mushr_elevation_env_cfg import MushrElevationPlayEnvCfg, MushrElevationRLEnvCfg, MushrElevationTerrainLevelsEnvCfg  # noqa: F401

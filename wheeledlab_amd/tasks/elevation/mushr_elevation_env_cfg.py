@@ -50,6 +50,7 @@ class ElevationTerrainImporterCfg(TerrainImporterCfg):
     mesh_path = None                   # Wavefront OBJ of the terrain mesh (z up, metres); exclusive with `heightfield`
     mesh_cell = 0.05                   # lattice spacing (m) the mesh is rasterised at
     terrain_generator = None           # envs.terrain_gen_cfg.TerrainGeneratorCfg, used with terrain_type = "generator" (exclusive too)
+    max_init_terrain_level = None      # terrain levels (a CurrTerm of mdp.terrain_levels_goal): envs start on rows 0 .. this; None: any row
     physics_material = RigidBodyMaterialCfg(friction_combine_mode="multiply", restitution_combine_mode="multiply",
                                             static_friction=1.0, dynamic_friction=1.0)
 
@@ -82,6 +83,9 @@ class ElevationCurriculumCfg:
     """:311-333"""
     more_goal = _ramp("vel_towards_goal", 5.0, 50, 5)
     more_falling_pen = _ramp("falling_penalty", 1.0, 50, 10)
+    # terrain levels (needs a generator terrain): a CurrTerm of mdp.terrain_levels_goal, or that function's name -- what a command-line
+    # override can spell: env.curriculum.terrain_levels=terrain_levels_goal
+    terrain_levels = None
 
 
 @configclass
@@ -142,6 +146,29 @@ class MushrElevationRLEnvCfg(ManagerBasedRLEnvCfg):
         self.sim.render_interval = self.decimation
         self.episode_length_s = 20
         self.scene = ElevationSceneCfg(num_envs=self.num_envs, env_spacing=self.env_spacing)
+
+
+@configclass
+class ElevationTerrainLevelsCurriculumCfg(ElevationCurriculumCfg):
+    terrain_levels = CurrTerm(func=mdp.terrain_levels_goal)
+
+
+@configclass
+class MushrElevationTerrainLevelsEnvCfg(MushrElevationRLEnvCfg):
+    """The elevation task on a generated terrain with per-env terrain levels (IsaacLab's terrain curriculum): 5 x 5 tiles of 8 m,
+    difficulty rising along x; every env spawns within 1.5 m of its tile's centre, its goals lie within 3.5 m of it, and the tile's
+    row follows the episodes' outcomes (mdp.terrain_levels_goal).  Not a registered task id: pass the class, or override
+    scene.terrain / curriculum / events / commands of Isaac-MushrElevationRL-v0 to the same values."""
+    curriculum: ElevationTerrainLevelsCurriculumCfg = ElevationTerrainLevelsCurriculumCfg()
+
+    def __post_init__(self):
+        super().__post_init__()
+        from ...envs.terrain_gen_cfg import TerrainGeneratorCfg
+        self.scene.terrain.terrain_type = "generator"
+        self.scene.terrain.terrain_generator = TerrainGeneratorCfg()
+        self.scene.terrain.max_init_terrain_level = 1
+        self.events.set_goal.params["pose_range"].update(x=(-1.5, 1.5), y=(-1.5, 1.5))
+        self.commands.goal_pose.ranges.pos_x = self.commands.goal_pose.ranges.pos_y = (-3.5, 3.5)
 
 
 @configclass
