@@ -96,6 +96,45 @@ def out_of_map_excused(coord, cells, spacing):
     return (h64 != h32) & (a >= min(h64, h32)) & (a <= max(h64, h32))
 
 
+# rows every task's reset writes (csrc/wl_kernel_common.h::store_reset_rows): pose, linear and angular velocity, last action,
+# the WL_MAX_REW_TERMS episode sums
+RESET_SHARED_ROWS = tuple(range(0, 13)) + (19, 20) + tuple(range(27, 35))
+
+
+def check_masked_reset(env, full_state, own_rows=()):
+    """A masked reset of `env` -- 70 envs (the last wavefront is partial), fresh (step 0), every row and the episode lengths
+    preloaded with non-zero values, every third env masked in -- against `full_state`: the state [rows, >= 70] an unmasked reset
+    of a batch with the same seed left at step 0, which the caller has held to the oracle (a draw depends on the env's global
+    index, the seed and the step, not on the batch size).  The drawn rows are thus exact against the kernel's own unmasked output,
+    which meets the oracle within the caller's tolerance; the zeroed and the untouched rows are exact in absolute terms.  Exact values:
+      masked in:  RESET_SHARED_ROWS and the task's `own_rows` equal full_state (so the velocities / actions / sums a reset zeroes
+                  are 0 although they were not before), episode_len 0, every other row as preloaded;
+      masked out, and the padding columns up to the stride: everything as preloaded."""
+    import torch
+    n = env.n
+    assert n == 70 and env.step_count == 0
+    rows, stride = env.state.shape
+    r, e = torch.arange(rows, dtype=torch.float32)[:, None], torch.arange(stride, dtype=torch.float32)[None, :]
+    env.state.copy_((1.0 + 0.25 * r + e / 128.0).to(env.state.device))        # > 0 everywhere, distinct per row and env
+    env.episode_len.copy_((5 + torch.arange(stride, dtype=torch.int32)).to(env.state.device))
+    before, ep_before = env.state.clone(), env.episode_len.clone()
+    mask = torch.arange(n, device=env.state.device) % 3 == 0
+    env.reset(mask)
+    torch.cuda.synchronize()
+    got, ep = env.state.cpu(), env.episode_len.cpu()
+    before, ep_before = before.cpu(), ep_before.cpu()
+    inn = torch.zeros(stride, dtype=torch.bool)
+    inn[:n] = mask.cpu()
+    assert torch.equal(got[:, ~inn], before[:, ~inn]) and torch.equal(ep[~inn], ep_before[~inn])
+    written = sorted(set(RESET_SHARED_ROWS) | set(own_rows))
+    kept = [i for i in range(rows) if i not in written]
+    want = torch.as_tensor(full_state)[:, :n][:, mask.cpu()]
+    assert torch.equal(got[written][:, inn], want[written])
+    assert (got[list(range(10, 13)) + [19, 20] + list(range(27, 35))][:, inn] == 0).all() and (ep[inn] == 0).all()
+    assert torch.equal(got[kept][:, inn], before[kept][:, inn])
+    assert int(inn.sum()) == 24
+
+
 # The edge sets live under tests/golden/ only: tests/golden/*_edges.npz (input seeds as generated) and tests/golden/seed1000/*_edges.npz
 # (WL_GOLDEN_SEED_OFFSET=1000), or WL_GOLDEN_DIR alone when it is set (the fresh-seed rerun of test_oracle_golden_drift.py).  The
 # edge values themselves are fixed; only their random filler follows the offset.

@@ -15,6 +15,7 @@ from oracle import drift_mdp as OM
 from oracle import drift_step as OS
 from oracle import params as OP
 from oracle import philox as PH
+from tests import parity_predicates as PRED
 
 pytestmark = pytest.mark.gpu
 
@@ -162,6 +163,8 @@ def test_reset_kernel_matches_oracle(lib):
     # every reset pose is within pos_noise of the centre line (events.py:122-124)
     d = OM.cross_track_dist(st[:3, :300].T, 0.8, 0.8, 0.0, 1.0)
     assert d.max() <= 0.5 * np.sqrt(2) + 1e-5
+    # a masked reset over preloaded rows: the same values, exactly, in the masked envs and nothing anywhere else
+    PRED.check_masked_reset(_fresh(70, seed=11), st, own_rows=(21, 22))      # + the two push timers
 
 
 def _single_step_parity(env, p, n, seed, mode, steps=40):

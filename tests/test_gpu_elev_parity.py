@@ -95,6 +95,8 @@ def test_elev_reset_and_observation_match_oracle():
     assert d[:, :13].max() < 2e-5
     assert d[:, 13:].max() < 2e-5                      # 26 x 26 height map: bilinear gathers agree to fp32 rounding
     assert obs.shape == (200, 689)
+    # a masked reset over preloaded rows: the same values, exactly, in the masked envs and nothing anywhere else
+    PRED.check_masked_reset(_fresh(70, seed=11)[0], st, own_rows=range(35, 41))      # + command frame, goal, command timer
 
 
 @pytest.mark.parametrize("lanes,z_scale", [(4, None), (1, None), (4, 1e-4), (1, 1e-4)])

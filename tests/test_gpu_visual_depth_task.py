@@ -42,9 +42,12 @@ def test_reset_places_cars_on_the_terrain_and_first_observation_matches_oracle()
     ep = np.ones(st.shape[1], np.int32)
     OS.reset_envs(p, o, ep, OS.spawn_cells(trav), np.arange(n), 11, 0, hf=hf)
     np.testing.assert_allclose(st[:23, :n], o[:23, :n], rtol=1e-6, atol=2e-6)
+    assert (st[27:35, :n] == 0).all()
     zt, _, _ = OH.sample(*hf, st[0, :n], st[1, :n])
     np.testing.assert_allclose(st[2, :n] - zt, 0.1, atol=1e-5)                       # 0.1 m above the terrain under the spawn cell
     assert np.abs(st[0, :n]).max() <= 20.0 and np.abs(st[1, :n]).max() <= 20.0 and zt.max() > 0.25   # on the field, hills included
+    # a masked reset over preloaded rows: the same values, exactly, in the masked envs and nothing anywhere else
+    PRED.check_masked_reset(_batch(70, 11)[0], st)
     obs = env.observe().cpu().numpy()
     want = OS.observe_depth(p, st[:, :n].copy(), hf, MAX_DEPTH)
     assert obs.shape == (n, 4808)

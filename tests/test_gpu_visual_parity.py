@@ -72,6 +72,8 @@ def test_visual_reset_and_camera_match_oracle(trav):
     OS.reset_envs(p, o, ep, cells, np.arange(128), 11, 0)
     np.testing.assert_allclose(st[:, :128], o[:, :128], rtol=1e-6, atol=2e-6)
     assert trav[VM.get_map_id(st[0, :128], st[1, :128])[1], VM.get_map_id(st[0, :128], st[1, :128])[0]].all()   # spawned on the path
+    # a masked reset over preloaded rows: the same values, exactly, in the masked envs and nothing anywhere else
+    PRED.check_masked_reset(_batch(70, trav, seed=11), st)
     # (brightness, contrast, blur sigma, contrast before brightness): torchvision's ColorJitter draws the op order per call
     for aug in ((1.0, 1.0, 0.0, 0), (1.4, 0.85, 1.7, 0), (0.5, 1.15, 0.4, 0), (1.4, 0.85, 1.7, 1), (1.7, 1.2, 0.0, 1), (0.4, 1.2, 3.0, 1)):
         env.p.brightness, env.p.contrast, env.p.blur_sigma, env.p.contrast_first = aug

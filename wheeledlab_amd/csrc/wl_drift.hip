@@ -205,20 +205,9 @@ __global__ void __launch_bounds__(kBlock) drift_reset_kernel(const WlDriftParams
     if (mask && !mask[e]) return;
     const Rows S = make_rows(b.state, b.stride);
     const ResetDraw rd = draw_reset(p, b.ref_poses, (uint32_t)(b.env_offset + e), step, seed);
-    st3(S, WL_S_PX, e, rd.pos);
-    S.st(WL_S_QW, e, rd.q.w);
-    S.st(WL_S_QX, e, rd.q.x);
-    S.st(WL_S_QY, e, rd.q.y);
-    S.st(WL_S_QZ, e, rd.q.z);
-    st3(S, WL_S_VX, e, v3(0.f, 0.f, 0.f));
-    st3(S, WL_S_WX, e, v3(0.f, 0.f, 0.f));
-    S.st(WL_S_ACT0, e, 0.f);
-    S.st(WL_S_ACT1, e, 0.f);
+    store_reset_rows(S, b, e, rd.pos, rd.q, v3(0.f, 0.f, 0.f));
     S.st(WL_S_TIMER_HF, e, rd.timer_hf);
     S.st(WL_S_TIMER_LF, e, rd.timer_lf);
-#pragma unroll
-    for (int i = 0; i < WL_MAX_REW_TERMS; ++i) S.st(WL_S_EPSUM0 + i, e, 0.f);
-    b.episode_len[e] = 0;
 }
 
 __global__ void __launch_bounds__(kBlock) drift_observe_kernel(const WlDriftParams p, const WlEnvBuffers b,

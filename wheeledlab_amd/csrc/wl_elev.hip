@@ -22,6 +22,8 @@
 //      already hidden behind it.)
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 // Debug builds only (tools/build_variants.sh ... -DWL_FUSED_TIMELINE=1; tools/fused_timeline.py): lane 0 of a wavefront stamps
 // the 100 MHz wall clock into wl_timeline[block][slot] at the phase boundaries of the fused step + scan launch.
 #ifndef WL_FUSED_TIMELINE
@@ -160,43 +162,24 @@ WL_DEV int next_level(const WlTerrainLevels& tl, int level, bool at_goal, bool f
     return lv;
 }
 
-// the part of a reset's draw that does not depend on where the env's tile is: pos.x / pos.y hold the OFFSETS from the tile's centre,
-// tgt_x / tgt_y the goal's; place_elev_reset adds the centre and stands the car on the terrain
-WL_DEV ElevReset draw_elev_reset_local(const WlElevParams& p, uint32_t gid, uint64_t step, uint64_t seed) {
-    const F4 u = philox_uniform4(gid, step, ES_RESET, seed);
-    const F4 c = philox_uniform4(gid, step, ES_CMD_RESET, seed);
-    ElevReset r;
-    r.pos = v3(sym(u.x, p.reset_xy), sym(u.y, p.reset_xy), 0.f);
-    float s, cc;
-    sincos_fast(0.5f * sym(u.z, p.reset_yaw), s, cc);
-    r.q = Quat{cc, 0.f, 0.f, s};
-    r.vx = fmaf(u.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
-    r.vy = fmaf(c.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
-    r.tgt_x = sym(c.x, p.cmd_xy);
-    r.tgt_y = sym(c.y, p.cmd_xy);
-    r.tgt_h = sym(c.z, p.cmd_heading);
-    return r;
-}
-WL_DEV void place_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, TileOrigin o) {
-    const float x = add_unfused(o.x, r.pos.x), y = add_unfused(o.y, r.pos.y);
+// stands a drawn car at (x, y) on the terrain
+WL_DEV void stand_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, float x, float y) {
     float zt;
     V3 n;
     g.sample(x, y, zt, n);
     r.pos = v3(x, y, fmaxf(p.reset_z, zt + p.spawn_clearance));
-    r.tgt_x = add_unfused(o.x, r.tgt_x);
-    r.tgt_y = add_unfused(o.y, r.tgt_y);
 }
-
-// isaaclab reset_root_state_uniform with the ranges of :409-419 + UniformPose2dCommand resample (:425-435)
-WL_DEV ElevReset draw_elev_reset(const WlElevParams& p, const HeightFieldGround& g, uint32_t gid, uint64_t step, uint64_t seed) {
+// isaaclab reset_root_state_uniform with the ranges of :409-419 + UniformPose2dCommand resample (:425-435).  STAND: the car is stood
+// on the terrain where it is drawn; otherwise pos.x / pos.y (and tgt_x / tgt_y) stay OFFSETS from a tile's centre for place_elev_reset
+// (`g` is read only when STAND: the origin-free wrapper passes nullptr)
+template <bool STAND>
+WL_DEV ElevReset draw_elev_reset_at(const WlElevParams& p, const HeightFieldGround* g, uint32_t gid, uint64_t step, uint64_t seed) {
     const F4 u = philox_uniform4(gid, step, ES_RESET, seed);
     const F4 c = philox_uniform4(gid, step, ES_CMD_RESET, seed);
     ElevReset r;
     const float x = sym(u.x, p.reset_xy), y = sym(u.y, p.reset_xy);
-    float zt;
-    V3 n;
-    g.sample(x, y, zt, n);
-    r.pos = v3(x, y, fmaxf(p.reset_z, zt + p.spawn_clearance));
+    if constexpr (STAND) stand_elev_reset(p, *g, r, x, y);
+    else r.pos = v3(x, y, 0.f);
     float s, cc;
     sincos_fast(0.5f * sym(u.z, p.reset_yaw), s, cc);
     r.q = Quat{cc, 0.f, 0.f, s};
@@ -206,6 +189,18 @@ WL_DEV ElevReset draw_elev_reset(const WlElevParams& p, const HeightFieldGround&
     r.tgt_y = sym(c.y, p.cmd_xy);
     r.tgt_h = sym(c.z, p.cmd_heading);
     return r;
+}
+// the part of a reset's draw that does not depend on where the env's tile is; place_elev_reset adds the centre and stands the car
+WL_DEV ElevReset draw_elev_reset_local(const WlElevParams& p, uint32_t gid, uint64_t step, uint64_t seed) {
+    return draw_elev_reset_at<false>(p, nullptr, gid, step, seed);
+}
+WL_DEV ElevReset draw_elev_reset(const WlElevParams& p, const HeightFieldGround& g, uint32_t gid, uint64_t step, uint64_t seed) {
+    return draw_elev_reset_at<true>(p, &g, gid, step, seed);
+}
+WL_DEV void place_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, TileOrigin o) {
+    stand_elev_reset(p, g, r, add_unfused(o.x, r.pos.x), add_unfused(o.y, r.pos.y));
+    r.tgt_x = add_unfused(o.x, r.tgt_x);
+    r.tgt_y = add_unfused(o.y, r.tgt_y);
 }
 
 // what the height scan needs of an env after its step: root position and the cos / sin of its yaw
@@ -589,10 +584,7 @@ __global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) e
         (void)elev_env_step<LANES, LEVELS>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics, tl_arg);
     }
     __syncthreads();
-    if (threadIdx.x < WL_M_COUNT) {
-        const float m = blk_metrics[threadIdx.x];
-        if (m != 0.f) atomicAdd(metric_shard(b, m_slot) + threadIdx.x, m);   // threads 0..15 = wavefront 0 of the block
-    }
+    block_metrics_flush(blk_metrics, b, m_slot);   // threads 0..15 = wavefront 0 of the block
 }
 
 // world_height_map (:44-48): the 26 x 26 yaw-aligned height scan, clipped to +-10, into obs[e][13:689].  One block per
@@ -702,10 +694,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_step_scan_kernel(const Ele
         }
         WL_TL(4);
         static_assert(WL_M_COUNT <= 64, "wavefront 0 flushes the block's metrics alone");
-        if (tid < WL_M_COUNT) {
-            const float m = blk_metrics[tid];
-            if (m != 0.f) atomicAdd(metric_shard(b, m_slot) + tid, m);
-        }
+        block_metrics_flush(blk_metrics, b, m_slot);
     } else {
         if (tid < 128) {      // wavefront 1: the block's reset draws, in the shadow of the physics
             const int j = tid - 64;
@@ -818,10 +807,7 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
             __syncthreads();   // barrier k: the poses of step k are published
         }
         if (valid) store_elev_state<4>(p, b, S, e, wid, wid == 0, rows, book);
-        if (tid < WL_M_COUNT) {   // only this wavefront accumulated
-            const float m = blk_metrics[tid];
-            if (m != 0.f) atomicAdd(metric_shard(b, slots.cur) + tid, m);
-        }
+        block_metrics_flush(blk_metrics, b, slots.cur);   // only this wavefront accumulated
         return;
     }
     // ---- wavefronts 1..7: the scan of step k, one step behind the physics ----
@@ -857,7 +843,6 @@ __global__ void __launch_bounds__(kFusedThreads) elev_rollout_persistent_kernel(
     }
 }
 
-// proprioceptive part only, lane per env: used by wl_elev_observe (reset / get_observations path)
 // ---- the runner's collection, K x { actions = actor(obs) -> env.step -> storage rows } (modified_rsl_rl_runner.py:70-80), as ONE launch ----
 // Block = 16 envs, eight wavefronts, K steps in a loop.  What makes the policy step cheap enough to live inside the env's
 // block: the ACTOR's first-layer matrix (64 x 689 f32 = 176 KB) is held in the block's REGISTERS for the whole launch (each
@@ -1110,13 +1095,11 @@ __global__ void __launch_bounds__(kFusedThreads) elev_collect_rollout_kernel(con
             carry_io<false>(carry, lane, rows, book);
             store_elev_state<4>(p, b, S, e, wid, wid == 0, rows, book);
         }
-        if (tid < WL_M_COUNT) {   // only this wavefront accumulated
-            const float v = blk_metrics[tid];
-            if (v != 0.f) atomicAdd(metric_shard(b, slots.cur) + tid, v);
-        }
+        block_metrics_flush(blk_metrics, b, slots.cur);   // only this wavefront accumulated
     }
 }
 
+// proprioceptive part only, lane per env: used by wl_elev_observe (reset / get_observations path)
 __global__ void __launch_bounds__(kBlock) elev_prop_kernel(const WlElevParams p, const WlEnvBuffers b, float* __restrict__ obs) {
     const int e = blockIdx.x * kBlock + threadIdx.x;
     if (e >= b.n_envs) return;
@@ -1142,17 +1125,7 @@ __global__ void __launch_bounds__(kBlock) elev_reset_kernel(const WlElevParams p
     } else {
         rd = draw_elev_reset(p, ground, gid, step, seed);
     }
-    st3(S, WL_S_PX, e, rd.pos);
-    S.st(WL_S_QW, e, rd.q.w);
-    S.st(WL_S_QX, e, rd.q.x);
-    S.st(WL_S_QY, e, rd.q.y);
-    S.st(WL_S_QZ, e, rd.q.z);
-    st3(S, WL_S_VX, e, v3(rd.vx, rd.vy, 0.f));
-    st3(S, WL_S_WX, e, v3(0.f, 0.f, 0.f));
-    S.st(WL_S_ACT0, e, 0.f);
-    S.st(WL_S_ACT1, e, 0.f);
-#pragma unroll
-    for (int i = 0; i < WL_MAX_REW_TERMS; ++i) S.st(WL_S_EPSUM0 + i, e, 0.f);
+    store_reset_rows(S, b, e, rd.pos, rd.q, v3(rd.vx, rd.vy, 0.f));
     S.st(WL_S_TGT_X, e, rd.tgt_x);
     S.st(WL_S_TGT_Y, e, rd.tgt_y);
     S.st(WL_S_TGT_H, e, rd.tgt_h);
@@ -1162,7 +1135,6 @@ __global__ void __launch_bounds__(kBlock) elev_reset_kernel(const WlElevParams p
     const float dx = rd.tgt_x - rd.pos.x, dy = rd.tgt_y - rd.pos.y;
     S.st(WL_S_CMD_BX, e, fmaf(c, dx, sn * dy));
     S.st(WL_S_CMD_BY, e, fmaf(-sn, dx, c * dy));
-    b.episode_len[e] = 0;
 }
 
 __global__ void __launch_bounds__(kBlock) elev_mdp_kernel(const WlElevParams p, int n, int64_t stride, const float* __restrict__ pos,
@@ -1202,6 +1174,13 @@ int check_levels(const WlTerrainLevels& tl) {
     if (!tl.type || !tl.origins || tl.rows < 1 || tl.cols < 1 || (int64_t)tl.rows * tl.cols > 0x3fffffffLL) return WL_EINVAL;
     if (((uintptr_t)tl.level & 3u) || ((uintptr_t)tl.type & 3u) || ((uintptr_t)tl.origins & 3u)) return WL_EALIGN;
     return WL_OK;
+}
+// Which LEVELS instantiation a launch takes -- without terrain levels, the code that never knew of them.  Calls launch(lv) with lv a
+// std::true_type / std::false_type (a template argument of the kernel).
+template <class F>
+inline void launch_levels(const WlElevParams* p, F&& launch) {
+    if (p->levels.level != nullptr) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 int check_elev(const WlElevParams* p, const WlEnvBuffers* b, const WlHeightField* hf) {
     int rc = check_implicit_env(p, b);
@@ -1254,18 +1233,20 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
     // round 4: 8192 envs 48.5 fused; 16 384 envs 92.5 / 75.4)
     const bool quad = use_quad(b) && (b->lanes == 4 || b->n_envs <= WL_ELEV_FUSED_MAX_ENVS);
     const ElevHead h = elev_head(p);
-    const bool levels = p->levels.level != nullptr;      // which instantiation: without levels, the code that never knew of them
     const dim3 fused_grid((b->n_envs + kFusedEnvs - 1) / kFusedEnvs), lane_grid(grid_for(b->n_envs));
     clear_error();
     for (int k = 0; k < n_steps; ++k) {
         const WlStepOut o = step_out_at(*out, k, obs_step_stride, vec_step_stride);
         const float2* a = (const float2*)(actions + (int64_t)k * b->n_envs * 2);
+        // (one launch_levels per kernel, not one around the if: keeps the emission order of the kernels)
         if (quad) {   // step + scan in one launch
-            if (levels) elev_step_scan_kernel<true><<<fused_grid, kFusedThreads, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
-            else elev_step_scan_kernel<false><<<fused_grid, kFusedThreads, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            launch_levels(p, [&](auto lv) {
+                elev_step_scan_kernel<decltype(lv)::value><<<fused_grid, kFusedThreads, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            });
         } else {
-            if (levels) elev_step_kernel<1, true><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
-            else elev_step_kernel<1, false><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            launch_levels(p, [&](auto lv) {
+                elev_step_kernel<1, decltype(lv)::value><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+            });
             launch_elev_scan(p, b, g, o.obs, (hipStream_t)stream);
         }
     }
@@ -1305,8 +1286,10 @@ int wl_elev_collect_rollout(const WlElevParams* p, const WlEnvBuffers* b, const 
     }
     const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
     clear_error();
-    const Kernel k = kernels[actor->activation == WL_ACT_ELU][p->levels.level != nullptr];
-    k<<<grid, kFusedThreads, lds_bytes, (hipStream_t)stream>>>(elev_head(p), vd, *b, g, *out, n_steps, seed, step0, pio, ms, p->levels);
+    launch_levels(p, [&](auto lv) {
+        kernels[actor->activation == WL_ACT_ELU][decltype(lv)::value]<<<grid, kFusedThreads, lds_bytes, (hipStream_t)stream>>>(
+            elev_head(p), vd, *b, g, *out, n_steps, seed, step0, pio, ms, p->levels);
+    });
     return launch_status();
 }
 
@@ -1320,10 +1303,11 @@ int wl_elev_rollout_persistent(const WlElevParams* p, const WlEnvBuffers* b, con
     if (n_steps > 1 && obs_step_stride < (int64_t)b->n_envs * WL_ELEV_OBS_DIM) return WL_EINVAL;   // the scan runs a step behind: rows must differ
     if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
-    const auto kernel = p->levels.level ? elev_rollout_persistent_kernel<true> : elev_rollout_persistent_kernel<false>;
-    kernel<<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(
-        elev_head(p), derive_vehicle(p->vehicle, p->sim_dt, p->decimation), *b, make_ground(hf), (const float2*)actions, *out, obs_step_stride,
-        vec_step_stride, n_steps, seed, step0, metric_slots(b, step0, (uint64_t)n_steps), p->levels);
+    launch_levels(p, [&](auto lv) {
+        elev_rollout_persistent_kernel<decltype(lv)::value><<<(b->n_envs + kFusedEnvs - 1) / kFusedEnvs, kFusedThreads, 0, (hipStream_t)stream>>>(
+            elev_head(p), derive_vehicle(p->vehicle, p->sim_dt, p->decimation), *b, make_ground(hf), (const float2*)actions, *out, obs_step_stride,
+            vec_step_stride, n_steps, seed, step0, metric_slots(b, step0, (uint64_t)n_steps), p->levels);
+    });
     return launch_status();
 }
 

@@ -57,6 +57,22 @@ WL_DEV void st3(const Rows& s, int row, int e, V3 v) {
     s.st(row + 1, e, v.y);
     s.st(row + 2, e, v.z);
 }
+// the rows every task's reset writes for env e: the drawn pose and linear velocity; angular velocity, last action and the episode
+// sums zeroed; the episode restarted.  (The task's own rows -- timers, goal commands -- are its reset kernel's.)
+WL_DEV void store_reset_rows(const Rows& S, const WlEnvBuffers& b, int e, V3 pos, Quat q, V3 v) {
+    st3(S, WL_S_PX, e, pos);
+    S.st(WL_S_QW, e, q.w);
+    S.st(WL_S_QX, e, q.x);
+    S.st(WL_S_QY, e, q.y);
+    S.st(WL_S_QZ, e, q.z);
+    st3(S, WL_S_VX, e, v);
+    st3(S, WL_S_WX, e, v3(0.f, 0.f, 0.f));
+    S.st(WL_S_ACT0, e, 0.f);
+    S.st(WL_S_ACT1, e, 0.f);
+#pragma unroll
+    for (int i = 0; i < WL_MAX_REW_TERMS; ++i) S.st(WL_S_EPSUM0 + i, e, 0.f);
+    b.episode_len[e] = 0;
+}
 
 // Kernel arguments live in memory the host rewrites for every launch and the GPU reads uncached; the compiler fetches
 // them with scalar loads in as many dependent batches as the 102-entry SGPR file forces (six `s_load ... s_waitcnt`
@@ -155,6 +171,13 @@ WL_DEV float* metric_shard(const WlEnvBuffers& b, int slot) {   // this wavefron
 WL_DEV void clear_metric_slot(const WlEnvBuffers& b, int slot) {   // block 0 zeroes all shards of `slot`
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < kMetricSlotFloats; i += (int)blockDim.x) b.metrics[(int64_t)slot * kMetricSlotFloats + i] = 0.f;
+}
+// the block's LDS metric sums -> the calling wavefront's shard of `slot`, by the block's first WL_M_COUNT threads (one wavefront)
+WL_DEV void block_metrics_flush(const float* blk_metrics, const WlEnvBuffers& b, int slot) {
+    if (threadIdx.x < WL_M_COUNT) {
+        const float m = blk_metrics[threadIdx.x];
+        if (m != 0.f) atomicAdd(metric_shard(b, slot) + threadIdx.x, m);
+    }
 }
 
 // How a GROUP of wavefronts of a block meets (the visual camera's render groups, the elevation collector's layer-1 wavefronts).

@@ -207,10 +207,7 @@ __global__ void __launch_bounds__(kBlock) visual_step_kernel(const WlVisualParam
                                        prop_stride > 0 ? out.obs + (int64_t)e * prop_stride + prop_offset : nullptr, reset_src);
     }
     __syncthreads();
-    if (threadIdx.x < WL_M_COUNT) {
-        const float v = blk_metrics[threadIdx.x];
-        if (v != 0.f) atomicAdd(metric_shard(b, m_slot) + threadIdx.x, v);   // threads 0..15 = wavefront 0 of the block
-    }
+    block_metrics_flush(blk_metrics, b, m_slot);   // threads 0..15 = wavefront 0 of the block
 }
 
 // camera ray of pixel (row, col) of the FULL 60 x 80 image in the body frame: optical axis = body +x, image right =
@@ -536,10 +533,7 @@ __global__ void __launch_bounds__(kPersistThreads) visual_rollout_persistent_ker
             }
             __syncthreads();   // barrier k: the poses of step k are published
         }
-        if (tid < WL_M_COUNT) {   // only this wavefront accumulated
-            const float v = blk_metrics[tid];
-            if (v != 0.f) atomicAdd(metric_shard(b, slots.cur) + tid, v);
-        }
+        block_metrics_flush(blk_metrics, b, slots.cur);   // only this wavefront accumulated
         return;
     }
     // ---- the other wavefronts: the camera of step k, one step behind the physics ----
@@ -580,18 +574,7 @@ __global__ void __launch_bounds__(kBlock) visual_reset_kernel(const WlVisualPara
     if (mask && !mask[e]) return;
     const Rows S = make_rows(b.state, b.stride);
     const VisReset rd = visual_reset_pose(p, m, ground, (uint32_t)(b.env_offset + e), step, seed);
-    st3(S, WL_S_PX, e, rd.pos);
-    S.st(WL_S_QW, e, rd.q.w);
-    S.st(WL_S_QX, e, rd.q.x);
-    S.st(WL_S_QY, e, rd.q.y);
-    S.st(WL_S_QZ, e, rd.q.z);
-    st3(S, WL_S_VX, e, v3(0.f, 0.f, 0.f));
-    st3(S, WL_S_WX, e, v3(0.f, 0.f, 0.f));
-    S.st(WL_S_ACT0, e, 0.f);
-    S.st(WL_S_ACT1, e, 0.f);
-#pragma unroll
-    for (int i = 0; i < WL_MAX_REW_TERMS; ++i) S.st(WL_S_EPSUM0 + i, e, 0.f);
-    b.episode_len[e] = 0;
+    store_reset_rows(S, b, e, rd.pos, rd.q, v3(0.f, 0.f, 0.f));
 }
 
 __global__ void __launch_bounds__(kBlock) visual_mdp_kernel(const WlVisualParams p, const WlTravMap m, int n, int64_t stride,
