@@ -48,6 +48,8 @@ def main():
                                name_prefix="rl-video", disable_logger=False)
         print(f"[INFO] Recording video of playback to: {folder}")
     env = RslRlVecEnvWrapper(ClipAction(env))
+    # a checkpoint trained behind an observation normaliser carries it (rsl_rl's obs_norm_state_dict): play it behind the same one
+    agent_cfg.empirical_normalization = "obs_norm_state_dict" in torch.load(args.checkpoint, map_location="cpu", weights_only=False)
     runner = OnPolicyRunner(env, agent_cfg, device=args.device)
     runner.load(args.checkpoint, load_optimizer=False)
     policy = runner.get_inference_policy(device=env.unwrapped.device)

@@ -140,11 +140,16 @@ def main():
     # replicated state must not have drifted apart (identical averaged gradients -> identical steps on every rank)
     flat_params = torch.cat([p.detach().reshape(-1) for p in runner.actor_critic.parameters()])
     in_sync = D.ranks_agree(flat_params)
+    if runner.obs_normalizer is not None:       # the observation statistics are replicated state too (merged from all-reduced sums)
+        nz = runner.obs_normalizer
+        in_sync = D.ranks_agree(torch.cat([nz._mean.reshape(-1), nz._var.reshape(-1), nz._std.reshape(-1)])) and in_sync
+        in_sync = D.ranks_agree(nz.count.reshape(1)) and in_sync          # the int64 itself: fp32 would hide a few rows at 1e8
     if world > 1:
         torch.distributed.barrier()
     if rank == 0:
         print(json.dumps({"run_config": args.run_config_name, "task": env_setup.task_name, "num_envs": env_setup.num_envs,
-                          "fused_collection": runner.fused, "fused_learner": runner.alg.fused_update, "kernel_policy": runner.kernel_policy, "iterations": len(hist),
+                          "fused_collection": runner.fused, "fused_learner": runner.alg.fused_update, "kernel_policy": runner.kernel_policy,
+                          "empirical_normalization": runner.obs_normalizer is not None, "iterations": len(hist),
                           "mean_step_reward_first": first["mean_step_reward"], "mean_step_reward_last": last["mean_step_reward"],
                           "mean_reward_last": last["mean_reward"], "mean_episode_length_last": last["mean_episode_length"],
                           "n_gpus": world, "ranks_in_sync": in_sync, "fps_last": last["fps"], "collection_fps_last": last["collection_fps"], "log_dir": log_dir}))

@@ -336,6 +336,20 @@ LIDAR_SIGNATURES = {
     "wl_lidar_scan": (C.c_int, [_P(WlLidarParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _vp, _vp, _vp]),
 }
 
+# include/wheeledlab_amd_obsnorm.h: empirical observation normalisation -- a header of its own, outside the drop-in step boundary
+WL_OBSNORM_VERSION = 1
+OBSNORM_MAX_DIM = 1 << 20
+OBSNORM_MAX_ROWS = 1 << 23
+
+# every symbol include/wheeledlab_amd_obsnorm.h declares
+OBSNORM_SIGNATURES = {
+    "wl_obsnorm_version": (C.c_int, []),
+    "wl_obsnorm_scratch_bytes": (C.c_int64, [_i64, _i32, _i64]),
+    "wl_obsnorm_accumulate": (C.c_int, [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wl_obsnorm_update": (C.c_int, [_i32, _vp, _i64, _i64, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wl_obsnorm_fold": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -358,7 +372,7 @@ def load(path: str | None = None):
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES, **OBSNORM_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -375,6 +389,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has terrain version {lib.wl_terrain_version()}, python expects {WL_TERRAIN_VERSION}: rebuild")
     if lib.wl_lidar_version() != WL_LIDAR_VERSION:
         raise HipExtensionMissing(f"{path} has lidar version {lib.wl_lidar_version()}, python expects {WL_LIDAR_VERSION}: rebuild")
+    if lib.wl_obsnorm_version() != WL_OBSNORM_VERSION:
+        raise HipExtensionMissing(f"{path} has obsnorm version {lib.wl_obsnorm_version()}, python expects {WL_OBSNORM_VERSION}: rebuild")
     _lib = lib
     return lib
 

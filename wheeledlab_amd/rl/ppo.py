@@ -15,13 +15,16 @@ What is MI355X-specific:
 * the update, drift agents: the minibatch step (forward, losses, backward, clipping, adaptive-KL rule, Adam) in the HIP
   library (`FusedPpoStep`: `wl_ppo_minibatch`, or `wl_ppo_gradients` -> all-reduce -> `wl_ppo_apply` when data-parallel);
   other widths: torch autograd with the weight gradients of the tall minibatches as chunked batched GEMMs (`_TallLinear`);
-* the actor / critic parameters the kernels read ARE the torch Parameters (updated in place, rsl_rl's checkpoint keys).
+* the actor / critic parameters the kernels read ARE the torch Parameters (updated in place, rsl_rl's checkpoint keys);
+* `empirical_normalization`: the observation statistics are merged once per iteration on the device and folded into the first
+  layers the collectors read (rl/normalizer.py, `wl_obs_norm.hip`), so every collector above stays in use on raw observations.
 On a CPU (tests, gloo world-2) everything here runs as plain torch.
 """
 from __future__ import annotations
 
 import os
 import time
+import warnings
 from collections import deque
 
 import torch
@@ -30,6 +33,7 @@ from torch import nn
 from .. import dist as D
 from ..policy import ActorCritic as _KernelActorCritic
 from ..policy import Mlp, RolloutStorage
+from .normalizer import RATIO_WARN
 
 _ACT = {"elu": nn.ELU, "relu": nn.ReLU, "tanh": nn.Tanh}
 
@@ -90,6 +94,7 @@ class ActorCritic(nn.Module):
         self.std = nn.Parameter(init_noise_std * torch.ones(num_actions))
         self.distribution = None
         self._fused = None
+        self._folded = None
 
     # -- torch path (gradient step, tasks without a fused collector) --
     def update_distribution(self, obs):
@@ -138,6 +143,30 @@ class ActorCritic(nn.Module):
         return self.activation in ("elu", "relu") and ok(self.actor, 2) and ok(self.critic, 1) and self.std.is_cuda
 
     def fused(self):
+        """the view the collectors read: the parameters themselves, or -- once an observation normaliser has folded itself into
+        the first layers (folded_view) -- the folded first layers over the same remaining parameters"""
+        return self._folded if self._folded is not None else self.param_view()
+
+    def folded_view(self):
+        """a kernel-side view for RAW observations under an observation normaliser: `actor.w1 / b1` and `critic.w1 / b1` are
+        tensors of their own that rl.normalizer.EmpiricalNormalization.fold() fills (W diag(inv_std), b - W' mean), always the
+        same ones, so a consumer that keeps their pointers reads the refreshed values at its next launch; every other layer and
+        `std` alias the parameters"""
+        if self._folded is None:
+            p = self.param_view()
+            v = _KernelActorCritic.__new__(_KernelActorCritic)
+            for name in ("actor", "critic"):
+                src = getattr(p, name)
+                m = Mlp.__new__(Mlp)
+                m.__dict__.update(src.__dict__)
+                m.w1, m.b1 = src.w1.clone(), src.b1.clone()
+                setattr(v, name, m)
+            v.std = p.std
+            self._folded = v
+        return self._folded
+
+    def param_view(self):
+        """the kernel-side view of the parameters themselves (what the learner's kernels update in place)"""
         if self._fused is None:
             v = _KernelActorCritic.__new__(_KernelActorCritic)   # a kernel-side view: aliases the Parameters, owns nothing
             v.actor = Mlp.from_sequential(self.actor, self.activation, self.std.device)
@@ -321,6 +350,15 @@ class OnPolicyRunner:
             raise ValueError("kernel_policy needs [64, 64] elu / relu MLPs with 2 actions on a GPU")
         self.kernel_policy = can_act if kernel_policy is None else bool(kernel_policy)
         self.storage = RolloutStorage(self.num_steps_per_env, env.num_envs, env.num_obs, env.num_actions, self.device)
+        # empirical observation normalisation (rl/normalizer.py): one normaliser shared by the actor and the critic (one
+        # observation group).  Off: None, and nothing below runs one launch more than without the field
+        self.obs_normalizer = None
+        if bool(cfg.get("empirical_normalization", False)):
+            from .normalizer import EmpiricalNormalization
+            self.obs_normalizer = EmpiricalNormalization(env.num_obs, until=int(cfg.get("empirical_normalization_until", 10 ** 8))).to(self.device)
+            if self._folds:
+                self.obs_normalizer.fold(self.actor_critic)
+        self._ratio_warned = False
         self.current_learning_iteration = 0
         # one process per GPU: every rank runs this loop on its own env shard with identical parameters (same seed, gradient
         # averaged per minibatch step in PPO); rank 0 prints and writes checkpoints, throughput is the whole job's
@@ -329,6 +367,15 @@ class OnPolicyRunner:
         self.tot_timesteps, self.tot_time = 0, 0.0
         self.history: list[dict] = []
         self.collection_paths: list[str] = []      # per iteration: "fused" or "stepwise"
+
+    @property
+    def _folds(self) -> bool:
+        """the collectors read raw observations through folded first layers (any kernel collector); else torch normalises"""
+        return self.obs_normalizer is not None and self.device.type == "cuda" and (self.fused or self.kernel_policy)
+
+    def _normalized(self, obs):
+        """what the torch actor / critic see of a raw observation: the frozen statistics applied, never updated here"""
+        return obs if self.obs_normalizer is None else self.obs_normalizer.normalize(obs)
 
     # ---- collection --------------------------------------------------------------------------------------
     def _collect_fused(self):
@@ -373,7 +420,7 @@ class OnPolicyRunner:
                              batch.step_count, batch.env_offset, planes_fresh=k > 0)
                     a = st.actions[k]
                 else:
-                    a = ac.act(obs)
+                    a = ac.act(self._normalized(obs))
                     st.actions[k].copy_(a)
                     st.mu[k].copy_(ac.action_mean)
                     st.actions_log_prob[k].copy_(ac.get_actions_log_prob(a))
@@ -385,9 +432,9 @@ class OnPolicyRunner:
             st.observations[self.num_steps_per_env].copy_(obs)
             K, n = st.n_steps, st.n_envs
             if one_launch:
-                st.values[K].copy_(ac.evaluate(obs).reshape(n))
+                st.values[K].copy_(ac.evaluate(self._normalized(obs)).reshape(n))
             else:
-                st.values.copy_(ac.evaluate(st.observations.reshape((K + 1) * n, -1)).reshape(K + 1, n))
+                st.values.copy_(ac.evaluate(self._normalized(st.observations.reshape((K + 1) * n, -1))).reshape(K + 1, n))
         return obs
 
     def _bookkeeping(self, st, carry_ret, carry_len):
@@ -471,7 +518,21 @@ class OnPolicyRunner:
                     st.bootstrap_time_outs(self.alg.gamma)
             torch.cuda.synchronize() if self.device.type == "cuda" else None
             t1 = time.time()
+            nz = self.obs_normalizer
+            if nz is not None:
+                # the storage rows 0 .. K - 1 become normalised in place with the statistics the collection ran with, then the
+                # statistics advance; the update reads those rows through the UNFOLDED parameters; the fold follows it with
+                # the new weights and the new statistics
+                losses_extra = dict(obs_norm_max_ratio=nz.merge_rollout(st, self.world))
+                if losses_extra["obs_norm_max_ratio"] > RATIO_WARN and not self._ratio_warned:
+                    self._ratio_warned = True
+                    warnings.warn(f"observation normaliser: max |mean| / (std + eps) = {losses_extra['obs_norm_max_ratio']:.0f} > "
+                                  f"{RATIO_WARN:.0f}: the folded first layer cancels (DESIGN.md, observation normalisation)")
             losses = self.alg.update(st)
+            if nz is not None:
+                losses.update(losses_extra)
+                if self._folds:
+                    nz.fold(self.actor_critic)
             torch.cuda.synchronize() if self.device.type == "cuda" else None
             t2 = time.time()
             self.current_learning_iteration = it + 1
@@ -496,12 +557,24 @@ class OnPolicyRunner:
     # ---- checkpoints: rsl_rl's keys (train_rl.py:96-106 resumes from `model_*.pt`) --------------------------
     def save(self, path: str, infos=None):
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        torch.save({"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer_state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        d = {"model_state_dict": self.actor_critic.state_dict(), "optimizer_state_dict": self.alg.optimizer_state_dict(),
+             "iter": self.current_learning_iteration, "infos": infos}
+        if self.obs_normalizer is not None:     # rsl_rl's keys; one observation group: both hold the one shared normaliser
+            d["obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+            d["critic_obs_norm_state_dict"] = self.obs_normalizer.state_dict()
+        torch.save(d, path)
 
     def load(self, path: str, load_optimizer: bool = True):
         d = torch.load(path, map_location=self.device, weights_only=False)
+        # a policy played without the normaliser it was trained behind (or behind one it never saw) is silently wrong: refuse
+        if ("obs_norm_state_dict" in d) != (self.obs_normalizer is not None):
+            raise ValueError(f"{path} was written with empirical_normalization={'obs_norm_state_dict' in d}, this runner has "
+                             f"empirical_normalization={self.obs_normalizer is not None}")
         self.actor_critic.load_state_dict(d["model_state_dict"])    # copies in place: the kernel view stays valid
+        if self.obs_normalizer is not None:
+            self.obs_normalizer.load_state_dict(d["obs_norm_state_dict"])
+            if self._folds:
+                self.obs_normalizer.fold(self.actor_critic)
         if load_optimizer:
             self.alg.load_optimizer_state(d["optimizer_state_dict"])
         self.current_learning_iteration = d["iter"]
@@ -511,7 +584,13 @@ class OnPolicyRunner:
         self.actor_critic.eval()
         if device is not None:
             self.actor_critic.to(device)
-        return self.actor_critic.act_inference
+        nz = self.obs_normalizer
+        if nz is None:
+            return self.actor_critic.act_inference
+        nz.eval()                               # eval mode: normalises, never updates
+        if device is not None:
+            nz.to(device)
+        return lambda obs: self.actor_critic.act_inference(nz(obs))
 
 
 def _finished_episodes(rewards, done, carry_ret, carry_len):
@@ -551,7 +630,7 @@ class FusedPpoStep:
         if not actor_critic.fusable() or actor_critic.actor[0].in_features != 14 or actor_critic.actor[4].out_features != 2:
             raise ValueError("the fused PPO step is specialised for the drift agents' 14-64-64-2 / 14-64-64-1 MLPs")
         self._C, self._A, self.lib = C, A, A.load()
-        self.ac, self.view = actor_critic, actor_critic.fused()
+        self.ac, self.view = actor_critic, actor_critic.param_view()
         dev = actor_critic.std.device
         self.dev = dev
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
@@ -684,7 +763,7 @@ class FusedWidePpoStep(FusedPpoStep):
         if not self.shapes_ok(capacity, mb_capacity):
             raise ValueError("rows per update and the minibatch size must be multiples of 64")
         self._C, self._A, self.lib = C, A, A.load()
-        self.ac, self.view = actor_critic, actor_critic.fused()
+        self.ac, self.view = actor_critic, actor_critic.param_view()
         dev = actor_critic.std.device
         self.dev = dev
         self.in_dim, self.dp = D_in, (D_in + 63) // 64 * 64

@@ -34,7 +34,7 @@ class MushrPPORunnerCfg:
     max_iterations: int = 150
     save_interval: int = 50
     experiment_name: str = "ppo_mushr"
-    empirical_normalization: bool = False
+    empirical_normalization: bool = False      # read by OnPolicyRunner (rl/normalizer.py); true: observations normalised by running moments
     policy: PolicyCfg = PolicyCfg()
     algorithm: AlgorithmCfg = AlgorithmCfg()
 

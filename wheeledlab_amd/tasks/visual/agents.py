@@ -16,6 +16,6 @@ class MushrPPORunnerCfg:
     max_iterations: int = 4000
     save_interval: int = 50
     experiment_name: str = "ppo_mushr_visual"
-    empirical_normalization: bool = False
+    empirical_normalization: bool = False      # read by OnPolicyRunner (rl/normalizer.py); true: observations normalised by running moments
     policy: ReluPolicyCfg = ReluPolicyCfg()
     algorithm: AlgorithmCfg = AlgorithmCfg()
