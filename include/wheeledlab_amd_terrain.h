@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define WL_TERRAIN_VERSION 2
+#define WL_TERRAIN_VERSION 3
 #define WL_TERRAIN_TILE 16               /* the raster pass fills 16 x 16-point tiles of the lattice, one workgroup each   */
 #define WL_TERRAIN_MAX_TILES_PER_FACE 64 /* a face whose lattice rectangle spans more tiles goes to the big list every tile filters */
 #define WL_TERRAIN_MAX_SIDE (1 << 23)    /* nx and ny: 2 .. WL_TERRAIN_MAX_SIDE - 1, nx * ny <= 2^31 - 1              */
@@ -114,6 +114,66 @@ int wl_terrain_gen_check(const WlTerrainGenParams* p, const WlTerrainTile* tiles
  * caller validates them with wl_terrain_gen_check -- the kernel itself clamps what it reads from them (loop counts, divisors), so
  * that no descriptor can send it out of bounds.  Allocates nothing, keeps no state. */
 int wl_terrain_generate(const WlTerrainGenParams* p, const WlTerrainTile* tiles, int16_t* codes_out, void* stream);
+
+/* ---- flat patches: level ground found on the lattice, to spawn on (wl_flat_patch.hip) -------------------------------------------------
+ *
+ * For each of n_tiles windows of the lattice, n_patches lattice points whose neighbourhood is level -- IsaacLab's FlatPatchSamplingCfg /
+ * TerrainImporter.flat_patches, searched on the device so that a field redrawn in place finds its patches again without a host
+ * round trip.  All integers on the lattice: attempt a = 0, 1, ... of slot k of tile t draws X = Philox(t, k, a, params.stream) (the
+ * library's Philox4x32, 7 rounds, key = the seed's words) and tests the point i = i_lo + hi32(X[0] * (i_hi - i_lo + 1)), j = j_lo +
+ * hi32(X[1] * (j_hi - j_lo + 1)) (hi32: the high half of the 64-bit product).  It is ACCEPTED when, over the lattice points (i + di,
+ * j + dj) with |di|, |dj| <= radius_cells and di^2 + dj^2 <= radius2 (indices clamped to the lattice), max code - min code <=
+ * max_diff_codes, min code >= z_lo_code and max code <= z_hi_code.  A bilinear cell lies between its corners, so a disc of lattice
+ * points that covers the metric disc bounds the surface inside it.  The slot takes the accepted attempt with the LOWEST index below
+ * max_tries; with none it takes the window's centre ((i_lo + i_hi) / 2, (j_lo + j_hi) / 2) and is marked failed.  Outputs, for slot
+ * s = t * n_patches + k: xy_out[s] = (x0 + fl(i * cell), y0 + fl(j * cell)) in fp32 (the product rounded before the sum), z_out[s] =
+ * fl(code(i, j) * z_scale), tries_out[s] = the accepted attempt's index or -1.  One wavefront per slot tests 64 consecutive attempts
+ * a round, at most ceil(max_tries / 64) rounds; plain stores, no atomics: the same bytes from run to run.
+ *
+ * The deal: wl_flat_patch_deal gives env e (global id gid = env_offset + e) the virtual column type_out[e] = (gid * cols / world_envs) *
+ * n_patches + hi32(W * n_patches), W = word 0 of Philox(gid, epoch low, epoch high, WL_TS_PATCH_DEAL): with xy_out read as the origins
+ * table [rows][cols * n_patches][2] of a WlTerrainLevels of cols * n_patches columns, the step kernels spawn about patches. */
+#define WL_TS_PATCH 14                   /* Philox stream ids: the finder's default, and the deal's                          */
+#define WL_TS_PATCH_DEAL 15
+#define WL_PATCH_MAX_RADIUS 64           /* radius_cells                                                                      */
+#define WL_PATCH_MAX_TRIES 65536         /* max_tries                                                                         */
+#define WL_PATCH_MAX_SLOTS (1 << 22)     /* n_tiles * n_patches                                                               */
+
+typedef struct WlPatchTile {
+    int32_t i_lo, i_hi, j_lo, j_hi;  /* the inclusive lattice window of patch centres                                         */
+    int32_t radius_cells;            /* the disc's bounding square: 0 .. WL_PATCH_MAX_RADIUS                                  */
+    int32_t radius2;                 /* di^2 + dj^2 <= radius2: 0 .. radius_cells^2                                           */
+    int32_t max_diff_codes;          /* largest max - min over the disc (>= 0)                                                */
+    int32_t z_lo_code, z_hi_code;    /* every code of the disc within [z_lo_code, z_hi_code]                                  */
+    int32_t max_tries;               /* 0 .. WL_PATCH_MAX_TRIES; 0: every slot takes the window's centre                      */
+    int32_t pad[2];
+} WlPatchTile;                       /* 48 bytes */
+
+typedef struct WlFlatPatchParams {
+    int32_t n_tiles, n_patches;      /* >= 1 each, n_tiles * n_patches <= WL_PATCH_MAX_SLOTS                                  */
+    uint32_t stream;                 /* Philox stream id (counter word 3): WL_TS_PATCH unless the caller keeps several sets   */
+    int32_t reserved;                /* 0                                                                                     */
+    uint64_t seed;
+} WlFlatPatchParams;                 /* 24 bytes */
+
+/* Validate the arguments as wl_flat_patches does, without a launch and without reading device memory: `tiles_host` is a HOST copy of
+ * the n_tiles descriptors (NULL: the descriptors are not checked).  WL_EINVAL: a field without codes or with sizes / placement out of
+ * range, counts out of range, an empty window, a disc that leaves the lattice, radius_cells, radius2, max_diff_codes or max_tries out
+ * of range.  WL_EALIGN: hf->height not 2-byte or tiles_host not 4-byte aligned. */
+int wl_flat_patch_check(const WlHeightField* hf, const WlFlatPatchParams* p, const WlPatchTile* tiles_host);
+
+/* Find the patches: `tiles` WlPatchTile [n_tiles], xy_out float [n_tiles][n_patches][2], z_out float [n_tiles][n_patches], tries_out
+ * int32 [n_tiles][n_patches], device pointers, 4-byte aligned (WL_EALIGN otherwise; NULL: WL_EINVAL).  The field and the parameters are
+ * validated before the launch and nothing is launched on a refusal; the descriptors live in device memory, so the caller validates
+ * them with wl_flat_patch_check -- the kernel clamps what it reads from them (window, radius, tries, every index).  Allocates
+ * nothing, keeps no state. */
+int wl_flat_patches(const WlHeightField* hf, const WlFlatPatchParams* p, const WlPatchTile* tiles, float* xy_out, float* z_out,
+                    int32_t* tries_out, void* stream);
+
+/* Deal every env a slot: type_out int32 [n_envs] (device, 4-byte aligned).  n_envs >= 0, env_offset >= 0, env_offset + n_envs <=
+ * world_envs, cols >= 1, n_patches >= 1, cols * n_patches <= 2^30 (WL_EINVAL otherwise; nothing is launched on a refusal). */
+int wl_flat_patch_deal(int32_t n_envs, int32_t env_offset, int32_t world_envs, int32_t cols, int32_t n_patches, uint64_t epoch,
+                       uint64_t seed, int32_t* type_out, void* stream);
 
 /* WL_TERRAIN_VERSION of the library */
 int wl_terrain_version(void);

@@ -12,7 +12,8 @@ F1TENTH_DRIFT_CONFIG); the remaining arguments are Hydra-style `key=value` overr
 (actor MLP on the matrix pipe + env.step, csrc/wl_policy.hip) and the PPO update runs in csrc/wl_ppo.hip;
 `--stepwise` forces the generic one-launch-per-env.step() collector (the only one for the elevation / visual tasks,
 whose observations are 689 / 3208 wide).  `train.terrain_resample_interval=K` redraws a procedural terrain (the elevation and
-visual-depth tasks with `scene.terrain.terrain_type = "generator"`) every K iterations."""
+visual-depth tasks with `scene.terrain.terrain_type = "generator"`) every K iterations; `train.patch_redeal_interval=K` (default 1)
+deals every env another spawn patch of its tile every K iterations (flat patches: mdp.reset_root_state_from_terrain)."""
 import argparse
 import json
 import os
@@ -59,6 +60,23 @@ def terrain_resampler(env, interval: int):
             return False
         env.regenerate_terrain(base_seed + it)
         return True
+    return before_iteration
+
+
+def patch_redealer(env, interval: int, then=None):
+    """`train.patch_redeal_interval=K` (default 1): every K iterations every env is dealt another of its tile's spawn patches (flat
+    patches with mdp.reset_root_state_from_terrain; one launch, nothing is reset).  `then`: the hook to run after it (the terrain
+    resampler).  None when there is nothing to deal and nothing to chain."""
+    levels = getattr(env._batch, "levels", None)
+    if int(interval or 0) <= 0 or levels is None or levels.patches is None:
+        return then
+    done = [0]
+
+    def before_iteration(it: int) -> bool:
+        done[0] += 1
+        if done[0] % int(interval) == 0:
+            env.redeal_patches(it)
+        return bool(then(it)) if then is not None else False
     return before_iteration
 
 
@@ -129,7 +147,8 @@ def main():
     env.seed(agent_cfg.seed)
     env.unwrapped.common_step_counter = train_cfg.set_env_step       # for continuing curriculums (train_rl.py:113)
     hist = runner.learn(train_cfg.num_iterations, verbose=not args.quiet,
-                        before_iteration=terrain_resampler(env.unwrapped, train_cfg.terrain_resample_interval))
+                        before_iteration=patch_redealer(env.unwrapped, train_cfg.patch_redeal_interval,
+                                                        terrain_resampler(env.unwrapped, train_cfg.terrain_resample_interval)))
     if log_dir:
         with open(os.path.join(log_dir, "history.json"), "w") as f:
             json.dump(hist, f)

@@ -280,7 +280,7 @@ VIEWER_SIGNATURES = {
 }
 
 # include/wheeledlab_amd_terrain.h: mesh terrains -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)
-WL_TERRAIN_VERSION = 2
+WL_TERRAIN_VERSION = 3
 TERRAIN_TILE = 16
 TERRAIN_MAX_TILES_PER_FACE = 64
 TERRAIN_MAX_SIDE = 1 << 23
@@ -311,6 +311,20 @@ class WlTerrainGenParams(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32), ("base_code", C.c_int32), ("seed", C.c_uint64)]
 
 
+# flat patches (the same header): level ground found on the lattice (csrc/wl_flat_patch.hip)
+TS_PATCH, TS_PATCH_DEAL = 14, 15
+PATCH_MAX_RADIUS, PATCH_MAX_TRIES, PATCH_MAX_SLOTS = 64, 65536, 1 << 22
+
+
+class WlPatchTile(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("i_lo", "i_hi", "j_lo", "j_hi", "radius_cells", "radius2", "max_diff_codes", "z_lo_code",
+                                         "z_hi_code", "max_tries")] + [("pad", C.c_int32 * 2)]
+
+
+class WlFlatPatchParams(C.Structure):
+    _fields_ = [("n_tiles", C.c_int32), ("n_patches", C.c_int32), ("stream", C.c_uint32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
 # every symbol include/wheeledlab_amd_terrain.h declares
 TERRAIN_SIGNATURES = {
     "wl_terrain_version": (C.c_int, []),
@@ -318,6 +332,9 @@ TERRAIN_SIGNATURES = {
     "wl_mesh_raster": (C.c_int, [_P(WlMeshRasterParams), _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "wl_terrain_gen_check": (C.c_int, [_P(WlTerrainGenParams), _vp]),
     "wl_terrain_generate": (C.c_int, [_P(WlTerrainGenParams), _vp, _vp, _vp]),
+    "wl_flat_patch_check": (C.c_int, [_P(WlHeightField), _P(WlFlatPatchParams), _vp]),
+    "wl_flat_patches": (C.c_int, [_P(WlHeightField), _P(WlFlatPatchParams), _vp, _vp, _vp, _vp, _vp]),
+    "wl_flat_patch_deal": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp]),
 }
 
 # include/wheeledlab_amd_lidar.h: lidar range scans -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)

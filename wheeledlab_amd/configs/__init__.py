@@ -77,6 +77,7 @@ class RLTrainConfig(TrainConfig):
     rl_algo_class: str = MISSING
     set_env_step: int = 0
     terrain_resample_interval: int = 0     # iterations between redraws of a procedural terrain (env.regenerate_terrain); 0: never
+    patch_redeal_interval: int = 1         # iterations between deals of the spawn patches (env.redeal_patches; flat patches only); 0: never
 
 
 @configclass

@@ -69,7 +69,8 @@ class DeviceHeightField:
     tensors; or another DeviceHeightField on the same device (shared).  `.heights`: the decoded fp32 grid -- exactly the values
     every kernel sees (what tests hand to the oracle).  `outside_z`: the height of the plane beyond the grid (what the contact samplers
     and the depth walk meet there); None keeps a shared field's own, else 0.  The field owns every table derived from the codes,
-    one of each for all its views: `pairs`, `heights` and `pyramid`; after editing `codes` in place, refresh() them.  A field made by
+    one of each for all its views: `pairs`, `heights` and `pyramid`, and every FlatPatches found on it; after editing `codes` in
+    place, refresh() them.  A field made by
     generate_heightfield remembers its TerrainGeneratorCfg (`generator`) and can be drawn again in place: regenerate()."""
 
     def __init__(self, heightfield, device, outside_z: float | None = None):
@@ -109,7 +110,8 @@ class DeviceHeightField:
             self.heights = torch.empty(self.codes.shape, dtype=torch.float32, device=self.device)
             self.pairs = torch.empty(self.codes.shape, dtype=torch.int32, device=self.device)
             # what every view of these buffers shares: the generator's config (None: not generated), the bound pyramid (None: no ray cast yet)
-            self._shared = {"generator": None, "pyramid": None}
+            # and the flat-patch sets found on it (weak references: a set lives as long as its owner)
+            self._shared = {"generator": None, "pyramid": None, "patches": []}
         self.outside_z = float(0.0 if outside_z is None else outside_z)
         ny, nx = self.codes.shape
         self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, self.pairs.data_ptr())
@@ -147,6 +149,11 @@ class DeviceHeightField:
         torch.mul(self.codes.to(torch.float32), torch.tensor(self.z_scale, dtype=torch.float32, device=self.device), out=self.heights)
         if self._shared["pyramid"] is not None:
             self._build("wl_heightfield_build_pyramid", self._shared["pyramid"])
+        if self._shared["patches"]:       # (no flat patches on the field: nothing is launched for them)
+            live = [r for r in self._shared["patches"] if r() is not None]
+            self._shared["patches"][:] = live
+            for r in live:
+                r().find()
         return self
 
     def as_tuple(self):
@@ -513,19 +520,217 @@ class DriftBatch(_EnvBatch):
         return storage
 
 
+class FlatPatches:
+    """Level ground found on a field by the device (wl_flat_patches; IsaacLab's TerrainImporter.flat_patches): for each of the
+    `tiles` windows (WlPatchTile rows as a structured array: envs.terrain_gen_cfg.patch_table / field_patch_table) `n_patches`
+    lattice points whose disc of neighbours is level.  `xy` float32 [T, P, 2], `z` float32 [T, P], `tries` int32 [T, P] (the accepted
+    attempt's index, -1: none -- the slot holds its window's centre) live on the device at fixed addresses: the field's refresh() --
+    so regenerate() -- finds them again in place.  `raise_on` bool [T]: tiles on which a failed slot is an error (checked after
+    every search, one synchronisation); elsewhere `failed` counts them, read lazily.  `name`: the set of a GENERATED field's config
+    (find_flat_patches): the windows then follow the field's generator -- when a redraw changes what the table was resolved from (a
+    new config; another seed without a curriculum, which moves the sub-terrain types) the table is resolved again from the field's
+    config, checked and uploaded into the same device buffer before the search; it must keep its tile and patch counts."""
+
+    def __init__(self, hf: "DeviceHeightField", tiles, n_patches: int, seed: int = 0, stream: int = A.TS_PATCH, raise_on=None, labels=None,
+                 name: str | None = None, cfg=None):
+        import weakref
+
+        import numpy as np
+        self.lib = A.load()
+        self.hf, self.device = hf, hf.device
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("flat patches are found on a HIP device (device='cuda:N'); there is no CPU path")
+        table = np.ascontiguousarray(tiles)
+        if table.dtype.itemsize != C.sizeof(A.WlPatchTile) or table.ndim != 1 or not len(table):
+            raise ValueError("flat patches: `tiles` is a non-empty 1-d array of WlPatchTile rows (terrain_gen_cfg.PATCH_DTYPE)")
+        self.n_tiles, self.n_patches, self.seed = len(table), int(n_patches), int(seed) & (2 ** 64 - 1)
+        self.params = A.WlFlatPatchParams(self.n_tiles, self.n_patches, int(stream), 0, self.seed)
+        self.name, self._cfg = name, cfg
+        self._resolved_from = self._table_key(hf.generator) if name is not None else None
+        self.tiles = torch.zeros(self.n_tiles * C.sizeof(A.WlPatchTile), dtype=torch.uint8, device=self.device)
+        self._searched = torch.zeros(self.n_tiles, dtype=torch.bool, device=self.device)
+        self._set_table(table, raise_on, labels)
+        self.xy = torch.zeros(self.n_tiles, self.n_patches, 2, dtype=torch.float32, device=self.device)
+        self.z = torch.zeros(self.n_tiles, self.n_patches, dtype=torch.float32, device=self.device)
+        self.tries = torch.full((self.n_tiles, self.n_patches), -1, dtype=torch.int32, device=self.device)
+        hf._shared["patches"].append(weakref.ref(self))
+        self.find()
+
+    @staticmethod
+    def _table_key(cfg, sampling: bool = True):
+        """what a generator config's patch table depends on: every field but the seed -- and the seed too without a curriculum (it
+        then draws every tile's sub-terrain type); sampling=False: without the generator-level flat_patch_sampling"""
+        if cfg is None:
+            return None
+        fields = dict(vars(cfg))
+        seed = fields.pop("seed", None)
+        if not sampling:
+            fields.pop("flat_patch_sampling", None)
+        return repr(fields), (None if cfg.curriculum else seed)
+
+    def _set_table(self, table, raise_on, labels):
+        """validate a table on the host and put it into the device buffer the kernel reads, in place"""
+        import numpy as np
+        table = np.ascontiguousarray(table)
+        rc = self.lib.wl_flat_patch_check(C.byref(self.hf.struct), C.byref(self.params), table.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise ValueError(f"flat patches: {self.n_tiles} windows x {self.n_patches} patches are outside the finder's range on a field of "
+                             f"{self.hf.struct.nx} x {self.hf.struct.ny} points ({A.ERRORS.get(rc, rc)}; include/wheeledlab_amd_terrain.h: non-empty "
+                             f"windows, discs inside the lattice, radius <= {A.PATCH_MAX_RADIUS} cells, max_tries <= {A.PATCH_MAX_TRIES})")
+        self.table = table
+        self.raise_on = np.zeros(self.n_tiles, bool) if raise_on is None else np.asarray(raise_on, bool).reshape(self.n_tiles)
+        self.labels = list(labels) if labels is not None else [f"tile {t}" for t in range(self.n_tiles)]
+        self.tiles.copy_(torch.from_numpy(table.view(np.uint8).reshape(-1).copy()))
+        self._searched.copy_(torch.from_numpy(table["max_tries"] > 0))
+
+    def _follow_generator(self):
+        """resolve the table again when the field's generator config no longer is what it was resolved from: from the field's
+        config when that carries the set, else from the config the set was made with, moved to the field's seed"""
+        gen = self.hf.generator
+        if self.name is None or gen is None:
+            return
+        key = self._table_key(gen)
+        if key == self._resolved_from:
+            return
+        from .envs import terrain_gen_cfg as G
+        src = gen
+        if self.name not in G.patch_names(gen):
+            src = self._cfg.replace(seed=gen.seed)
+            if self._table_key(src, sampling=False) != self._table_key(gen, sampling=False):
+                raise ValueError(f"flat patches '{self.name}': the field was redrawn from a generator config that neither carries the "
+                                 "sampling nor equals, but for the seed, the one the patches were resolved from: put flat_patch_sampling "
+                                 "into the config handed to regenerate()")
+        table, n_patches, raise_on, labels = G.patch_table(src, self.name)
+        if len(table) != self.n_tiles or n_patches != self.n_patches:
+            raise ValueError(f"flat patches '{self.name}': the new generator config gives {len(table)} tiles x {n_patches} patches, the set "
+                             f"holds {self.n_tiles} x {self.n_patches} at fixed addresses -- build a new field and new patches instead")
+        self._set_table(table, raise_on, labels)
+        self._resolved_from = key
+
+    def find(self):
+        """search the field's codes as they are now, on the current stream, into the same buffers"""
+        self._follow_generator()
+        A.check(self.lib.wl_flat_patches(C.byref(self.hf.struct), C.byref(self.params), self.tiles.data_ptr(), self.xy.data_ptr(),
+                                         self.z.data_ptr(), self.tries.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                "wl_flat_patches")
+        if self.raise_on.any():
+            bad = ((self.tries < 0).any(1).cpu().numpy()) & self.raise_on
+            if bad.any():
+                t = int(bad.argmax())
+                raise ValueError(f"flat patches: {self.labels[t]} has no level ground for {int((self.tries[t] < 0).sum())} of its "
+                                 f"{self.n_patches} patches within {int(self.table['max_tries'][t])} tries (radius {int(self.table['radius_cells'][t])} "
+                                 f"cells, height difference {int(self.table['max_diff_codes'][t])} codes): relax the sampling or set on_failure='centre'")
+        return self
+
+    @property
+    def failed(self) -> int:
+        """slots of the searched tiles (max_tries > 0) that found nothing and hold their window's centre (one synchronisation)"""
+        return int(((self.tries < 0) & self._searched[:, None]).sum())
+
+    def positions(self) -> torch.Tensor:
+        """[T, P, 3]: (x, y, z) of every patch"""
+        return torch.cat([self.xy, self.z[..., None]], -1)
+
+
+def find_flat_patches(hf: DeviceHeightField, cfg, seed: int = 0, name: str = "init_pos", stream: int = A.TS_PATCH) -> FlatPatches:
+    """Flat patches on any field: `cfg` a FlatPatchSamplingCfg (or its fields as a dict) -- one window, the field itself -- or the
+    TerrainGeneratorCfg the field was generated from -- one window per tile, the patches it and its sub-terrains call `name`."""
+    from .envs import terrain_gen_cfg as G
+    if isinstance(cfg, G.TerrainGeneratorCfg):
+        geo = G.lattice(cfg)
+        if (geo["nx"], geo["ny"]) != (hf.struct.nx, hf.struct.ny):
+            raise ValueError(f"flat patches: the generator config gives {geo['nx']} x {geo['ny']} points, the field has {hf.struct.nx} x {hf.struct.ny}")
+        if hf.generator is not None and FlatPatches._table_key(hf.generator, False) != FlatPatches._table_key(cfg.replace(seed=hf.generator.seed), False):
+            raise ValueError("flat patches: `cfg` lays its tiles out otherwise than the generator config the field was last drawn from "
+                             "(they may differ in the seed and in the generator-level flat_patch_sampling alone)")
+        cfg = cfg.replace(seed=hf.generator.seed) if hf.generator is not None else cfg
+        table, P, raise_on, labels = G.patch_table(cfg, name)
+    else:
+        table, P, raise_on, labels = G.field_patch_table(cfg, hf.struct.nx, hf.struct.ny, hf.x0, hf.y0, hf.cell, hf.z_scale)
+    return FlatPatches(hf, table, P, seed, stream, raise_on, labels, *((name, cfg) if isinstance(cfg, G.TerrainGeneratorCfg) else ()))
+
+
 class TerrainLevels:
     """The terrain curriculum's device tables (WlTerrainLevels): `level` / `type` int32 [n] -- the row and column of every env's
     tile, LIVE: the step kernels move `level` at episode ends -- and `origins` float32 [rows * cols, 2], the tile centres.  Built
     from the TerrainGeneratorCfg of a generated field for envs env_offset .. env_offset + n of a world of `world_envs` envs (a
     shard holds its slice of the one big batch's assignment: envs.terrain_levels.initial_assignment), or from ready tables
-    (from_tables).  Hand it to ElevBatch(terrain_levels=...)."""
+    (from_tables).  Hand it to ElevBatch(terrain_levels=...).
+
+    With `flat_patches` (a FlatPatches of rows * cols tiles, P patches each) every patch is a VIRTUAL COLUMN: the tables the kernels
+    read have cols * P columns, `origins` IS the finder's xy buffer ([tile][k][2] = row-major [rows][cols * P][2]: found again in
+    place when the field is redrawn) and type[e] = column * P + slot, dealt on the device (wl_flat_patch_deal; redeal(epoch) deals
+    again).  The step kernels, unchanged, then spawn about a patch and move levels as before.  `tile_cols`, `tile_origins` and
+    `terrain_types` stay the real grid's."""
+
+    n_patches, patches, grid = 1, None, None
 
     def __init__(self, cfg, n_envs: int, device="cuda:0", env_offset: int = 0, world_envs: int | None = None,
-                 max_init_terrain_level: int | None = None, seed: int = 42):
+                 max_init_terrain_level: int | None = None, seed: int = 42, flat_patches: "FlatPatches | None" = None):
         from .envs import terrain_levels as TL
         level, types = TL.initial_assignment(cfg, n_envs, env_offset, world_envs, max_init_terrain_level, seed)
-        self._set(level, types, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device)
+        if flat_patches is None:
+            self._set(level, types, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device)
+        else:
+            self._set_patches(level, flat_patches, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device, env_offset, world_envs, seed)
         self.max_init_terrain_level = TL.clamp_max_init(cfg, max_init_terrain_level)
+
+    @classmethod
+    def on_patches(cls, flat_patches: "FlatPatches", n_envs: int, rows: int = 1, cols: int = 1, level=None, tile_origins=None,
+                   device="cuda:0", env_offset: int = 0, world_envs: int | None = None, seed: int = 42, grid=None):
+        """levels over a FlatPatches of rows * cols tiles without a generator config; the default is the one-row table of a field
+        that was not generated (a height array, a rasterised mesh): one tile, level 0 for good (the wrap rule keeps it there).  A
+        generated grid WITHOUT a curriculum is one row too -- rows = 1, cols = every tile, `grid` = (its rows, its columns): the
+        envs are spread over all tiles and stay where they are."""
+        import numpy as np
+        self = cls.__new__(cls)
+        self.grid = None if grid is None else (int(grid[0]), int(grid[1]))
+        o = np.zeros((int(rows) * int(cols), 2), np.float32) if tile_origins is None else tile_origins
+        self._set_patches(np.zeros(int(n_envs), np.int32) if level is None else level, flat_patches, o, rows, cols, device, env_offset,
+                          world_envs, seed)
+        self.max_init_terrain_level = int(rows) - 1
+        return self
+
+    def _set_patches(self, level, fp, tile_origins, rows, cols, device, env_offset, world_envs, seed):
+        n = len(level)
+        self.env_offset, self.world_envs, self.seed = int(env_offset), int(n if world_envs is None else world_envs), int(seed) & (2 ** 64 - 1)
+        if fp.n_tiles != int(rows) * int(cols) or fp.device != _canonical_device(device):
+            raise ValueError(f"flat patches of {fp.n_tiles} tiles on {fp.device} for {rows} x {cols} tiles on {_canonical_device(device)}")
+        self.patches, self.n_patches = fp, fp.n_patches
+        types = torch.zeros(n, dtype=torch.int32, device=fp.device)
+        self._set(level, types, fp.xy.view(-1, 2), int(rows), int(cols) * fp.n_patches, device, share_origins=True)
+        self.tile_cols = int(cols)
+        self.tile_origins = torch.as_tensor(tile_origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
+        self.redeal(0)
+
+    def redeal(self, epoch: int):
+        """deal every env a slot of its column again (wl_flat_patch_deal on the current stream: no host work, no synchronisation);
+        the slot counts from the env's next reset on.  Without flat patches: nothing to deal."""
+        if self.patches is None:
+            return
+        lib = A.load()
+        A.check(lib.wl_flat_patch_deal(self.type.shape[0], self.env_offset, self.world_envs, self.tile_cols, self.n_patches, int(epoch),
+                                       self.seed, self.type.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                "wl_flat_patch_deal")
+
+    @property
+    def terrain_types(self) -> torch.Tensor:
+        """[n] int32: the column of every env's tile on the real grid (type // P; `type` itself without flat patches)"""
+        if self.patches is None:
+            return self.type
+        col = torch.div(self.type, self.n_patches, rounding_mode="floor")
+        return col if self.grid is None else col % self.grid[1]
+
+    @property
+    def terrain_levels(self) -> torch.Tensor:
+        """[n] int32: the row of every env's tile on the real grid -- `level` itself (LIVE) unless a grid without a curriculum
+        was laid out as one row"""
+        return self.level if self.grid is None else torch.div(torch.div(self.type, self.n_patches, rounding_mode="floor"), self.grid[1],
+                                                               rounding_mode="floor")
+
+    @property
+    def grid_shape(self) -> tuple:
+        return (self.rows, self.tile_cols) if self.grid is None else self.grid
 
     @classmethod
     def from_tables(cls, level, types, origins, rows: int, cols: int, device="cuda:0"):
@@ -535,11 +740,13 @@ class TerrainLevels:
         self.max_init_terrain_level = int(rows) - 1
         return self
 
-    def _set(self, level, types, origins, rows, cols, device):
+    def _set(self, level, types, origins, rows, cols, device, share_origins: bool = False):
         self.device, self.rows, self.cols = _canonical_device(device), int(rows), int(cols)
         self.level = torch.as_tensor(level).to(self.device, torch.int32).contiguous().clone()
         self.type = torch.as_tensor(types).to(self.device, torch.int32).contiguous().clone()
-        self.origins = torch.as_tensor(origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
+        # (shared: the finder's own buffer, which it fills again in place)
+        self.origins = origins if share_origins else torch.as_tensor(origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
+        self.tile_cols, self.tile_origins = self.cols, self.origins
         if self.rows < 1 or self.cols < 1 or self.origins.shape[0] != self.rows * self.cols or self.level.shape != self.type.shape or self.level.dim() != 1:
             raise ValueError(f"terrain levels: {self.rows} x {self.cols} tiles need origins [{self.rows * self.cols}, 2] and level / type of one length")
         if self.level.numel() and (int(self.level.min()) < 0 or int(self.level.max()) >= self.rows or int(self.type.min()) < 0

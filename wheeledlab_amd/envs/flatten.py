@@ -378,11 +378,19 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     if round(p.scan_size / p.scan_res) + 1 != A.ELEV_SCAN_N or pat.size[0] != pat.size[1]:
         raise NotImplementedError(f"the fused height scan is {A.ELEV_SCAN_N} x {A.ELEV_SCAN_N} rays")
     # events + command
-    rt = _startup_events(cfg, su, ("reset_uniform",))
+    for name, term in _terms(cfg.events):     # an event by name (a command-line override): mdp.<name> must be an event term
+        if isinstance(term.func, str):
+            if getattr(getattr(mdp, term.func, None), "wl_event", None) is None:
+                raise ValueError(f"events.{name}.func = '{term.func}': not an event term of wheeledlab_amd.envs.mdp")
+            term.func = getattr(mdp, term.func)
+    rt = _startup_events(cfg, su, ("reset_uniform", "reset_from_terrain"))
+    from_terrain = rt is not None and getattr(rt.func, "wl_event", None) == "reset_from_terrain"
     if rt is not None:
         pr, vr = rt.params["pose_range"], rt.params["velocity_range"]
-        p.reset_xy, p.reset_yaw = _sym(pr["x"], "reset x"), _sym(pr["yaw"], "reset yaw")
-        if tuple(pr["x"]) != tuple(pr["y"]) or tuple(vr["x"]) != tuple(vr["y"]):
+        # (from the terrain: the patch is the position; a pose_range without x / y spawns ON it)
+        px, py = (pr.get("x", (0.0, 0.0)), pr.get("y", pr.get("x", (0.0, 0.0)))) if from_terrain else (pr["x"], pr["y"])
+        p.reset_xy, p.reset_yaw = _sym(px, "reset x"), _sym(pr.get("yaw", (0.0, 0.0)) if from_terrain else pr["yaw"], "reset yaw")
+        if tuple(px) != tuple(py) or tuple(vr["x"]) != tuple(vr["y"]):
             raise NotImplementedError("reset ranges must be equal in x and y")
         p.reset_vel[0], p.reset_vel[1] = vr["x"]
     p.reset_z = float(cfg.scene.terrain.height)
@@ -399,12 +407,60 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     terms = _terms(cfg.curriculum)
     level_terms = [name for name, term in terms if term.func is mdp.terrain_levels_goal]
     flat.curriculum = [(name, term) for name, term in terms if term.func is not mdp.terrain_levels_goal]
-    flat.extra.update(_terrain_source(cfg.scene.terrain, reset_range=None if level_terms else (-p.reset_xy, p.reset_xy)))
+    flat.extra.update(_terrain_source(cfg.scene.terrain, reset_range=None if level_terms or from_terrain else (-p.reset_xy, p.reset_xy)))
     if level_terms:
         from .terrain_levels import check_curriculum
         check_curriculum(flat.extra["terrain_generator"], p.reset_xy, p.cmd_xy)
         flat.extra["terrain_levels"] = dict(name=level_terms[0], max_init_terrain_level=getattr(cfg.scene.terrain, "max_init_terrain_level", None))
+    flat.extra["flat_patches"] = _flat_patch_source(cfg.scene.terrain, flat.extra["terrain_generator"], from_terrain, p.reset_xy, p.cmd_xy)
     return flat
+
+
+def _flat_patch_source(t, gen, from_terrain: bool, reset_xy: float, cmd_xy: float):
+    """The flat patches of an elevation scene: None, or dict(names, sampling, spawn) -- `names` every set to find (a generator's and
+    its sub-terrains' flat_patch_sampling; scene.terrain.flat_patch_sampling on a field that was not generated), `sampling` the
+    latter's {name: FlatPatchSamplingCfg}, `spawn` whether resets use "init_pos" (mdp.reset_root_state_from_terrain).  A spawn must
+    stay on its patch and the goal square about every possible patch on the lattice: each failure a ValueError naming the quantity."""
+    from . import terrain_gen_cfg as G
+    own = getattr(t, "flat_patch_sampling", None)
+    if gen is not None:
+        if own:
+            raise ValueError("scene.terrain.flat_patch_sampling is for height arrays and meshes: a generated terrain takes "
+                             "flat_patch_sampling on its TerrainGeneratorCfg or its sub-terrains")
+        names, sampling = G.patch_names(gen), None
+    else:
+        sampling = {k: G.as_patch_cfg(v) for k, v in (own or {}).items()}
+        names = sorted(sampling)
+    if from_terrain and "init_pos" not in names:
+        raise ValueError('reset_root_state_from_terrain needs "init_pos" flat patches: set flat_patch_sampling = {"init_pos": '
+                         "FlatPatchSamplingCfg(...)} on the terrain generator, a sub-terrain or scene.terrain")
+    if not names:
+        return None
+    if from_terrain:
+        if gen is not None:
+            table, _, _, _ = G.patch_table(gen, "init_pos")
+            subs, default = G.tile_names(gen), (gen.flat_patch_sampling or {}).get("init_pos")
+            radii = [G.patch_radius(G.as_patch_cfg(c)) for c in ((gen.sub_terrains[s].flat_patch_sampling or {}).get("init_pos") or default for s in subs)
+                     if c is not None]
+            geo = G.lattice(gen)
+            check_patch_goals(table, geo["nx"], geo["ny"], geo["cell"], cmd_xy)
+        else:
+            radii = [G.patch_radius(sampling["init_pos"])]
+        if math.sqrt(2.0) * float(reset_xy) > min(radii) + 1e-9:
+            raise ValueError(f"reset_xy {float(reset_xy):g} m: the corner of the spawn square, {math.sqrt(2.0) * float(reset_xy):g} m from the patch's "
+                             f"centre, leaves the patch (patch_radius {min(radii):g} m): lower pose_range x / y or raise patch_radius")
+    return dict(names=names, sampling=sampling, spawn=bool(from_terrain))
+
+
+def check_patch_goals(table, nx: int, ny: int, cell: float, cmd_xy: float):
+    """ValueError unless the goal square (+-cmd_xy) about every point of every window of `table` stays on the lattice -- the
+    one-point windows of tiles without a sampling included: cars spawn at their centre and draw goals about it"""
+    searched = table
+    for axis, lo, hi, n in (("x", "i_lo", "i_hi", nx), ("y", "j_lo", "j_hi", ny)):
+        if searched[lo].min() * cell - float(cmd_xy) < -1e-9 or searched[hi].max() * cell + float(cmd_xy) > (n - 1) * cell + 1e-9:
+            raise ValueError(f"cmd_xy {float(cmd_xy):g} m: the goal square about an outer flat patch leaves the lattice in {axis} (patch centres "
+                             f"span points {int(searched[lo].min())} .. {int(searched[hi].max())} of {n} at {cell:g} m): lower it, narrow "
+                             f"{axis}_range or widen border_width")
 
 
 def _terrain_source(t, reset_range=None, reset_range_y=None) -> dict:

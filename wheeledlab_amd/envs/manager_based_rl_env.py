@@ -243,7 +243,11 @@ class ManagerBasedRLEnv:
                 world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
                 levels = TerrainLevels(flat.extra["terrain_generator"], self.num_envs, self.device, rank * self.num_envs, world * self.num_envs,
                                        flat.extra["terrain_levels"]["max_init_terrain_level"], seed)
+            patches = {}
+            if flat.extra.get("flat_patches") is not None:
+                patches, levels = self._find_flat_patches(flat, levels, rank, seed)
             self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), terrain_levels=levels, **common)
+            self._batch.flat_patches = patches
         elif flat.task in ("visual", "visual_depth"):
             x = flat.extra
             kw = dict(trav_map=x["map"], spacing=x["spacing"], map_kwargs=dict(map_size=x["map_size"], env_size=x["env_size"],
@@ -284,7 +288,7 @@ class ManagerBasedRLEnv:
         self.extras = {}
         self.obs_buf = {}
         self._log_keys = episode_log_keys(self.reward_manager._slots, flat.termination_names)
-        if getattr(self._batch, "levels", None) is not None:      # the mean level: one reduction, run when the log is read
+        if getattr(self._batch, "levels", None) is not None and flat.extra.get("terrain_levels") is not None:      # the mean level: one reduction, run when the log is read
             self._log_keys["Curriculum/" + flat.extra["terrain_levels"]["name"]] = ("f", self._batch.levels.mean_level)
         # "torch terms run between the kernel launches": the fused collectors (one launch per rollout / writing straight
         # into the runner's storage) are off whenever any kind of custom term is registered
@@ -356,6 +360,48 @@ class ManagerBasedRLEnv:
         self.obs_buf = {"policy": self._with_custom_obs(self._batch.observe())}
         return self.obs_buf, self.extras
 
+    def _find_flat_patches(self, flat, levels, rank: int, seed: int):
+        """the scene's flat patches (flatten._flat_patch_source), found on the device: -> ({name: FlatPatches}, the levels tables).
+        With spawn patches the tables carry "init_pos" as virtual columns: the curriculum's own grid, a generated grid without a
+        curriculum as one row of all its tiles, any other field as one tile."""
+        import zlib
+
+        from ..core import DeviceHeightField, TerrainLevels, find_flat_patches
+        from . import terrain_levels as TL
+        from .flatten import check_patch_goals
+        spec, gen = flat.extra["flat_patches"], flat.extra.get("terrain_generator")
+        hf = flat.extra.get("heightfield")
+        if not isinstance(hf, DeviceHeightField):      # the field the batch will share (built here so that the patches live on it)
+            from ..terrain import synthetic_heightfield
+            hf = flat.extra["heightfield"] = DeviceHeightField(hf if hf is not None else synthetic_heightfield(), self.device)
+        found = {}
+        for name in spec["names"]:
+            # one key per name: sets with equal sampling must not coincide ("init_pos" keeps the env's seed)
+            key = seed if name == "init_pos" else (seed & 0xFFFFFFFF) | (zlib.crc32(name.encode()) << 32)
+            found[name] = find_flat_patches(hf, gen if gen is not None else spec["sampling"][name], key, name)
+        if not spec["spawn"]:
+            return found, levels
+        fp = found["init_pos"]
+        world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
+        where = dict(device=self.device, env_offset=rank * self.num_envs, world_envs=world * self.num_envs, seed=seed)
+        if levels is not None:
+            levels = TerrainLevels(gen, self.num_envs, max_init_terrain_level=flat.extra["terrain_levels"]["max_init_terrain_level"],
+                                   flat_patches=fp, **where)
+        elif gen is not None:
+            levels = TerrainLevels.on_patches(fp, self.num_envs, 1, fp.n_tiles, tile_origins=TL.tile_origins(gen),
+                                              grid=(int(gen.num_rows), int(gen.num_cols)), **where)
+        else:
+            check_patch_goals(fp.table, hf.struct.nx, hf.struct.ny, hf.cell, flat.params.cmd_xy)
+            levels = TerrainLevels.on_patches(fp, self.num_envs, **where)
+        return found, levels
+
+    def redeal_patches(self, epoch: int):
+        """deal every env another of its tile's spawn patches (core.TerrainLevels.redeal: one launch, no synchronisation); it counts
+        from the env's next reset on.  Nothing without spawn patches."""
+        levels = getattr(self._batch, "levels", None)
+        if levels is not None:
+            levels.redeal(int(epoch))
+
     def regenerate_terrain(self, seed=None):
         """Draw the procedural terrain again (scene.terrain.terrain_type = "generator") under `seed` -- None: the current seed + 1
         -- in place on the device (core.DeviceHeightField.regenerate), then reset every env: the cars would otherwise sit inside
@@ -363,7 +409,9 @@ class ManagerBasedRLEnv:
         hf = getattr(self._batch, "hf", None)
         if hf is None or hf.generator is None:
             raise ValueError('regenerate_terrain needs a generated terrain: scene.terrain.terrain_type = "generator"')
-        hf.regenerate(int(hf.generator.seed) + 1 if seed is None else int(seed))
+        hf.regenerate(int(hf.generator.seed) + 1 if seed is None else int(seed))      # (finds the field's flat patches again, in place)
+        self._patch_epoch = getattr(self, "_patch_epoch", 0) + 1
+        self.redeal_patches((1 << 32) + self._patch_epoch)                            # (epochs apart from the training loop's iterations)
         return self.reset()
 
     def step(self, action: torch.Tensor):

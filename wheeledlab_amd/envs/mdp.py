@@ -388,6 +388,16 @@ def reset_root_state_uniform(env, env_ids, pose_range, velocity_range, asset_cfg
     env._batch.reset(mask)
 
 
+@_event("reset_from_terrain")
+def reset_root_state_from_terrain(env, env_ids, pose_range, velocity_range, asset_cfg=_ROBOT):   # isaaclab mdp.events
+    """spawn on one of the terrain's "init_pos" flat patches (scene.terrain.flat_patches: FlatPatchSamplingCfg on the generator, a
+    sub-terrain or scene.terrain): the patch is the env's slot of its tile, dealt on the device; pose_range["x"] / ["y"] (default 0)
+    spread the spawn about it, ["yaw"] turns it.  The goal is drawn about the same patch; "target" patches are not consumed."""
+    mask = torch.zeros(env.num_envs, dtype=torch.uint8, device=env.device)
+    mask[env_ids] = 1
+    env._batch.reset(mask)
+
+
 # =====================================================================================================================
 # Visual task terms (reference: wheeledlab_tasks/visual/mushr_visual_env_cfg.py, mdp_sensors/observations.py)
 # =====================================================================================================================

@@ -413,7 +413,9 @@ class LidarView:
 class TerrainLevelsView:
     """`env.scene.terrain` of an env that carries terrain levels: the terrain's config (every attribute of it reads through) plus
     IsaacLab's TerrainImporter tensors -- `terrain_levels` / `terrain_types` int32 [n], LIVE (the tensors the step kernels read and
-    write), `terrain_origins` [rows, cols, 3] (tile centres, z = the terrain's height there) and `env_origins` [n, 3]."""
+    write), `terrain_origins` [rows, cols, 3] (tile centres, z = the terrain's height there) and `env_origins` [n, 3].  With flat
+    patches (core.FlatPatches): `flat_patches[name]` [rows, cols, P, 3], every patch's (x, y, z) as the device found it;
+    `terrain_types` is then the tile's column (type // P) and the origins stay the tile centres."""
 
     def __init__(self, cfg, batch):
         self.__dict__.update(_cfg=cfg, _b=batch)
@@ -424,29 +426,46 @@ class TerrainLevelsView:
     def __setattr__(self, name, value):
         setattr(self._cfg, name, value)
 
+    def _levels(self, what: str):
+        """the batch's level tables; without them (patches that no reset term spawns on, no terrain-levels term) the importer's per-env
+        tensors do not exist"""
+        lv = self._b.levels
+        if lv is None:
+            # (not an AttributeError: __getattr__ would take over and report the config's missing attribute instead)
+            raise RuntimeError(f"scene.terrain.{what}: this env carries no terrain levels -- its flat patches are exposed (flat_patches) but "
+                                 "no reset term spawns on them (mdp.reset_root_state_from_terrain) and there is no terrain_levels curriculum term")
+        return lv
+
+    @property
+    def flat_patches(self):
+        lv, gen = self._b.levels, self._b.hf.generator
+        shape = lv.grid_shape if lv is not None else (int(gen.num_rows), int(gen.num_cols)) if gen is not None else (1, 1)
+        return {name: fp.positions().reshape(*shape, fp.n_patches, 3) for name, fp in getattr(self._b, "flat_patches", {}).items()}
+
     @property
     def terrain_levels(self):
-        return self._b.levels.level
+        return self._levels("terrain_levels").terrain_levels
 
     @property
     def terrain_types(self):
-        return self._b.levels.type
+        return self._levels("terrain_types").terrain_types
 
     @property
     def terrain_origins(self):
-        lv, hf = self._b.levels, self._b.hf
-        u, v = (lv.origins[:, 0] - hf.x0) / hf.cell, (lv.origins[:, 1] - hf.y0) / hf.cell
+        lv, hf = self._levels("terrain_origins"), self._b.hf
+        o = lv.tile_origins
+        u, v = (o[:, 0] - hf.x0) / hf.cell, (o[:, 1] - hf.y0) / hf.cell
         ny, nx = hf.heights.shape
         i, j = u.floor().long().clamp(0, nx - 2), v.floor().long().clamp(0, ny - 2)
         fu, fv = (u - i).clamp(0, 1), (v - j).clamp(0, 1)
         h = hf.heights
         z = (h[j, i] * (1 - fu) + h[j, i + 1] * fu) * (1 - fv) + (h[j + 1, i] * (1 - fu) + h[j + 1, i + 1] * fu) * fv
-        return torch.cat([lv.origins, z[:, None]], 1).reshape(lv.rows, lv.cols, 3)
+        return torch.cat([o, z[:, None]], 1).reshape(*lv.grid_shape, 3)
 
     @property
     def env_origins(self):
-        lv = self._b.levels
-        return self.terrain_origins[lv.level.long(), lv.type.long()]
+        lv = self._levels("env_origins")
+        return self.terrain_origins[lv.terrain_levels.long(), lv.terrain_types.long()]
 
 
 class SceneView:
@@ -474,7 +493,7 @@ class SceneView:
             if isinstance(value, LidarCfg):
                 self.sensors[name] = LidarView(batch, value)
         self.terrain = getattr(cfg, "terrain", None)
-        if getattr(batch, "levels", None) is not None:
+        if getattr(batch, "levels", None) is not None or getattr(batch, "flat_patches", None):
             self.terrain = TerrainLevelsView(self.terrain, batch)
 
     def __getitem__(self, key):

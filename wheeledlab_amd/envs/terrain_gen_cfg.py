@@ -51,6 +51,7 @@ def _cells(metres: float, scale: float, lo: int = 0) -> int:
 @configclass
 class HfTerrainBaseCfg:
     proportion: float = 1.0
+    flat_patch_sampling: dict | None = None     # {name: FlatPatchSamplingCfg}: level ground to find on this sub-terrain's tiles
 
     def resolve(self, difficulty: float, gen) -> dict:       # -> the WlTerrainTile fields this type sets
         raise NotImplementedError
@@ -167,6 +168,7 @@ class TerrainGeneratorCfg:
     sub_terrains: dict = default_sub_terrains()     # (configclass deep-copies every default per instance: nothing is shared)
     difficulty_range: tuple = (0.0, 1.0)
     base_height: float = BASE_Z
+    flat_patch_sampling: dict | None = None     # {name: FlatPatchSamplingCfg} for every sub-terrain that sets none under that name
 
 
 def lattice(cfg) -> dict:
@@ -186,13 +188,23 @@ def lattice(cfg) -> dict:
                 seed=int(cfg.seed) & (2 ** 64 - 1), x0=-0.5 * nx * hs, y0=-0.5 * ny * hs, cell=hs, z_scale=vs)
 
 
-def tile_table(cfg) -> np.ndarray:
-    """-> WlTerrainTile [num_rows * num_cols] as a structured array (TILE_DTYPE; tile t = row * num_cols + col).
-    curriculum=True: a column's type follows the cumulative proportions (column c takes the first type whose cumulative share
-    exceeds (c + 1/2) / num_cols: the column's centre, which no rounding of the shares can put on a boundary) and the difficulty rises with the row: lo + (hi - lo) * (row + U) / num_rows, U in [0, 1) word 0 of
-    Philox(t, 0, 0, TS_TABLE).  Otherwise both are drawn per tile: difficulty lo + (hi - lo) * U, type from word 1 against the
-    cumulative proportions.  Each type then maps its ranges linearly in the difficulty to cells and codes (its `resolve`)."""
-    geo = lattice(cfg)
+def _tile_choices(cfg, geo, names, cum) -> list:
+    """(index into `names`, difficulty) of every tile, by tile_table's rule"""
+    d_lo, d_hi = (float(v) for v in cfg.difficulty_range)
+    rows, cols = geo["rows"], geo["cols"]
+    out = []
+    for r in range(rows):
+        for c in range(cols):
+            w = philox4x32(r * cols + c, 0, 0, TS_TABLE, geo["seed"])
+            if cfg.curriculum:
+                k, d = int(np.searchsorted(cum, (c + 0.5) / cols, side="right")), d_lo + (d_hi - d_lo) * (r + _u01(w[0])) / rows
+            else:
+                k, d = int(np.searchsorted(cum, _u01(w[1]), side="right")), d_lo + (d_hi - d_lo) * _u01(w[0])
+            out.append((min(k, len(names) - 1), d))
+    return out
+
+
+def _cumulative_proportions(cfg):
     names = list(cfg.sub_terrains)
     if not names:
         raise ValueError("TerrainGeneratorCfg.sub_terrains is empty")
@@ -201,19 +213,31 @@ def tile_table(cfg) -> np.ndarray:
         raise ValueError("sub-terrain proportions must be non-negative with a positive sum")
     cum = np.cumsum(prop / prop.sum())
     cum[-1] = 1.0
-    d_lo, d_hi = (float(v) for v in cfg.difficulty_range)
+    return names, cum
+
+
+def tile_names(cfg) -> list:
+    """the sub_terrains key of every tile (tile t = row * num_cols + col), by tile_table's rule"""
+    names, cum = _cumulative_proportions(cfg)
+    return [names[k] for k, _ in _tile_choices(cfg, lattice(cfg), names, cum)]
+
+
+def tile_table(cfg) -> np.ndarray:
+    """-> WlTerrainTile [num_rows * num_cols] as a structured array (TILE_DTYPE; tile t = row * num_cols + col).
+    curriculum=True: a column's type follows the cumulative proportions (column c takes the first type whose cumulative share
+    exceeds (c + 1/2) / num_cols: the column's centre, which no rounding of the shares can put on a boundary) and the difficulty rises with the row: lo + (hi - lo) * (row + U) / num_rows, U in [0, 1) word 0 of
+    Philox(t, 0, 0, TS_TABLE).  Otherwise both are drawn per tile: difficulty lo + (hi - lo) * U, type from word 1 against the
+    cumulative proportions.  Each type then maps its ranges linearly in the difficulty to cells and codes (its `resolve`)."""
+    geo = lattice(cfg)
+    names, cum = _cumulative_proportions(cfg)
     rows, cols = geo["rows"], geo["cols"]
     table = np.zeros(rows * cols, TILE_DTYPE)
     table["step_cells"], table["n_levels"], table["size_lo"], table["size_hi"] = 1, 1, 1, 1
+    choice = _tile_choices(cfg, geo, names, cum)
     for r in range(rows):
         for c in range(cols):
             t = r * cols + c
-            w = philox4x32(t, 0, 0, TS_TABLE, geo["seed"])
-            if cfg.curriculum:
-                k, d = int(np.searchsorted(cum, (c + 0.5) / cols, side="right")), d_lo + (d_hi - d_lo) * (r + _u01(w[0])) / rows
-            else:
-                k, d = int(np.searchsorted(cum, _u01(w[1]), side="right")), d_lo + (d_hi - d_lo) * _u01(w[0])
-            k = min(k, len(names) - 1)
+            k, d = choice[t]
             for key, val in cfg.sub_terrains[names[k]].resolve(d, cfg).items():
                 table[key][t] = val
             table["difficulty"][t] = d
@@ -246,3 +270,135 @@ def check_covers(cfg, x_range, y_range=None, what: str = "the task's reset squar
         if lo > want_lo + 1e-9 or hi < want_hi - 1e-9:
             raise ValueError(f"the generated terrain spans {axis} in [{lo:g}, {hi:g}] m and does not cover {what}, "
                              f"[{want_lo:g}, {want_hi:g}] m: raise num_rows / num_cols, size or border_width")
+
+
+# ---- flat patches: level ground to spawn on (include/wheeledlab_amd_terrain.h WlPatchTile; csrc/wl_flat_patch.hip) -----------------
+
+PATCH_DTYPE = np.dtype([(n, np.int32, (2,) if n == "pad" else ()) for n, _ in A.WlPatchTile._fields_])
+assert PATCH_DTYPE.itemsize == 48
+_CODE_LIMIT = 2 ** 30      # z bounds beyond every 16-bit code: "no bound"
+
+
+@configclass
+class FlatPatchSamplingCfg:
+    """IsaacLab's isaaclab.terrains.FlatPatchSamplingCfg: `num_patches` points per tile about which the ground within `patch_radius`
+    metres (a list: the largest) varies by at most `max_height_diff` metres and lies within `z_range`; centres within x_range /
+    y_range metres of the tile's centre.  z_range is measured from the generator's base_height (from z = 0 on a field that was
+    not generated).  Ours: `max_tries` attempts per patch (IsaacLab's loop runs a fixed count and raises) and `on_failure` -- "centre":
+    a slot without an accepted attempt takes the centre of its window and is counted (FlatPatches.failed); "raise": a ValueError
+    that names the tile."""
+    num_patches: int = 8
+    patch_radius: float | list = 0.15
+    x_range: tuple = (-1e6, 1e6)
+    y_range: tuple = (-1e6, 1e6)
+    z_range: tuple = (-1e6, 1e6)
+    max_height_diff: float = 0.02
+    max_tries: int = 4096
+    on_failure: str = "centre"
+
+
+def as_patch_cfg(c) -> FlatPatchSamplingCfg:
+    """a FlatPatchSamplingCfg from itself or from its fields as a dict (what a command-line override gives), validated"""
+    if isinstance(c, dict):
+        c = FlatPatchSamplingCfg(**c)
+    if not isinstance(c, FlatPatchSamplingCfg):
+        raise ValueError(f"flat_patch_sampling entries are FlatPatchSamplingCfg (or its fields as a dict), got {type(c).__name__}")
+    r = patch_radius(c)
+    if int(c.num_patches) < 1:
+        raise ValueError(f"FlatPatchSamplingCfg.num_patches {c.num_patches}: at least 1")
+    if not (math.isfinite(r) and r >= 0):
+        raise ValueError(f"FlatPatchSamplingCfg.patch_radius {c.patch_radius}: non-negative and finite")
+    if not (math.isfinite(float(c.max_height_diff)) and float(c.max_height_diff) >= 0):
+        raise ValueError(f"FlatPatchSamplingCfg.max_height_diff {c.max_height_diff}: non-negative and finite")
+    if not 0 <= int(c.max_tries) <= A.PATCH_MAX_TRIES:
+        raise ValueError(f"FlatPatchSamplingCfg.max_tries {c.max_tries}: 0 .. {A.PATCH_MAX_TRIES}")
+    if c.on_failure not in ("centre", "raise"):
+        raise ValueError(f"FlatPatchSamplingCfg.on_failure '{c.on_failure}': 'centre' or 'raise'")
+    return c
+
+
+def patch_radius(c) -> float:
+    r = c.patch_radius
+    return float(max(r)) if isinstance(r, (list, tuple)) else float(r)
+
+
+def resolve_patch_tile(c, cell: float, z_scale: float, extent, centre, z_base: float = 0.0, what: str = "the field") -> dict:
+    """The WlPatchTile fields of one window, in float64: `extent` = (i0, i1, j0, j1), the inclusive lattice rectangle the patch DISCS
+    may touch (a tile, or the whole field); `centre` = (xc, yc) in LATTICE units (metres from lattice point (0, 0) over the cell),
+    what x_range / y_range are measured from.  radius_cells = ceil(r / cell - 1e-9) rounds the radius UP to whole cells, so the
+    tested disc of lattice points covers the metric one; radius2 = floor((r / cell)^2 + 1e-9); max_diff_codes = floor(d / z_scale +
+    1e-9).  The window of patch centres is the extent inset by radius_cells, cut to the ranges."""
+    c = as_patch_cfg(c)
+    q = patch_radius(c) / cell
+    rc, r2 = int(math.ceil(q - 1e-9)), int(math.floor(q * q + 1e-9))
+    if rc > A.PATCH_MAX_RADIUS:
+        raise ValueError(f"patch_radius {patch_radius(c):g} m is {rc} cells of {cell:g} m: at most {A.PATCH_MAX_RADIUS}")
+    i0, i1, j0, j1 = extent
+    lo, hi = [], []
+    for a0, a1, mid, rng, axis in ((i0, i1, centre[0], c.x_range, "x"), (j0, j1, centre[1], c.y_range, "y")):
+        w_lo = max(a0 + rc, int(math.ceil(mid + float(rng[0]) / cell - 1e-9)))
+        w_hi = min(a1 - rc, int(math.floor(mid + float(rng[1]) / cell + 1e-9)))
+        if w_lo > w_hi:
+            raise ValueError(f"flat patches on {what}: no patch centre is left in {axis} (points {a0} .. {a1} inset by the radius of "
+                             f"{rc} cells, cut to {axis}_range {tuple(rng)}): lower patch_radius or widen the range")
+        lo.append(w_lo)
+        hi.append(w_hi)
+    z = [(z_base + float(v)) / z_scale for v in c.z_range]
+    return dict(i_lo=lo[0], i_hi=hi[0], j_lo=lo[1], j_hi=hi[1], radius_cells=rc, radius2=r2,
+                max_diff_codes=min(int(math.floor(float(c.max_height_diff) / z_scale + 1e-9)), _CODE_LIMIT),
+                z_lo_code=int(max(-_CODE_LIMIT, min(_CODE_LIMIT, math.ceil(z[0] - 1e-9)))),
+                z_hi_code=int(max(-_CODE_LIMIT, min(_CODE_LIMIT, math.floor(z[1] + 1e-9)))), max_tries=int(c.max_tries))
+
+
+def patch_names(cfg) -> list:
+    """every name under which the generator or one of its sub-terrains asks for flat patches, sorted"""
+    names = set(cfg.flat_patch_sampling or ())
+    for s in cfg.sub_terrains.values():
+        names |= set(s.flat_patch_sampling or ())
+    return sorted(names)
+
+
+def patch_table(cfg, name: str):
+    """-> (WlPatchTile [rows * cols] as a structured array, num_patches, raise_on bool [rows * cols], labels): the windows of the
+    patches called `name` on every tile of a generated grid.  A tile's sampling is its sub-terrain's flat_patch_sampling[name], else
+    the generator's; a tile with neither gets max_tries = 0 and a window holding its centre alone: every slot takes the centre.
+    Every sampling under one name must ask for the same num_patches (one table, one stride)."""
+    geo = lattice(cfg)
+    subs = tile_names(cfg)
+    default = (cfg.flat_patch_sampling or {}).get(name)
+    per_tile = [((cfg.sub_terrains[s].flat_patch_sampling or {}).get(name) or default) for s in subs]
+    per_tile = [None if c is None else as_patch_cfg(c) for c in per_tile]
+    counts = sorted({int(c.num_patches) for c in per_tile if c is not None})
+    if not counts:
+        raise ValueError(f"no flat_patch_sampling named '{name}' on the generator or any of its sub-terrains")
+    if len(counts) > 1:
+        raise ValueError(f"flat patches '{name}': num_patches differs between sub-terrains ({counts}); one table needs one count")
+    rows, cols, tnx, tny, b = geo["rows"], geo["cols"], geo["tile_nx"], geo["tile_ny"], geo["border"]
+    table = np.zeros(rows * cols, PATCH_DTYPE)
+    raise_on, labels = np.zeros(rows * cols, bool), []
+    for r in range(rows):
+        for c in range(cols):
+            t = r * cols + c
+            labels.append(f"tile {t} (row {r}, column {c}, '{subs[t]}')")
+            extent = (b + r * tnx, b + (r + 1) * tnx - 1, b + c * tny, b + (c + 1) * tny - 1)
+            centre = (b + (r + 0.5) * tnx, b + (c + 0.5) * tny)        # where envs.terrain_levels.tile_origins puts the tile's origin
+            if per_tile[t] is None:
+                fields = dict(i_lo=int(centre[0]), i_hi=int(centre[0]), j_lo=int(centre[1]), j_hi=int(centre[1]), z_lo_code=-_CODE_LIMIT,
+                              z_hi_code=_CODE_LIMIT)
+            else:
+                fields = resolve_patch_tile(per_tile[t], geo["cell"], geo["z_scale"], extent, centre, float(cfg.base_height), labels[-1])
+                raise_on[t] = per_tile[t].on_failure == "raise"
+            for key, val in fields.items():
+                table[key][t] = val
+    return table, counts[0], raise_on, labels
+
+
+def field_patch_table(c, nx: int, ny: int, x0: float, y0: float, cell: float, z_scale: float):
+    """the one-tile table of a field that was not generated (a height array, a rasterised mesh): the window is the field inset by
+    the radius, cut to x_range / y_range in WORLD metres; z_range from z = 0.  Same return as patch_table."""
+    c = as_patch_cfg(c)
+    fields = resolve_patch_tile(c, cell, z_scale, (0, int(nx) - 1, 0, int(ny) - 1), (-float(x0) / cell, -float(y0) / cell), 0.0, "the field")
+    table = np.zeros(1, PATCH_DTYPE)
+    for key, val in fields.items():
+        table[key][0] = val
+    return table, int(c.num_patches), np.array([c.on_failure == "raise"]), ["the field"]

@@ -50,6 +50,7 @@ class ElevationTerrainImporterCfg(TerrainImporterCfg):
     mesh_path = None                   # Wavefront OBJ of the terrain mesh (z up, metres); exclusive with `heightfield`
     mesh_cell = 0.05                   # lattice spacing (m) the mesh is rasterised at
     terrain_generator = None           # envs.terrain_gen_cfg.TerrainGeneratorCfg, used with terrain_type = "generator" (exclusive too)
+    flat_patch_sampling = None         # {name: envs.terrain_gen_cfg.FlatPatchSamplingCfg} on a height array or mesh (a generator carries its own)
     max_init_terrain_level = None      # terrain levels (a CurrTerm of mdp.terrain_levels_goal): envs start on rows 0 .. this; None: any row
     physics_material = RigidBodyMaterialCfg(friction_combine_mode="multiply", restitution_combine_mode="multiply",
                                             static_friction=1.0, dynamic_friction=1.0)
