@@ -49,7 +49,7 @@ def terrain_resampler(env, interval: int):
     policy that memorises one field.  None for K = 0."""
     if int(interval or 0) <= 0:
         return None
-    hf = getattr(env._batch, "hf", None)
+    hf = env._batch.hf
     if hf is None or hf.generator is None:
         raise ValueError('train.terrain_resample_interval needs env.scene.terrain.terrain_type = "generator"')
     base_seed, done = int(hf.generator.seed), [0]
@@ -67,7 +67,7 @@ def patch_redealer(env, interval: int, then=None):
     """`train.patch_redeal_interval=K` (default 1): every K iterations every env is dealt another of its tile's spawn patches (flat
     patches with mdp.reset_root_state_from_terrain; one launch, nothing is reset).  `then`: the hook to run after it (the terrain
     resampler).  None when there is nothing to deal and nothing to chain."""
-    levels = getattr(env._batch, "levels", None)
+    levels = env._batch.levels
     if int(interval or 0) <= 0 or levels is None or levels.patches is None:
         return then
     done = [0]

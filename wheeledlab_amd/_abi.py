@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+
 WL_ABI_VERSION = 24
 WL_ABI_REVISION = 1     # layout changes inside the ABI version (1: WlElevParams.levels)
 WL_MAX_REW_TERMS = 8
@@ -379,8 +381,7 @@ def load(path: str | None = None):
     path = path or LIB_PATH
     # PyTorch (the owner of the HBM allocations and streams we are handed) bundles its own libamdhip64.so with the same
     # SONAME as /opt/rocm's.  It must be in the process BEFORE our library is dlopen'ed so that both bind to ONE HIP
-    # runtime; the other order gives two runtimes and every launch on torch memory fails.
-    import torch  # noqa: F401
+    # runtime; the other order gives two runtimes and every launch on torch memory fails.  (This module imports torch.)
     if not os.path.exists(path):
         raise HipExtensionMissing(
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -410,6 +411,11 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has obsnorm version {lib.wl_obsnorm_version()}, python expects {WL_OBSNORM_VERSION}: rebuild")
     _lib = lib
     return lib
+
+
+def stream(device):
+    """the current stream of `device` as the hipStream_t argument of every launch"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def check(rc: int, what: str):

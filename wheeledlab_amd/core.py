@@ -1,4 +1,6 @@
-"""DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch: device buffers of one shard of a task's envs + thin calls into the C ABI.
+"""DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch: device buffers of one shard of a task's envs + thin calls into the C ABI,
+with what they share (_EnvBatch, ring_plan, the startup events).  The terrain a batch stands on is field.py's, the sensors that
+read it sensors.py's; their names are re-exported here, where they used to live.
 
 PyTorch is plumbing here: it owns the HBM allocations and the stream; every kernel is ours (csrc/*.hip).
 """
@@ -6,11 +8,17 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
+from types import MappingProxyType
 
 import torch
 
 from . import _abi as A
+from .field import (DeviceHeightField, FlatPatches, TerrainLevels, _canonical_device, _launch_terrain_generator,  # noqa: F401
+                    find_flat_patches, generate_heightfield, mesh_heightfield, pair_table)
 from .params import drift_params
+from .sensors import DepthCamera, LidarScanner, _cached_depth_camera, _field_key  # noqa: F401
+from .terrain import synthetic_heightfield
 
 
 def stadium_reference_poses(u: torch.Tensor, track_radius: float = 0.8, straight: float = 0.8) -> torch.Tensor:
@@ -46,243 +54,6 @@ def apply_startup_events(lib, bufs: "A.WlEnvBuffers", su, seed: int, stream, ran
     A.check(lib.wl_startup_randomize(C.byref(sp), C.byref(bufs), int(seed), stream), "wl_startup_randomize")
 
 
-def _canonical_device(device) -> torch.device:
-    """torch.device with its index filled in: 'cuda' and 'cuda:0' name the same GPU but compare unequal"""
-    d = torch.device(device)
-    if d.type == "cuda" and d.index is None:
-        d = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    return d
-
-
-def pair_table(codes: torch.Tensor) -> torch.Tensor:
-    """WlHeightField.pair as the header defines it: pair[j][i] = code[j][i] (low half) | code[min(j + 1, ny - 1)][i] << 16, int32
-    [ny, nx] (what wl_heightfield_pairs builds on the device; here in torch, for host-side fields and as the test's definition)"""
-    c = codes.to(torch.int32)
-    up = torch.cat([c[1:], c[-1:]], 0)
-    return ((c & 0xffff) | (up << 16)).to(torch.int32).contiguous()
-
-
-class DeviceHeightField:
-    """A heightfield resident on the device as the kernels read it (WlHeightField, ABI 21): 16-bit height codes [ny, nx] and the
-    vertical scale, z = code * z_scale.  `heightfield` is `(height, x0, y0, cell)` with float heights (quantised: terrain.
-    quantize_heights' rule, z_scale 2^-13 m unless the range needs more) or `(codes int16, x0, y0, cell, z_scale)`, arrays or
-    tensors; or another DeviceHeightField on the same device (shared).  `.heights`: the decoded fp32 grid -- exactly the values
-    every kernel sees (what tests hand to the oracle).  `outside_z`: the height of the plane beyond the grid (what the contact samplers
-    and the depth walk meet there); None keeps a shared field's own, else 0.  The field owns every table derived from the codes,
-    one of each for all its views: `pairs`, `heights` and `pyramid`, and every FlatPatches found on it; after editing `codes` in
-    place, refresh() them.  A field made by
-    generate_heightfield remembers its TerrainGeneratorCfg (`generator`) and can be drawn again in place: regenerate()."""
-
-    def __init__(self, heightfield, device, outside_z: float | None = None):
-        from .terrain import default_z_scale
-        self.device = _canonical_device(device)
-        if isinstance(heightfield, DeviceHeightField):
-            src = heightfield
-            if src.device != self.device:
-                raise ValueError(f"a DeviceHeightField lives on {src.device}; it cannot be shared with {self.device}")
-            self.codes, self.z_scale, self.heights, self.pairs = src.codes, src.z_scale, src.heights, src.pairs
-            self.x0, self.y0, self.cell = src.x0, src.y0, src.cell
-            self._shared = src._shared
-            outside_z = src.outside_z if outside_z is None else outside_z
-        else:
-            h, x0, y0, cell, *rest = heightfield
-            h = torch.as_tensor(h)
-            if h.dtype == torch.int16:
-                if not rest:
-                    raise ValueError("int16 height codes need their z_scale: (codes, x0, y0, cell, z_scale)")
-                self.codes, self.z_scale = h.contiguous().to(self.device), float(rest[0])
-            else:
-                h = h.to(self.device, torch.float64)
-                if not bool(torch.isfinite(h).all()):
-                    raise ValueError("heightfield with non-finite heights")
-                hmax = float(h.abs().max()) if h.numel() else 0.0
-                self.z_scale = float(rest[0]) if rest else default_z_scale(hmax)
-                if rest and math.isfinite(self.z_scale) and self.z_scale > 0 and hmax > 32767 * self.z_scale:
-                    # (the default scale widens itself; an explicit one that cannot hold the heights would flatten them silently)
-                    raise ValueError(f"heights up to {hmax:g} m do not fit 16-bit codes of z_scale {self.z_scale:g} m "
-                                     f"(+-{32767 * self.z_scale:g} m): pass a larger z_scale or none")
-                self.codes = torch.clamp(torch.round(h / self.z_scale), -32767, 32767).to(torch.int16).contiguous() if (
-                    math.isfinite(self.z_scale) and self.z_scale > 0) else torch.zeros((0,), dtype=torch.int16)
-            if not (math.isfinite(self.z_scale) and self.z_scale > 0) or self.codes.dim() != 2:
-                raise ValueError("heightfield: a [ny, nx] grid and a positive, finite z_scale")
-            self.x0, self.y0, self.cell = float(x0), float(y0), float(cell)
-            # the decoded grid and the row-pair table the height scan gathers from (WlHeightField.pair, ABI 23): filled by refresh()
-            self.heights = torch.empty(self.codes.shape, dtype=torch.float32, device=self.device)
-            self.pairs = torch.empty(self.codes.shape, dtype=torch.int32, device=self.device)
-            # what every view of these buffers shares: the generator's config (None: not generated), the bound pyramid (None: no ray cast yet)
-            # and the flat-patch sets found on it (weak references: a set lives as long as its owner)
-            self._shared = {"generator": None, "pyramid": None, "patches": []}
-        self.outside_z = float(0.0 if outside_z is None else outside_z)
-        ny, nx = self.codes.shape
-        self.struct = A.WlHeightField(self.codes.data_ptr(), nx, ny, self.x0, self.y0, self.cell, self.outside_z, self.z_scale, self.pairs.data_ptr())
-        if not isinstance(heightfield, DeviceHeightField):
-            self.refresh()
-
-    def _build(self, fn: str, table: torch.Tensor):
-        """a derived table from the codes, on the current stream"""
-        A.check(getattr(A.load(), fn)(C.byref(self.struct), table.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), fn)
-
-    @property
-    def pyramid(self) -> torch.Tensor:
-        """the bound pyramid the depth walk, the lidar scan and the viewer descend (float32 [wl_heightfield_pyramid_floats], packed
-        words): built at the first access, ONE for all views -- the builder reads no outside_z, the walks apply their view's own"""
-        if self._shared["pyramid"] is None:
-            if self.device.type != "cuda":
-                raise A.HipExtensionMissing("the bound pyramid needs a field on a HIP device (device='cuda:N'); there is no CPU path")
-            ny, nx = self.codes.shape
-            n_f = int(A.load().wl_heightfield_pyramid_floats(nx, ny))
-            if n_f <= 0:
-                raise A.WlError(f"heightfield of {nx} x {ny} points is outside the pyramid's range")
-            # (zeros: the builder leaves the padding between the levels alone -- equal fields give equal buffers, word for word)
-            pyr = torch.zeros(n_f, dtype=torch.float32, device=self.device)
-            self._build("wl_heightfield_build_pyramid", pyr)
-            self._shared["pyramid"] = pyr
-        return self._shared["pyramid"]
-
-    def refresh(self):
-        """Bring every derived table in line with `codes` as they are now, in place (no address moves): `pairs`, `heights` and, once
-        built, the pyramid.  Run it after editing `codes` in place: nothing detects such an edit, and the kernels read the tables."""
-        if self.device.type == "cuda":
-            self._build("wl_heightfield_pairs", self.pairs)
-        else:
-            self.pairs.copy_(pair_table(self.codes))
-        torch.mul(self.codes.to(torch.float32), torch.tensor(self.z_scale, dtype=torch.float32, device=self.device), out=self.heights)
-        if self._shared["pyramid"] is not None:
-            self._build("wl_heightfield_build_pyramid", self._shared["pyramid"])
-        if self._shared["patches"]:       # (no flat patches on the field: nothing is launched for them)
-            live = [r for r in self._shared["patches"] if r() is not None]
-            self._shared["patches"][:] = live
-            for r in live:
-                r().find()
-        return self
-
-    def as_tuple(self):
-        """(decoded heights, x0, y0, cell): the form the oracle's functions take"""
-        return self.heights, self.x0, self.y0, self.cell
-
-    @property
-    def generator(self):
-        """the TerrainGeneratorCfg the codes were last generated from (None: not a generated field)"""
-        return self._shared["generator"]
-
-    def regenerate(self, cfg_or_seed=None):
-        """Draw the field again IN PLACE from a TerrainGeneratorCfg, or from the current one under another seed (an int; None: the
-        same seed): new codes into the same device buffers (wl_terrain_generate), then refresh() -- every WlHeightField and pyramid
-        pointer a batch holds stays valid, and nothing that reads the field afterwards sees the old one.  The new config must give
-        the same lattice (points, placement, vertical scale).  Cars stand where they stood: reset them (env.regenerate_terrain does)."""
-        from .envs import terrain_gen_cfg as G
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("regenerate needs a field on a HIP device (device='cuda:N'); there is no CPU path")
-        cfg = self.generator
-        if isinstance(cfg_or_seed, int) and not isinstance(cfg_or_seed, bool):
-            if cfg is None:
-                raise ValueError("regenerate(seed) needs a generated field (core.generate_heightfield); pass a TerrainGeneratorCfg")
-            cfg = cfg.replace(seed=int(cfg_or_seed))
-        elif cfg_or_seed is not None:
-            cfg = cfg_or_seed
-        if cfg is None:
-            raise ValueError("regenerate() of a field that was not generated needs a TerrainGeneratorCfg")
-        geo = G.lattice(cfg)
-        ny, nx = self.codes.shape
-        if (geo["nx"], geo["ny"]) != (nx, ny) or (geo["x0"], geo["y0"], geo["cell"], geo["z_scale"]) != (self.x0, self.y0, self.cell, self.z_scale):
-            raise ValueError(f"regenerate: the config gives a lattice of {geo['nx']} x {geo['ny']} points at ({geo['x0']:g}, {geo['y0']:g}), "
-                             f"cell {geo['cell']:g} m, z_scale {geo['z_scale']:g} m; the field is {nx} x {ny} at ({self.x0:g}, {self.y0:g}), "
-                             f"cell {self.cell:g} m, z_scale {self.z_scale:g} m -- build a new field instead")
-        _launch_terrain_generator(cfg, self.codes)
-        self._shared["generator"] = cfg
-        # _field_key tells snapshots of this tensor (fields from a TUPLE holding it, which nobody refreshes) apart by its version
-        # counter, which a kernel write through data_ptr() does not touch: bump it by hand
-        torch.autograd.graph.increment_version(self.codes)
-        return self.refresh()
-
-
-def _launch_terrain_generator(cfg, codes: torch.Tensor):
-    """validate the config's descriptor table on the host (wl_terrain_gen_check), upload it and generate into `codes`"""
-    import numpy as np
-
-    from .envs import terrain_gen_cfg as G
-    lib = A.load()
-    p, table = G.gen_params(cfg), np.ascontiguousarray(G.tile_table(cfg))
-    if lib.wl_terrain_gen_check(C.byref(p), table.ctypes.data_as(C.c_void_p)) != 0:
-        raise ValueError("TerrainGeneratorCfg resolves to a grid or a sub-terrain outside the generator's range "
-                         "(include/wheeledlab_amd_terrain.h: sizes, level ranges within +-32767 codes, at most 64 obstacles)")
-    if codes.device.type != "cuda" or codes.dtype != torch.int16 or not codes.is_contiguous() or tuple(codes.shape) != (p.ny, p.nx):
-        raise ValueError(f"the generator writes contiguous int16 codes [{p.ny}, {p.nx}] on a HIP device")
-    tiles = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(codes.device)
-    A.check(lib.wl_terrain_generate(C.byref(p), tiles.data_ptr(), codes.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)), "wl_terrain_generate")
-
-
-def generate_heightfield(cfg, device="cuda:0", outside_z: float | None = None) -> DeviceHeightField:
-    """A procedural terrain (envs.terrain_gen_cfg.TerrainGeneratorCfg) generated on the device: the codes are allocated there and
-    written by wl_terrain_generate, the pair table by wl_heightfield_pairs -- nothing but the tile descriptors (64 bytes each)
-    crosses the bus.  -> a DeviceHeightField that ElevBatch / VisualDepthBatch / DepthCamera take as `heightfield`, and whose
-    regenerate() draws it again in place.  `outside_z`: the plane beyond the lattice, 0 unless given (as for every other field)."""
-    from .envs import terrain_gen_cfg as G
-    dev = _canonical_device(device)
-    if dev.type != "cuda":
-        raise A.HipExtensionMissing("generate_heightfield needs a HIP device (device='cuda:N'); there is no CPU path")
-    geo = G.lattice(cfg)
-    codes = torch.empty((geo["ny"], geo["nx"]), dtype=torch.int16, device=dev)
-    _launch_terrain_generator(cfg, codes)
-    hf = DeviceHeightField((codes, geo["x0"], geo["y0"], geo["cell"], geo["z_scale"]), dev, outside_z)
-    hf._shared["generator"] = cfg
-    return hf
-
-
-def mesh_heightfield(vertices, faces, cell: float, device="cuda:0", lattice=None, fill_z: float = 0.0, stats: dict | None = None):
-    """Rasterise a triangle mesh into a height lattice on the device (include/wheeledlab_amd_terrain.h: wl_mesh_raster): at each
-    lattice point the highest triangle whose xy projection contains it, `fill_z` where none does -- what a height scanner casting
-    straight down returns.  `vertices` float [V, 3] (world, metres) and `faces` int [F, 3], arrays or tensors; `lattice` = (x0, y0,
-    nx, ny), or None for the mesh's xy bounds on multiples of `cell`.  -> (heights float32 [ny, nx] on `device`, x0, y0, cell): the
-    tuple DeviceHeightField, ElevBatch(heightfield=...), VisualDepthBatch(heightfield=...) and scene.terrain.heightfield take.
-    Raises ValueError for faces with an index outside [0, V) or a non-finite vertex (one synchronisation: the launch's status).
-    `stats`: a dict that receives the launch's status words (invalid, binned, big, entries: WL_TERRAIN_STATUS_WORDS)."""
-    dev = _canonical_device(device)
-    v = torch.as_tensor(vertices).to(dev, torch.float32).reshape(-1, 3).contiguous()
-    f = torch.as_tensor(faces).to(dev).reshape(-1, 3)
-    if f.dtype.is_floating_point or f.dtype == torch.bool:
-        raise ValueError("faces must be integer vertex indices")
-    if f.numel() and (int(f.min()) < -2 ** 31 or int(f.max()) >= 2 ** 31):
-        raise ValueError("face indices beyond int32")
-    f = f.to(torch.int32).contiguous()
-    c32 = float(torch.tensor(cell, dtype=torch.float32))
-    if not (math.isfinite(c32) and c32 > 0):
-        raise ValueError("cell must be positive and finite")
-    if lattice is None:
-        if v.shape[0] == 0:
-            raise ValueError("an empty mesh has no bounds: pass lattice=(x0, y0, nx, ny)")
-        lo, hi = v[:, :2].double().min(0).values.tolist(), v[:, :2].double().max(0).values.tolist()
-        if not all(math.isfinite(a) for a in lo + hi):
-            raise ValueError("mesh with non-finite vertex coordinates")
-        x0, y0 = (float(torch.tensor(c32 * math.floor(a / c32), dtype=torch.float32)) for a in lo)
-        nx, ny = (max(2, math.ceil((b - a) / c32) + 1) for a, b in zip((x0, y0), hi))
-    else:
-        x0, y0, nx, ny = lattice
-        x0, y0, nx, ny = float(torch.tensor(x0, dtype=torch.float32)), float(torch.tensor(y0, dtype=torch.float32)), int(nx), int(ny)
-    lib = A.load()
-    if not math.isfinite(float(fill_z)):
-        raise ValueError("fill_z must be finite")
-    fits = max(abs(nx), abs(ny), f.shape[0], v.shape[0]) < 2 ** 31
-    need = lib.wl_mesh_raster_scratch_bytes(f.shape[0], nx, ny) if fits else -1
-    if need <= 0:
-        raise ValueError(f"a lattice of {nx} x {ny} points (2 .. {A.TERRAIN_MAX_SIDE - 1} each, at most 2^31 - 1 in all) for "
-                         f"{f.shape[0]} faces is out of range")
-    p = A.WlMeshRasterParams(x0, y0, c32, nx, ny, float(fill_z))
-    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    heights = torch.empty((ny, nx), dtype=torch.float32, device=dev)
-    status = torch.zeros(A.TERRAIN_STATUS_WORDS, dtype=torch.int32, device=dev)
-    A.check(lib.wl_mesh_raster(C.byref(p), v.data_ptr(), v.shape[0], f.data_ptr(), f.shape[0], scratch.data_ptr(), need, heights.data_ptr(),
-                               status.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "wl_mesh_raster")
-    words = status.tolist()
-    if stats is not None:
-        stats.update(zip(("invalid", "binned", "big", "entries"), words))
-    bad = words[0]
-    if bad:
-        raise ValueError(f"{bad} of {f.shape[0]} faces have a vertex index outside [0, {v.shape[0]}) or a non-finite vertex")
-    return heights, x0, y0, c32
-
-
 def ring_plan(step0: int, n_steps: int, slots: int):
     """How a persistent launch of `n_steps` steps from step `step0` runs on a metric ring of `slots` slots.  The launch folds all
     its steps into slot step0 % R and clears slot (step0 + n) % R for its successor.  Returns (segments, zero):
@@ -314,12 +85,16 @@ class _EnvBatch:
     pose_epoch = 0       # bumped by everything that moves cars WITHOUT advancing step_count (resets, plugin pose writes)
     _out_key = None
     _ring_split_warned = False
+    # the terrain a batch carries: a DeviceHeightField, a TerrainLevels, {name: FlatPatches} (ElevBatch and VisualDepthBatch set their own)
+    hf = levels = None
+    flat_patches = MappingProxyType({})
 
     def __init__(self, n_envs: int, device, params, seed: int, env_offset: int, metrics_slots: int, ref_table=None):
         self.lib = A.load()  # raises HipExtensionMissing -- no fallback
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise A.HipExtensionMissing(f"{type(self).__name__} needs a HIP device (device='cuda:N'); there is no CPU path")
+        self._stream = partial(A.stream, self.device)      # the current stream as every launch takes it
         self.n = int(n_envs)
         self.stride = ((self.n + 63) // 64) * 64
         self.p, self.seed, self.env_offset, self.step_count = params, int(seed), int(env_offset), 0
@@ -342,9 +117,6 @@ class _EnvBatch:
         self._out = A.WlStepOut(self.obs.data_ptr(), self.reward.data_ptr(), self.terminated.data_ptr(),
                                 self.truncated.data_ptr(), self.dones.data_ptr())
         self._args = (C.byref(self._bufs),)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     @property
     def metrics(self) -> torch.Tensor:
@@ -520,249 +292,6 @@ class DriftBatch(_EnvBatch):
         return storage
 
 
-class FlatPatches:
-    """Level ground found on a field by the device (wl_flat_patches; IsaacLab's TerrainImporter.flat_patches): for each of the
-    `tiles` windows (WlPatchTile rows as a structured array: envs.terrain_gen_cfg.patch_table / field_patch_table) `n_patches`
-    lattice points whose disc of neighbours is level.  `xy` float32 [T, P, 2], `z` float32 [T, P], `tries` int32 [T, P] (the accepted
-    attempt's index, -1: none -- the slot holds its window's centre) live on the device at fixed addresses: the field's refresh() --
-    so regenerate() -- finds them again in place.  `raise_on` bool [T]: tiles on which a failed slot is an error (checked after
-    every search, one synchronisation); elsewhere `failed` counts them, read lazily.  `name`: the set of a GENERATED field's config
-    (find_flat_patches): the windows then follow the field's generator -- when a redraw changes what the table was resolved from (a
-    new config; another seed without a curriculum, which moves the sub-terrain types) the table is resolved again from the field's
-    config, checked and uploaded into the same device buffer before the search; it must keep its tile and patch counts."""
-
-    def __init__(self, hf: "DeviceHeightField", tiles, n_patches: int, seed: int = 0, stream: int = A.TS_PATCH, raise_on=None, labels=None,
-                 name: str | None = None, cfg=None):
-        import weakref
-
-        import numpy as np
-        self.lib = A.load()
-        self.hf, self.device = hf, hf.device
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("flat patches are found on a HIP device (device='cuda:N'); there is no CPU path")
-        table = np.ascontiguousarray(tiles)
-        if table.dtype.itemsize != C.sizeof(A.WlPatchTile) or table.ndim != 1 or not len(table):
-            raise ValueError("flat patches: `tiles` is a non-empty 1-d array of WlPatchTile rows (terrain_gen_cfg.PATCH_DTYPE)")
-        self.n_tiles, self.n_patches, self.seed = len(table), int(n_patches), int(seed) & (2 ** 64 - 1)
-        self.params = A.WlFlatPatchParams(self.n_tiles, self.n_patches, int(stream), 0, self.seed)
-        self.name, self._cfg = name, cfg
-        self._resolved_from = self._table_key(hf.generator) if name is not None else None
-        self.tiles = torch.zeros(self.n_tiles * C.sizeof(A.WlPatchTile), dtype=torch.uint8, device=self.device)
-        self._searched = torch.zeros(self.n_tiles, dtype=torch.bool, device=self.device)
-        self._set_table(table, raise_on, labels)
-        self.xy = torch.zeros(self.n_tiles, self.n_patches, 2, dtype=torch.float32, device=self.device)
-        self.z = torch.zeros(self.n_tiles, self.n_patches, dtype=torch.float32, device=self.device)
-        self.tries = torch.full((self.n_tiles, self.n_patches), -1, dtype=torch.int32, device=self.device)
-        hf._shared["patches"].append(weakref.ref(self))
-        self.find()
-
-    @staticmethod
-    def _table_key(cfg, sampling: bool = True):
-        """what a generator config's patch table depends on: every field but the seed -- and the seed too without a curriculum (it
-        then draws every tile's sub-terrain type); sampling=False: without the generator-level flat_patch_sampling"""
-        if cfg is None:
-            return None
-        fields = dict(vars(cfg))
-        seed = fields.pop("seed", None)
-        if not sampling:
-            fields.pop("flat_patch_sampling", None)
-        return repr(fields), (None if cfg.curriculum else seed)
-
-    def _set_table(self, table, raise_on, labels):
-        """validate a table on the host and put it into the device buffer the kernel reads, in place"""
-        import numpy as np
-        table = np.ascontiguousarray(table)
-        rc = self.lib.wl_flat_patch_check(C.byref(self.hf.struct), C.byref(self.params), table.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise ValueError(f"flat patches: {self.n_tiles} windows x {self.n_patches} patches are outside the finder's range on a field of "
-                             f"{self.hf.struct.nx} x {self.hf.struct.ny} points ({A.ERRORS.get(rc, rc)}; include/wheeledlab_amd_terrain.h: non-empty "
-                             f"windows, discs inside the lattice, radius <= {A.PATCH_MAX_RADIUS} cells, max_tries <= {A.PATCH_MAX_TRIES})")
-        self.table = table
-        self.raise_on = np.zeros(self.n_tiles, bool) if raise_on is None else np.asarray(raise_on, bool).reshape(self.n_tiles)
-        self.labels = list(labels) if labels is not None else [f"tile {t}" for t in range(self.n_tiles)]
-        self.tiles.copy_(torch.from_numpy(table.view(np.uint8).reshape(-1).copy()))
-        self._searched.copy_(torch.from_numpy(table["max_tries"] > 0))
-
-    def _follow_generator(self):
-        """resolve the table again when the field's generator config no longer is what it was resolved from: from the field's
-        config when that carries the set, else from the config the set was made with, moved to the field's seed"""
-        gen = self.hf.generator
-        if self.name is None or gen is None:
-            return
-        key = self._table_key(gen)
-        if key == self._resolved_from:
-            return
-        from .envs import terrain_gen_cfg as G
-        src = gen
-        if self.name not in G.patch_names(gen):
-            src = self._cfg.replace(seed=gen.seed)
-            if self._table_key(src, sampling=False) != self._table_key(gen, sampling=False):
-                raise ValueError(f"flat patches '{self.name}': the field was redrawn from a generator config that neither carries the "
-                                 "sampling nor equals, but for the seed, the one the patches were resolved from: put flat_patch_sampling "
-                                 "into the config handed to regenerate()")
-        table, n_patches, raise_on, labels = G.patch_table(src, self.name)
-        if len(table) != self.n_tiles or n_patches != self.n_patches:
-            raise ValueError(f"flat patches '{self.name}': the new generator config gives {len(table)} tiles x {n_patches} patches, the set "
-                             f"holds {self.n_tiles} x {self.n_patches} at fixed addresses -- build a new field and new patches instead")
-        self._set_table(table, raise_on, labels)
-        self._resolved_from = key
-
-    def find(self):
-        """search the field's codes as they are now, on the current stream, into the same buffers"""
-        self._follow_generator()
-        A.check(self.lib.wl_flat_patches(C.byref(self.hf.struct), C.byref(self.params), self.tiles.data_ptr(), self.xy.data_ptr(),
-                                         self.z.data_ptr(), self.tries.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                "wl_flat_patches")
-        if self.raise_on.any():
-            bad = ((self.tries < 0).any(1).cpu().numpy()) & self.raise_on
-            if bad.any():
-                t = int(bad.argmax())
-                raise ValueError(f"flat patches: {self.labels[t]} has no level ground for {int((self.tries[t] < 0).sum())} of its "
-                                 f"{self.n_patches} patches within {int(self.table['max_tries'][t])} tries (radius {int(self.table['radius_cells'][t])} "
-                                 f"cells, height difference {int(self.table['max_diff_codes'][t])} codes): relax the sampling or set on_failure='centre'")
-        return self
-
-    @property
-    def failed(self) -> int:
-        """slots of the searched tiles (max_tries > 0) that found nothing and hold their window's centre (one synchronisation)"""
-        return int(((self.tries < 0) & self._searched[:, None]).sum())
-
-    def positions(self) -> torch.Tensor:
-        """[T, P, 3]: (x, y, z) of every patch"""
-        return torch.cat([self.xy, self.z[..., None]], -1)
-
-
-def find_flat_patches(hf: DeviceHeightField, cfg, seed: int = 0, name: str = "init_pos", stream: int = A.TS_PATCH) -> FlatPatches:
-    """Flat patches on any field: `cfg` a FlatPatchSamplingCfg (or its fields as a dict) -- one window, the field itself -- or the
-    TerrainGeneratorCfg the field was generated from -- one window per tile, the patches it and its sub-terrains call `name`."""
-    from .envs import terrain_gen_cfg as G
-    if isinstance(cfg, G.TerrainGeneratorCfg):
-        geo = G.lattice(cfg)
-        if (geo["nx"], geo["ny"]) != (hf.struct.nx, hf.struct.ny):
-            raise ValueError(f"flat patches: the generator config gives {geo['nx']} x {geo['ny']} points, the field has {hf.struct.nx} x {hf.struct.ny}")
-        if hf.generator is not None and FlatPatches._table_key(hf.generator, False) != FlatPatches._table_key(cfg.replace(seed=hf.generator.seed), False):
-            raise ValueError("flat patches: `cfg` lays its tiles out otherwise than the generator config the field was last drawn from "
-                             "(they may differ in the seed and in the generator-level flat_patch_sampling alone)")
-        cfg = cfg.replace(seed=hf.generator.seed) if hf.generator is not None else cfg
-        table, P, raise_on, labels = G.patch_table(cfg, name)
-    else:
-        table, P, raise_on, labels = G.field_patch_table(cfg, hf.struct.nx, hf.struct.ny, hf.x0, hf.y0, hf.cell, hf.z_scale)
-    return FlatPatches(hf, table, P, seed, stream, raise_on, labels, *((name, cfg) if isinstance(cfg, G.TerrainGeneratorCfg) else ()))
-
-
-class TerrainLevels:
-    """The terrain curriculum's device tables (WlTerrainLevels): `level` / `type` int32 [n] -- the row and column of every env's
-    tile, LIVE: the step kernels move `level` at episode ends -- and `origins` float32 [rows * cols, 2], the tile centres.  Built
-    from the TerrainGeneratorCfg of a generated field for envs env_offset .. env_offset + n of a world of `world_envs` envs (a
-    shard holds its slice of the one big batch's assignment: envs.terrain_levels.initial_assignment), or from ready tables
-    (from_tables).  Hand it to ElevBatch(terrain_levels=...).
-
-    With `flat_patches` (a FlatPatches of rows * cols tiles, P patches each) every patch is a VIRTUAL COLUMN: the tables the kernels
-    read have cols * P columns, `origins` IS the finder's xy buffer ([tile][k][2] = row-major [rows][cols * P][2]: found again in
-    place when the field is redrawn) and type[e] = column * P + slot, dealt on the device (wl_flat_patch_deal; redeal(epoch) deals
-    again).  The step kernels, unchanged, then spawn about a patch and move levels as before.  `tile_cols`, `tile_origins` and
-    `terrain_types` stay the real grid's."""
-
-    n_patches, patches, grid = 1, None, None
-
-    def __init__(self, cfg, n_envs: int, device="cuda:0", env_offset: int = 0, world_envs: int | None = None,
-                 max_init_terrain_level: int | None = None, seed: int = 42, flat_patches: "FlatPatches | None" = None):
-        from .envs import terrain_levels as TL
-        level, types = TL.initial_assignment(cfg, n_envs, env_offset, world_envs, max_init_terrain_level, seed)
-        if flat_patches is None:
-            self._set(level, types, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device)
-        else:
-            self._set_patches(level, flat_patches, TL.tile_origins(cfg), int(cfg.num_rows), int(cfg.num_cols), device, env_offset, world_envs, seed)
-        self.max_init_terrain_level = TL.clamp_max_init(cfg, max_init_terrain_level)
-
-    @classmethod
-    def on_patches(cls, flat_patches: "FlatPatches", n_envs: int, rows: int = 1, cols: int = 1, level=None, tile_origins=None,
-                   device="cuda:0", env_offset: int = 0, world_envs: int | None = None, seed: int = 42, grid=None):
-        """levels over a FlatPatches of rows * cols tiles without a generator config; the default is the one-row table of a field
-        that was not generated (a height array, a rasterised mesh): one tile, level 0 for good (the wrap rule keeps it there).  A
-        generated grid WITHOUT a curriculum is one row too -- rows = 1, cols = every tile, `grid` = (its rows, its columns): the
-        envs are spread over all tiles and stay where they are."""
-        import numpy as np
-        self = cls.__new__(cls)
-        self.grid = None if grid is None else (int(grid[0]), int(grid[1]))
-        o = np.zeros((int(rows) * int(cols), 2), np.float32) if tile_origins is None else tile_origins
-        self._set_patches(np.zeros(int(n_envs), np.int32) if level is None else level, flat_patches, o, rows, cols, device, env_offset,
-                          world_envs, seed)
-        self.max_init_terrain_level = int(rows) - 1
-        return self
-
-    def _set_patches(self, level, fp, tile_origins, rows, cols, device, env_offset, world_envs, seed):
-        n = len(level)
-        self.env_offset, self.world_envs, self.seed = int(env_offset), int(n if world_envs is None else world_envs), int(seed) & (2 ** 64 - 1)
-        if fp.n_tiles != int(rows) * int(cols) or fp.device != _canonical_device(device):
-            raise ValueError(f"flat patches of {fp.n_tiles} tiles on {fp.device} for {rows} x {cols} tiles on {_canonical_device(device)}")
-        self.patches, self.n_patches = fp, fp.n_patches
-        types = torch.zeros(n, dtype=torch.int32, device=fp.device)
-        self._set(level, types, fp.xy.view(-1, 2), int(rows), int(cols) * fp.n_patches, device, share_origins=True)
-        self.tile_cols = int(cols)
-        self.tile_origins = torch.as_tensor(tile_origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
-        self.redeal(0)
-
-    def redeal(self, epoch: int):
-        """deal every env a slot of its column again (wl_flat_patch_deal on the current stream: no host work, no synchronisation);
-        the slot counts from the env's next reset on.  Without flat patches: nothing to deal."""
-        if self.patches is None:
-            return
-        lib = A.load()
-        A.check(lib.wl_flat_patch_deal(self.type.shape[0], self.env_offset, self.world_envs, self.tile_cols, self.n_patches, int(epoch),
-                                       self.seed, self.type.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                "wl_flat_patch_deal")
-
-    @property
-    def terrain_types(self) -> torch.Tensor:
-        """[n] int32: the column of every env's tile on the real grid (type // P; `type` itself without flat patches)"""
-        if self.patches is None:
-            return self.type
-        col = torch.div(self.type, self.n_patches, rounding_mode="floor")
-        return col if self.grid is None else col % self.grid[1]
-
-    @property
-    def terrain_levels(self) -> torch.Tensor:
-        """[n] int32: the row of every env's tile on the real grid -- `level` itself (LIVE) unless a grid without a curriculum
-        was laid out as one row"""
-        return self.level if self.grid is None else torch.div(torch.div(self.type, self.n_patches, rounding_mode="floor"), self.grid[1],
-                                                               rounding_mode="floor")
-
-    @property
-    def grid_shape(self) -> tuple:
-        return (self.rows, self.tile_cols) if self.grid is None else self.grid
-
-    @classmethod
-    def from_tables(cls, level, types, origins, rows: int, cols: int, device="cuda:0"):
-        """level / types [n] integers in [0, rows) / [0, cols), origins [rows * cols, 2] metres"""
-        self = cls.__new__(cls)
-        self._set(level, types, origins, rows, cols, device)
-        self.max_init_terrain_level = int(rows) - 1
-        return self
-
-    def _set(self, level, types, origins, rows, cols, device, share_origins: bool = False):
-        self.device, self.rows, self.cols = _canonical_device(device), int(rows), int(cols)
-        self.level = torch.as_tensor(level).to(self.device, torch.int32).contiguous().clone()
-        self.type = torch.as_tensor(types).to(self.device, torch.int32).contiguous().clone()
-        # (shared: the finder's own buffer, which it fills again in place)
-        self.origins = origins if share_origins else torch.as_tensor(origins).to(self.device, torch.float32).reshape(-1, 2).contiguous().clone()
-        self.tile_cols, self.tile_origins = self.cols, self.origins
-        if self.rows < 1 or self.cols < 1 or self.origins.shape[0] != self.rows * self.cols or self.level.shape != self.type.shape or self.level.dim() != 1:
-            raise ValueError(f"terrain levels: {self.rows} x {self.cols} tiles need origins [{self.rows * self.cols}, 2] and level / type of one length")
-        if self.level.numel() and (int(self.level.min()) < 0 or int(self.level.max()) >= self.rows or int(self.type.min()) < 0
-                                   or int(self.type.max()) >= self.cols):
-            raise ValueError(f"terrain levels outside [0, {self.rows}) or types outside [0, {self.cols})")
-        self.struct = A.WlTerrainLevels(self.level.data_ptr(), self.type.data_ptr(), self.origins.data_ptr(), self.rows, self.cols)
-
-    def env_origins_xy(self) -> torch.Tensor:
-        """[n, 2]: the centre of every env's tile as the levels stand"""
-        return self.origins[self.level.long() * self.cols + self.type.long()]
-
-    def mean_level(self) -> torch.Tensor:
-        """0-dim device tensor: what the terrain_levels curriculum term reports"""
-        return self.level.float().mean()
-
-
 class ElevBatch(_EnvBatch):
     """n elevation-task envs on one GPU (same SoA state matrix; rows WL_S_CMD_* carry the goal command)."""
 
@@ -770,11 +299,12 @@ class ElevBatch(_EnvBatch):
     _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_elev_reset", "wl_elev_step", "wl_elev_rollout", "wl_elev_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params: A.WlElevParams | None = None, seed: int = 42,
-                 env_offset: int = 0, heightfield=None, metrics_slots: int = 1, startup=None, terrain_levels: TerrainLevels | None = None):
+                 env_offset: int = 0, heightfield=None, metrics_slots: int = 1, startup=None, terrain_levels: TerrainLevels | None = None,
+                 flat_patches=None):
         from .params import elev_params
-        from .terrain import synthetic_heightfield
         super().__init__(n_envs, device, params if params is not None else elev_params(), seed, env_offset, metrics_slots)
         self.set_terrain_levels(terrain_levels)
+        self.flat_patches = dict(flat_patches or {})
         self.hf = DeviceHeightField(heightfield if heightfield is not None else synthetic_heightfield(), self.device)
         self.height, self._hf = self.hf.heights, self.hf.struct       # the DECODED fp32 grid (what the kernels see); the ABI struct
         self._args = (C.byref(self._bufs), C.byref(self._hf))
@@ -899,7 +429,6 @@ class VisualDepthBatch(VisualBatch):
 
     def __init__(self, n_envs: int, device="cuda:0", params=None, seed: int = 42, env_offset: int = 0, trav_map=None,
                  spacing=(0.5, 0.5), metrics_slots: int = 1, startup=None, map_kwargs=None, heightfield=None, max_depth: float = 20.0):
-        from .terrain import synthetic_heightfield
         if trav_map is None and map_kwargs is None:
             map_kwargs = dict(map_size=(80, 80), env_size=(40, 40), sub_group_size=(20, 20), num_walkers=1)
         super().__init__(n_envs, device, params, seed, env_offset, trav_map, spacing, metrics_slots, startup, map_kwargs)
@@ -943,115 +472,3 @@ class VisualDepthBatch(VisualBatch):
         if heightfield is None:
             return self.camera.render(self, self.max_depth if max_depth is None else max_depth, out)
         return super().depth(heightfield, 20.0 if max_depth is None else max_depth, out)
-
-
-class DepthCamera:
-    """The visual task's pinhole camera rendering distance_to_image_plane against a heightfield (wl_visual_depth): its parameters
-    and a view of the field (`hf`: its own outside plane, the field's buffers and its one bound pyramid), renders the poses of ANY
-    batch (rows WL_S_PX.. / WL_S_QW.. of its state matrix).  Reference hook: mdp_sensors/observations.py:89-95; camera
-    visual/mushr_visual_env_cfg.py:230-246."""
-
-    IMG_H, IMG_W = 60, 80
-
-    def __init__(self, heightfield, device="cuda:0", params: A.WlVisualParams | None = None, outside_z: float | None = None):
-        from .params import visual_params
-        self.lib = A.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("DepthCamera needs a HIP device; there is no CPU path")
-        self.p = params if params is not None else visual_params()
-        self.hf = DeviceHeightField(heightfield, self.device, outside_z)     # a tuple (quantised here) or a batch's own `.hf` (shared)
-        self.height, self._hf = self.hf.heights, self.hf.struct
-        self._pyr = self.hf.pyramid.data_ptr()    # resolved once: the field rebuilds its pyramid in place (refresh), never moves it
-
-    _stream = _EnvBatch._stream
-    pyramid = property(lambda self: self.hf.pyramid)
-
-    def build_pyramid(self):
-        """the field's derived tables (the pyramid among them) from its codes as they are now"""
-        self.hf.refresh()
-
-    def render(self, batch, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
-        if out is None:
-            out = torch.empty(batch.n, self.IMG_H, self.IMG_W, dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == batch.n * self.IMG_H * self.IMG_W
-        A.check(self.lib.wl_visual_depth(C.byref(self.p), C.byref(batch._bufs), C.byref(self._hf), self._pyr,
-                                         float(max_depth), out.data_ptr(), self._stream()), "wl_visual_depth")
-        return out
-
-
-class LidarScanner:
-    """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
-    (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
-    field and pyramid come from the batch's cached DepthCamera, i.e. from the batch's DeviceHeightField (which owns the one pyramid).
-    render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
-    the terrain (what a miss reads in the scene is LidarData's business)."""
-
-    def __init__(self, cfg=None, device="cuda:0"):
-        from .envs.sensors_cfg import LidarCfg
-        self.lib = A.load()
-        self.device = _canonical_device(device)
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("LidarScanner needs a HIP device; there is no CPU path")
-        self.cfg = cfg = cfg if cfg is not None else LidarCfg()
-        dirs = cfg.pattern_cfg.directions()
-        self.n_beams = int(dirs.shape[0])
-        if not 1 <= self.n_beams <= A.LIDAR_MAX_BEAMS:
-            raise ValueError(f"a lidar pattern of {self.n_beams} beams (1 .. {A.LIDAR_MAX_BEAMS})")
-        self.beam_dirs = torch.as_tensor(dirs, dtype=torch.float32).contiguous().to(self.device)
-        self.max_range = float(cfg.max_range)
-        if not (math.isfinite(self.max_range) and self.max_range > 0):
-            raise ValueError(f"lidar max_range must be positive and finite, got {cfg.max_range}")
-        q = [float(v) for v in cfg.offset_rot]
-        qn = math.sqrt(sum(v * v for v in q))
-        if not (math.isfinite(qn) and qn > 0):
-            raise ValueError(f"lidar offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
-        self.params = A.WlLidarParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
-                                      self.n_beams, self.max_range, int(bool(cfg.attach_yaw_only)))
-        self._plane = None
-
-    _stream = _EnvBatch._stream
-
-    def camera_of(self, batch) -> DepthCamera:
-        """the terrain the batch's cars stand on, as CameraData does it: the visual-depth task's own camera, the elevation task's
-        heightfield, else the z = 0 plane (a 3 x 3 zero grid: beyond it the outside plane is z = 0 as well)"""
-        if getattr(batch, "camera", None) is not None:
-            return batch.camera
-        if hasattr(batch, "hf"):
-            return _cached_depth_camera(batch, batch.hf)
-        if self._plane is None:       # one tensor per scanner: the batch's camera cache keys on it
-            self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
-        return _cached_depth_camera(batch, self._plane)
-
-    def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
-        """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
-        cam = camera if camera is not None else self.camera_of(batch)
-        if out is None:
-            out = torch.empty(batch.n, self.n_beams, dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch.n, self.n_beams)
-        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr,
-                                       self.beam_dirs.data_ptr(), out.data_ptr(), self._stream()), "wl_lidar_scan")
-        return out
-
-
-def _field_key(heightfield) -> tuple:
-    """What tells one `heightfield` argument from another (pure: needs no device).  A DeviceHeightField: its shared buffers' identity and
-    the view's outside plane -- it refreshes its tables in place, so no version.  A tuple is a SNAPSHOT: the array object, placement,
-    shape, vertical scale (the same codes under another one are another field) and -- for tensors -- the in-place version counter."""
-    if isinstance(heightfield, DeviceHeightField):
-        return id(heightfield._shared), heightfield.outside_z
-    h, x0, y0, cell = heightfield[:4]
-    return (id(h), float(x0), float(y0), float(cell), tuple(h.shape), getattr(h, "_version", None),
-            float(heightfield[4]) if len(heightfield) > 4 else None)
-
-
-def _cached_depth_camera(batch, heightfield) -> DepthCamera:
-    """one DepthCamera per batch and array (or shared buffers): built on first use, and again when _field_key tells the argument
-    from the last one -- a newer snapshot of an array replaces the older (a tuple becomes a DeviceHeightField of its own)"""
-    cache = batch.__dict__.setdefault("_depth_cameras", {})
-    key = _field_key(heightfield)
-    hit = cache.get(key[0])
-    if hit is None or hit[0] != key:
-        # (the entry holds the argument alive: an id is only unique among live objects)
-        hit = cache[key[0]] = (key, heightfield, DepthCamera(heightfield, batch.device, batch.p if isinstance(batch.p, A.WlVisualParams) else None))
-    return hit[2]

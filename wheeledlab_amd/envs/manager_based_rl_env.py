@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from .. import _abi as A
-from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch, generate_heightfield, mesh_heightfield
-from ..terrain import load_obj
+from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
+from ..field import assemble_terrain
 from .configclass import fields_of
 from .flatten import flatten_cfg
 from .scene import SceneView
@@ -226,34 +226,23 @@ class ManagerBasedRLEnv:
         flat = flatten_cfg(cfg)
         self._flat = flat
         self._task = flat.task
-        rank = 0
+        rank, world = 0, 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank = torch.distributed.get_rank()
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
         seed = 42 if cfg.seed is None else int(cfg.seed)
         common = dict(device=self.device, params=flat.params, seed=seed, env_offset=rank * self.num_envs,
                       metrics_slots=int(cfg.metrics_slots), startup=flat.startup)
-        if flat.extra.get("mesh_path") is not None:      # a mesh terrain: rasterised once, then a heightfield like any other
-            flat.extra["heightfield"] = mesh_heightfield(*load_obj(flat.extra["mesh_path"]), flat.extra["mesh_cell"], device=self.device)
-        if flat.extra.get("terrain_generator") is not None:      # a procedural terrain: generated on the device, redrawn in place
-            flat.extra["heightfield"] = generate_heightfield(flat.extra["terrain_generator"], self.device)
+        # the task's terrain: the field, each rank's slice of the world's level tables and the flat patches found on the device
+        heightfield, levels, patches = assemble_terrain(flat.extra, flat.params.cmd_xy if flat.task == "elevation" else None, self.num_envs,
+                                                        self.device, rank * self.num_envs, world * self.num_envs, seed)
         if flat.task == "elevation":
-            levels = None
-            if flat.extra.get("terrain_levels") is not None:      # each rank builds its slice of the world's assignment
-                from ..core import TerrainLevels
-                world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
-                levels = TerrainLevels(flat.extra["terrain_generator"], self.num_envs, self.device, rank * self.num_envs, world * self.num_envs,
-                                       flat.extra["terrain_levels"]["max_init_terrain_level"], seed)
-            patches = {}
-            if flat.extra.get("flat_patches") is not None:
-                patches, levels = self._find_flat_patches(flat, levels, rank, seed)
-            self._batch = ElevBatch(self.num_envs, heightfield=flat.extra.get("heightfield"), terrain_levels=levels, **common)
-            self._batch.flat_patches = patches
+            self._batch = ElevBatch(self.num_envs, heightfield=heightfield, terrain_levels=levels, flat_patches=patches, **common)
         elif flat.task in ("visual", "visual_depth"):
             x = flat.extra
             kw = dict(trav_map=x["map"], spacing=x["spacing"], map_kwargs=dict(map_size=x["map_size"], env_size=x["env_size"],
                                                                               sub_group_size=x["group"], num_walkers=x["walkers"]))
             if flat.task == "visual_depth":
-                self._batch = VisualDepthBatch(self.num_envs, heightfield=x.get("heightfield"), max_depth=x["max_depth"], **kw, **common)
+                self._batch = VisualDepthBatch(self.num_envs, heightfield=heightfield, max_depth=x["max_depth"], **kw, **common)
             else:
                 self._batch = VisualBatch(self.num_envs, **kw, **common)
         else:
@@ -288,7 +277,7 @@ class ManagerBasedRLEnv:
         self.extras = {}
         self.obs_buf = {}
         self._log_keys = episode_log_keys(self.reward_manager._slots, flat.termination_names)
-        if getattr(self._batch, "levels", None) is not None and flat.extra.get("terrain_levels") is not None:      # the mean level: one reduction, run when the log is read
+        if self._batch.levels is not None and flat.extra.get("terrain_levels") is not None:      # the mean level: one reduction, run when the log is read
             self._log_keys["Curriculum/" + flat.extra["terrain_levels"]["name"]] = ("f", self._batch.levels.mean_level)
         # "torch terms run between the kernel launches": the fused collectors (one launch per rollout / writing straight
         # into the runner's storage) are off whenever any kind of custom term is registered
@@ -360,53 +349,17 @@ class ManagerBasedRLEnv:
         self.obs_buf = {"policy": self._with_custom_obs(self._batch.observe())}
         return self.obs_buf, self.extras
 
-    def _find_flat_patches(self, flat, levels, rank: int, seed: int):
-        """the scene's flat patches (flatten._flat_patch_source), found on the device: -> ({name: FlatPatches}, the levels tables).
-        With spawn patches the tables carry "init_pos" as virtual columns: the curriculum's own grid, a generated grid without a
-        curriculum as one row of all its tiles, any other field as one tile."""
-        import zlib
-
-        from ..core import DeviceHeightField, TerrainLevels, find_flat_patches
-        from . import terrain_levels as TL
-        from .flatten import check_patch_goals
-        spec, gen = flat.extra["flat_patches"], flat.extra.get("terrain_generator")
-        hf = flat.extra.get("heightfield")
-        if not isinstance(hf, DeviceHeightField):      # the field the batch will share (built here so that the patches live on it)
-            from ..terrain import synthetic_heightfield
-            hf = flat.extra["heightfield"] = DeviceHeightField(hf if hf is not None else synthetic_heightfield(), self.device)
-        found = {}
-        for name in spec["names"]:
-            # one key per name: sets with equal sampling must not coincide ("init_pos" keeps the env's seed)
-            key = seed if name == "init_pos" else (seed & 0xFFFFFFFF) | (zlib.crc32(name.encode()) << 32)
-            found[name] = find_flat_patches(hf, gen if gen is not None else spec["sampling"][name], key, name)
-        if not spec["spawn"]:
-            return found, levels
-        fp = found["init_pos"]
-        world = torch.distributed.get_world_size() if torch.distributed.is_available() and torch.distributed.is_initialized() else 1
-        where = dict(device=self.device, env_offset=rank * self.num_envs, world_envs=world * self.num_envs, seed=seed)
-        if levels is not None:
-            levels = TerrainLevels(gen, self.num_envs, max_init_terrain_level=flat.extra["terrain_levels"]["max_init_terrain_level"],
-                                   flat_patches=fp, **where)
-        elif gen is not None:
-            levels = TerrainLevels.on_patches(fp, self.num_envs, 1, fp.n_tiles, tile_origins=TL.tile_origins(gen),
-                                              grid=(int(gen.num_rows), int(gen.num_cols)), **where)
-        else:
-            check_patch_goals(fp.table, hf.struct.nx, hf.struct.ny, hf.cell, flat.params.cmd_xy)
-            levels = TerrainLevels.on_patches(fp, self.num_envs, **where)
-        return found, levels
-
     def redeal_patches(self, epoch: int):
-        """deal every env another of its tile's spawn patches (core.TerrainLevels.redeal: one launch, no synchronisation); it counts
+        """deal every env another of its tile's spawn patches (field.TerrainLevels.redeal: one launch, no synchronisation); it counts
         from the env's next reset on.  Nothing without spawn patches."""
-        levels = getattr(self._batch, "levels", None)
-        if levels is not None:
-            levels.redeal(int(epoch))
+        if self._batch.levels is not None:
+            self._batch.levels.redeal(int(epoch))
 
     def regenerate_terrain(self, seed=None):
         """Draw the procedural terrain again (scene.terrain.terrain_type = "generator") under `seed` -- None: the current seed + 1
-        -- in place on the device (core.DeviceHeightField.regenerate), then reset every env: the cars would otherwise sit inside
+        -- in place on the device (field.DeviceHeightField.regenerate), then reset every env: the cars would otherwise sit inside
         or above the new ground.  -> (observations, extras) of the reset."""
-        hf = getattr(self._batch, "hf", None)
+        hf = self._batch.hf
         if hf is None or hf.generator is None:
             raise ValueError('regenerate_terrain needs a generated terrain: scene.terrain.terrain_type = "generator"')
         hf.regenerate(int(hf.generator.seed) + 1 if seed is None else int(seed))      # (finds the field's flat patches again, in place)

@@ -243,7 +243,7 @@ def terrain_levels_goal(env, env_ids=None, asset_cfg=_ROBOT):
     draws a uniform row.  The move itself is made INSIDE the step kernels, where the resets are (csrc/wl_elev.hip next_level;
     flatten.py switches it on when a CurrTerm names this function); the term's value -- logged as Curriculum/terrain_levels -- is the
     mean level, a 0-dim device tensor."""
-    levels = getattr(env._batch, "levels", None)
+    levels = env._batch.levels
     if levels is None:
         raise ValueError("terrain_levels_goal: this env carries no terrain levels (register it as a CurrTerm on a generator terrain)")
     return levels.mean_level()
@@ -528,7 +528,7 @@ def raycast_depth(env, sensor_cfg=_CAMERA, heightfield=None, max_depth: float | 
     far = env.scene.sensors[sensor_cfg.name].data.far if max_depth is None else max_depth
     if heightfield is None:
         return env.scene.sensors[sensor_cfg.name].data._camera().render(env._batch, far).unsqueeze(-1)
-    from ..core import _cached_depth_camera          # any task's batch: the camera is built on (and cached with) the batch
+    from ..sensors import _cached_depth_camera          # any task's batch: the camera is built on (and cached with) the batch
     return _cached_depth_camera(env._batch, heightfield).render(env._batch, far).unsqueeze(-1)
 
 

@@ -211,12 +211,11 @@ class CameraData:
 
     def _camera(self):
         if self._cam is None:
-            from ..core import DepthCamera
+            from ..sensors import DepthCamera
             b = self._b
-            if hasattr(b, "hf"):            # elevation and visual-depth tasks: the batch's own field (shared: its buffers, its pyramid)
-                hf = b.hf
-            else:                           # flat ground: any grid at z = 0 (beyond it the outside plane is z = 0 as well)
-                hf = (torch.zeros(3, 3, dtype=torch.float32, device=b.device), -1.0, -1.0, 1.0)
+            # elevation and visual-depth tasks: the batch's own field (shared: its buffers, its pyramid); else flat ground: any grid at
+            # z = 0 (beyond it the outside plane is z = 0 as well)
+            hf = b.hf if b.hf is not None else (torch.zeros(3, 3, dtype=torch.float32, device=b.device), -1.0, -1.0, 1.0)
             self._cam = DepthCamera(hf, b.device, b.p if isinstance(b.p, A.WlVisualParams) else self._params_from_cfg())
         return self._cam
 
@@ -325,7 +324,7 @@ def _quat_apply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
 class LidarData:
     """`sensor.data` of a scene lidar (envs.sensors_cfg.LidarCfg; an IsaacLab RayCaster with a lidar pattern, un-vendored):
     `output["linear_depth"]` [N, B] -- the ranges `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized` read (mdp_sensors/
-    observations.py:25-58) -- rendered by the lidar kernel (core.LidarScanner, wl_lidar_scan) against the task's terrain;
+    observations.py:25-58) -- rendered by the lidar kernel (sensors.LidarScanner, wl_lidar_scan) against the task's terrain;
     `ray_hits_w` [N, B, 3] (+inf where a beam meets nothing within max_range, as Warp's ray caster reports a miss); `pos_w` [N, 3]
     and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like CameraData."""
 
@@ -338,7 +337,7 @@ class LidarData:
 
     def scanner(self):
         if self._scanner is None:
-            from ..core import LidarScanner
+            from ..sensors import LidarScanner
             self._scanner = LidarScanner(self._cfg, self._b.device)
         return self._scanner
 
@@ -414,7 +413,7 @@ class TerrainLevelsView:
     """`env.scene.terrain` of an env that carries terrain levels: the terrain's config (every attribute of it reads through) plus
     IsaacLab's TerrainImporter tensors -- `terrain_levels` / `terrain_types` int32 [n], LIVE (the tensors the step kernels read and
     write), `terrain_origins` [rows, cols, 3] (tile centres, z = the terrain's height there) and `env_origins` [n, 3].  With flat
-    patches (core.FlatPatches): `flat_patches[name]` [rows, cols, P, 3], every patch's (x, y, z) as the device found it;
+    patches (field.FlatPatches): `flat_patches[name]` [rows, cols, P, 3], every patch's (x, y, z) as the device found it;
     `terrain_types` is then the tile's column (type // P) and the origins stay the tile centres."""
 
     def __init__(self, cfg, batch):
@@ -440,7 +439,7 @@ class TerrainLevelsView:
     def flat_patches(self):
         lv, gen = self._b.levels, self._b.hf.generator
         shape = lv.grid_shape if lv is not None else (int(gen.num_rows), int(gen.num_cols)) if gen is not None else (1, 1)
-        return {name: fp.positions().reshape(*shape, fp.n_patches, 3) for name, fp in getattr(self._b, "flat_patches", {}).items()}
+        return {name: fp.positions().reshape(*shape, fp.n_patches, 3) for name, fp in self._b.flat_patches.items()}
 
     @property
     def terrain_levels(self):
@@ -472,7 +471,7 @@ class SceneView:
     @property
     def env_origins(self):
         """[n, 3]: zeros (env_spacing = 0, mushr_drift_env_cfg.py:373) unless the batch carries terrain levels -- then every env's tile centre"""
-        if getattr(self._b, "levels", None) is not None:
+        if self._b.levels is not None:
             return self.terrain.env_origins
         return self._zero_origins
 

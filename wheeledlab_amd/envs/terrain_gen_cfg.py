@@ -25,8 +25,9 @@ TILE_DTYPE = np.dtype([(n, np.float32 if n in ("slope", "amplitude", "difficulty
 assert TILE_DTYPE.itemsize == 64
 
 
-def philox4x32(c0: int, c1: int, c2: int, c3: int, seed: int, rounds: int = 7):
-    """the library's generator (csrc/wl_rng.h) on python integers: counter (c0, c1, c2, c3), key = the seed's two words"""
+def philox4x32(c0, c1: int, c2: int, c3: int, seed: int, rounds: int = 7):
+    """the library's generator (csrc/wl_rng.h) on python integers: counter (c0, c1, c2, c3), key = the seed's two words.  The
+    package's one statement of it: no product exceeds 64 bits, so `c0` may as well be a uint64 array (terrain_levels.philox_word0)"""
     m = 0xFFFFFFFF
     c0, c1, c2, c3, k0, k1 = c0 & m, c1 & m, c2 & m, c3 & m, seed & m, (seed >> 32) & m
     for _ in range(rounds):

@@ -8,22 +8,16 @@ from __future__ import annotations
 
 import numpy as np
 
-from .terrain_gen_cfg import lattice
+from .terrain_gen_cfg import lattice, philox4x32
 
 LEVEL_STREAM = 3       # csrc/wl_elev.hip ES_LEVEL: the Philox stream of the initial levels (step 0) and of the wrap draw (the step)
 
 
 def philox_word0(gid, step: int, stream: int, seed: int, rounds: int = 7) -> np.ndarray:
-    """word 0 of the library's Philox4x32 (csrc/wl_rng.h) for counters (gid, step lo, step hi, stream), key = the seed's two words"""
-    m = np.uint64(0xFFFFFFFF)
-    c0 = np.asarray(gid, np.uint64) & m
-    c1, c2, c3 = (np.full_like(c0, np.uint64(v)) for v in (step & 0xFFFFFFFF, (step >> 32) & 0xFFFFFFFF, stream))
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(rounds):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & m, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & m
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c0.astype(np.uint32)
+    """word 0 of the library's Philox4x32 (terrain_gen_cfg.philox4x32, here on an array of counters) for (gid, step lo, step hi, stream)"""
+    c0 = np.asarray(gid, np.uint64)
+    # (flat: numpy's mixed arithmetic of a 0-d uint64 and a python integer has not always stayed in integers)
+    return philox4x32(c0.reshape(-1), step, step >> 32, stream, seed, rounds)[0].astype(np.uint32).reshape(c0.shape)
 
 
 def uniform_below(word, n: int) -> np.ndarray:

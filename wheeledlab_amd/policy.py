@@ -62,7 +62,7 @@ class Mlp:
         y = torch.empty(*x.shape[:-1], self.out_dim, dtype=torch.float32, device=self.device)
         s = self.struct()
         A.check(A.load().wl_mlp_forward(C.byref(s), x.numel() // self.in_dim, x.data_ptr(), y.data_ptr(),
-                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "wl_mlp_forward")
+                                        A.stream(self.device)), "wl_mlp_forward")
         return y
 
 
@@ -129,7 +129,7 @@ class ActorCritic:
             self._act_key, self._act_structs, self._act_fn = key, (self.actor.struct(), self.critic.struct()), A.load().wl_actor_critic_act
             self._act_scratch = None
         a, c = self._act_structs
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        stream = A.stream(obs.device)
         form = self.planes_form(max(n, self.global_rows or 0), D)
         if self.planes if self.planes is not None else form is not None:
             two = self.planes_two_launch if self.planes_two_launch is not None else form != "one"
@@ -167,7 +167,7 @@ class ActorCritic:
             vb = self._values_scratch = (key, A.WlActScratch(w_hi.data_ptr(), w_lo.data_ptr(), part.data_ptr(), dp, 1, chunk, 2), w_hi, w_lo,
                                          part, (self.actor.struct(), self.critic.struct()))
         sc, (a, c) = vb[1], vb[5]
-        lib, stream = A.load(), C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        lib, stream = A.load(), A.stream(obs.device)
         A.check(lib.wl_actor_critic_planes(C.byref(a), C.byref(c), C.byref(sc), stream), "wl_actor_critic_planes")
         for r0 in range(0, N, chunk):
             m = min(chunk, N - r0)
@@ -231,7 +231,7 @@ class RolloutStorage:
             returns = torch.empty_like(self.rewards)
             A.check(A.load().wl_gae(K, self.n_envs, self.rewards.data_ptr(), self.values.data_ptr(), self.dones.data_ptr(),
                                     float(gamma), float(lam), returns.data_ptr(), adv.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream(self.rewards.device).cuda_stream)), "wl_gae")
+                                    A.stream(self.rewards.device)), "wl_gae")
         else:
             last = torch.zeros(self.n_envs, dtype=torch.float32, device=self.rewards.device)
             not_done = 1.0 - self.dones.to(torch.float32)

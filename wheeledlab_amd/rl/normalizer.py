@@ -17,8 +17,6 @@ On a GPU the merge is csrc/wl_obs_norm.hip (one pass over the rows: normalise in
 float64 merge on the device); on the CPU everything here is plain torch in float64."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -127,14 +125,10 @@ class EmpiricalNormalization(nn.Module):
             from .. import _abi as A
             A.check(A.load().wl_obsnorm_update(self.dim, sums.data_ptr(), K * n * world, self.until if self.until is not None else 2 ** 62,
                                                self.eps, self._mean.data_ptr(), self._var.data_ptr(), self._std.data_ptr(),
-                                               self._inv_std.data_ptr(), self.count.data_ptr(), self._stream(x.device)), "wl_obsnorm_update")
+                                               self._inv_std.data_ptr(), self.count.data_ptr(), A.stream(x.device)), "wl_obsnorm_update")
         else:
             self._merge(sums, K * n * world)
         return self.max_ratio()
-
-    @staticmethod
-    def _stream(device):
-        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
     def _accumulate(self, x, out=None):
         """wl_obsnorm_accumulate over the rows of x (a [rows, D] float32 view with unit column stride): -> float64 [2, D] sums about
@@ -155,7 +149,7 @@ class EmpiricalNormalization(nn.Module):
             sums = torch.empty(2, self.dim, dtype=torch.float64, device=x.device)
             A.check(lib.wl_obsnorm_accumulate(rows, self.dim, xs.data_ptr(), stride, self._mean.data_ptr(), self._inv_std.data_ptr(),
                                               None if out is None else out[r0:r0 + rows].data_ptr(), self._scratch.data_ptr(),
-                                              sums.data_ptr(), self._stream(x.device)), "wl_obsnorm_accumulate")
+                                              sums.data_ptr(), A.stream(x.device)), "wl_obsnorm_accumulate")
             total = sums if total is None else total + sums
         return total
 
@@ -172,7 +166,7 @@ class EmpiricalNormalization(nn.Module):
                 from .. import _abi as A
                 assert w.is_contiguous() and m.w1.is_contiguous() and m.w1.data_ptr() != w.data_ptr()
                 A.check(A.load().wl_obsnorm_fold(self.dim, w.shape[0], w.data_ptr(), b.data_ptr(), self._mean.data_ptr(),
-                                                 self._inv_std.data_ptr(), m.w1.data_ptr(), m.b1.data_ptr(), self._stream(w.device)),
+                                                 self._inv_std.data_ptr(), m.w1.data_ptr(), m.b1.data_ptr(), A.stream(w.device)),
                         "wl_obsnorm_fold")
             else:
                 mean, inv = self._mean.double().squeeze(0), self._inv_std.double().squeeze(0)

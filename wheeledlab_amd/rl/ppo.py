@@ -454,7 +454,7 @@ class OnPolicyRunner:
         A.check(A.load().wl_rollout_bookkeeping(K, n, st.rewards.data_ptr(), st.values.data_ptr(), st.dones.data_ptr(),
                                                 st.time_outs.data_ptr(), st.actions.data_ptr(), float(self.alg.gamma),
                                                 carry_ret.data_ptr(), carry_len.data_ptr(), ep_ret.data_ptr(), ep_len.data_ptr(),
-                                                stats.data_ptr(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                                                stats.data_ptr(), A.stream(self.device)),
                 "wl_rollout_bookkeeping")
         sel = st.dones.view(-1).nonzero().view(-1)[-100:]
         out = torch.cat([stats.sum(1), ep_ret.view(-1)[sel], ep_len.view(-1)[sel]]).tolist()
@@ -658,7 +658,7 @@ class FusedPpoStep:
                             sigma_old.data_ptr())
 
     def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return self._A.stream(self.dev)
 
     @property
     def learning_rate(self) -> float:

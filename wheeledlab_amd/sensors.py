@@ -1,0 +1,122 @@
+"""The sensors that read a DeviceHeightField from the poses of any batch: DepthCamera (the visual task's pinhole camera as a depth
+image) and LidarScanner (range scans), and the per-batch cache of cameras (_cached_depth_camera, keyed by _field_key).  A sensor
+takes a batch as an argument; this module imports field, never core.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from . import _abi as A
+from .field import DeviceHeightField, _canonical_device
+
+
+class DepthCamera:
+    """The visual task's pinhole camera rendering distance_to_image_plane against a heightfield (wl_visual_depth): its parameters
+    and a view of the field (`hf`: its own outside plane, the field's buffers and its one bound pyramid), renders the poses of ANY
+    batch (rows WL_S_PX.. / WL_S_QW.. of its state matrix).  Reference hook: mdp_sensors/observations.py:89-95; camera
+    visual/mushr_visual_env_cfg.py:230-246."""
+
+    IMG_H, IMG_W = 60, 80
+
+    def __init__(self, heightfield, device="cuda:0", params: A.WlVisualParams | None = None, outside_z: float | None = None):
+        from .params import visual_params
+        self.lib = A.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("DepthCamera needs a HIP device; there is no CPU path")
+        self.p = params if params is not None else visual_params()
+        self.hf = DeviceHeightField(heightfield, self.device, outside_z)     # a tuple (quantised here) or a batch's own `.hf` (shared)
+        self.height, self._hf = self.hf.heights, self.hf.struct
+        self._pyr = self.hf.pyramid.data_ptr()    # resolved once: the field rebuilds its pyramid in place (refresh), never moves it
+
+    pyramid = property(lambda self: self.hf.pyramid)
+
+    def build_pyramid(self):
+        """the field's derived tables (the pyramid among them) from its codes as they are now"""
+        self.hf.refresh()
+
+    def render(self, batch, max_depth: float = 20.0, out: torch.Tensor | None = None) -> torch.Tensor:
+        if out is None:
+            out = torch.empty(batch.n, self.IMG_H, self.IMG_W, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == batch.n * self.IMG_H * self.IMG_W
+        A.check(self.lib.wl_visual_depth(C.byref(self.p), C.byref(batch._bufs), C.byref(self._hf), self._pyr,
+                                         float(max_depth), out.data_ptr(), A.stream(self.device)), "wl_visual_depth")
+        return out
+
+
+class LidarScanner:
+    """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
+    (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
+    field and pyramid come from the batch's cached DepthCamera, i.e. from the batch's DeviceHeightField (which owns the one pyramid).
+    render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
+    the terrain (what a miss reads in the scene is LidarData's business)."""
+
+    def __init__(self, cfg=None, device="cuda:0"):
+        from .envs.sensors_cfg import LidarCfg
+        self.lib = A.load()
+        self.device = _canonical_device(device)
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("LidarScanner needs a HIP device; there is no CPU path")
+        self.cfg = cfg = cfg if cfg is not None else LidarCfg()
+        dirs = cfg.pattern_cfg.directions()
+        self.n_beams = int(dirs.shape[0])
+        if not 1 <= self.n_beams <= A.LIDAR_MAX_BEAMS:
+            raise ValueError(f"a lidar pattern of {self.n_beams} beams (1 .. {A.LIDAR_MAX_BEAMS})")
+        self.beam_dirs = torch.as_tensor(dirs, dtype=torch.float32).contiguous().to(self.device)
+        self.max_range = float(cfg.max_range)
+        if not (math.isfinite(self.max_range) and self.max_range > 0):
+            raise ValueError(f"lidar max_range must be positive and finite, got {cfg.max_range}")
+        q = [float(v) for v in cfg.offset_rot]
+        qn = math.sqrt(sum(v * v for v in q))
+        if not (math.isfinite(qn) and qn > 0):
+            raise ValueError(f"lidar offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
+        self.params = A.WlLidarParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
+                                      self.n_beams, self.max_range, int(bool(cfg.attach_yaw_only)))
+        self._plane = None
+
+    def camera_of(self, batch) -> DepthCamera:
+        """the terrain the batch's cars stand on, as CameraData does it: the visual-depth task's own camera, the elevation task's
+        heightfield, else the z = 0 plane (a 3 x 3 zero grid: beyond it the outside plane is z = 0 as well)"""
+        if getattr(batch, "camera", None) is not None:
+            return batch.camera
+        if batch.hf is not None:
+            return _cached_depth_camera(batch, batch.hf)
+        if self._plane is None:       # one tensor per scanner: the batch's camera cache keys on it
+            self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
+        return _cached_depth_camera(batch, self._plane)
+
+    def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
+        """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
+        cam = camera if camera is not None else self.camera_of(batch)
+        if out is None:
+            out = torch.empty(batch.n, self.n_beams, dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch.n, self.n_beams)
+        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr,
+                                       self.beam_dirs.data_ptr(), out.data_ptr(), A.stream(self.device)), "wl_lidar_scan")
+        return out
+
+
+def _field_key(heightfield) -> tuple:
+    """What tells one `heightfield` argument from another (pure: needs no device).  A DeviceHeightField: its shared buffers' identity and
+    the view's outside plane -- it refreshes its tables in place, so no version.  A tuple is a SNAPSHOT: the array object, placement,
+    shape, vertical scale (the same codes under another one are another field) and -- for tensors -- the in-place version counter."""
+    if isinstance(heightfield, DeviceHeightField):
+        return id(heightfield._shared), heightfield.outside_z
+    h, x0, y0, cell = heightfield[:4]
+    return (id(h), float(x0), float(y0), float(cell), tuple(h.shape), getattr(h, "_version", None),
+            float(heightfield[4]) if len(heightfield) > 4 else None)
+
+
+def _cached_depth_camera(batch, heightfield) -> DepthCamera:
+    """one DepthCamera per batch and array (or shared buffers): built on first use, and again when _field_key tells the argument
+    from the last one -- a newer snapshot of an array replaces the older (a tuple becomes a DeviceHeightField of its own)"""
+    cache = batch.__dict__.setdefault("_depth_cameras", {})
+    key = _field_key(heightfield)
+    hit = cache.get(key[0])
+    if hit is None or hit[0] != key:
+        # (the entry holds the argument alive: an id is only unique among live objects)
+        hit = cache[key[0]] = (key, heightfield, DepthCamera(heightfield, batch.device, batch.p if isinstance(batch.p, A.WlVisualParams) else None))
+    return hit[2]

@@ -2,7 +2,7 @@
 wheeledlab_tasks/elevation/mushr_elevation_env_cfg.py; line citations inline.  Terms are the kernel-backed ones of
 `wheeledlab_amd.envs.mdp`.  The terrain is a heightfield: pass your own `(height, x0, y0, cell)` in `scene.terrain.heightfield`, or
 a triangle mesh as an OBJ file in `scene.terrain.mesh_path` (the reference's `huge_compact.usd`, exported, or your own: rasterised on
-the device at `mesh_cell` metres, core.mesh_heightfield), or a procedural terrain (`scene.terrain.terrain_type = "generator"` with
+the device at `mesh_cell` metres, field.mesh_heightfield), or a procedural terrain (`scene.terrain.terrain_type = "generator"` with
 `scene.terrain.terrain_generator` a wheeledlab_amd.envs.terrain_gen_cfg.TerrainGeneratorCfg, generated on the device and redrawn by
 env.regenerate_terrain), or leave all of them None for the synthetic field."""
 from ...assets import MUSHR_SUS_CFG

@@ -5,7 +5,7 @@ the snapshot; SURVEY.md 8d config 3 prescribes a synthetic 800 x 800 grid at 0.0
 place.  Users with a real heightfield pass their own array to the env / ElevBatch instead: `(height, x0, y0, cell)` with float
 heights (quantised here, `quantize_heights`) or `(codes int16, x0, y0, cell, z_scale)` as an IsaacLab generator produced them.  Users
 with a triangle mesh (that terrain exported to OBJ, or their own) read it with `load_obj` and rasterise it on the device with
-`core.mesh_heightfield` -- what the reference's downward height scanner sees at each lattice point -- or set
+`field.mesh_heightfield` -- what the reference's downward height scanner sees at each lattice point -- or set
 `scene.terrain.mesh_path` in the task config."""
 from __future__ import annotations
 

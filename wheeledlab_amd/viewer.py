@@ -106,9 +106,6 @@ class Viewer:
         self.hfov_deg, self.far_clip = float(hfov_deg), float(far_clip)
         self._scratch = None
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _scratch_for(self, n):
         need = int(self.lib.wl_viewer_scratch_bytes(self.width, self.height, int(n)))
         if need <= 0:
@@ -121,9 +118,8 @@ class Viewer:
         return batch.hf.struct, batch.hf.pyramid
 
     def params(self, batch, eye, lookat, env_index: int = 0) -> A.WlViewerParams:
-        hf = getattr(batch, "hf", None)
         return viewer_params(self.width, self.height, eye, lookat, batch.p.vehicle, self.hfov_deg, self.far_clip,
-                             ground=A.VIEWER_HEIGHTFIELD if hf is not None else A.VIEWER_PLANE, env_index=env_index,
+                             ground=A.VIEWER_HEIGHTFIELD if batch.hf is not None else A.VIEWER_PLANE, env_index=env_index,
                              id_offset=int(batch.env_offset))
 
     def render(self, batch, eye, lookat, env_index: int = 0, out=None, depth=None, ids=None) -> torch.Tensor:
@@ -144,5 +140,5 @@ class Viewer:
         A.check(self.lib.wl_viewer_render(C.byref(p), C.byref(batch._bufs), C.byref(hf) if hf is not None else None,
                                           pyr.data_ptr() if pyr is not None else None, C.byref(m) if m is not None else None,
                                           scratch.data_ptr(), need, out.data_ptr(), depth.data_ptr() if depth is not None else None,
-                                          ids.data_ptr() if ids is not None else None, self._stream()), "wl_viewer_render")
+                                          ids.data_ptr() if ids is not None else None, A.stream(self.device)), "wl_viewer_render")
         return out
