@@ -1,0 +1,541 @@
+"""The ray caster on the GPU (wl_raycast_scan through sensors.RayCaster and the scene's RayCasterSensorData / RayCasterCameraData): closed forms
+on the plane, every ray against the float64 reference (tests/raycaster_reference.py: oracle/depth.c one ray per table entry) on the
+bench field and the non-bench fields of tests/heightfield_cases.py, the column form against a float64 bilinear and against the walk,
+the fused height scanner, the lidar and the depth camera as yardsticks, the launch's edges, the env surface and a short PPO run.
+Yardstick for walked rays (lidar_reference.check): the 0.999 quantile of the relative error and the hit / miss disagreement fraction
+both below 1e-4.  The column form's bounds are raycaster_reference.column_bounds, computed from the field and the rays."""
+import numpy as np
+import pytest
+import torch
+
+from tests import heightfield_cases as HC
+from tests import lidar_reference as LR
+from tests import raycaster_reference as RR
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _posed(pos, quat):
+    """a batch whose state rows carry the given root poses (the scan reads rows WL_S_PX.. / WL_S_QW.. only)"""
+    from wheeledlab_amd.core import DriftBatch
+    b = DriftBatch(len(pos), device=DEV, seed=1)
+    b.state[0:3, : b.n] = torch.from_numpy(np.ascontiguousarray(pos.T)).to(DEV)
+    b.state[3:7, : b.n] = torch.from_numpy(np.ascontiguousarray(quat.T)).to(DEV)
+    return b
+
+
+def _posed_elev(pos, quat, b=None):
+    """an elevation batch (its terrain: the bench field) carrying the given root poses"""
+    from wheeledlab_amd.core import ElevBatch
+    b = b if b is not None else ElevBatch(len(pos), device=DEV, seed=1)
+    b.state[0:3, : b.n] = torch.from_numpy(np.ascontiguousarray(pos.T)).to(DEV)
+    b.state[3:7, : b.n] = torch.from_numpy(np.ascontiguousarray(quat.T)).to(DEV)
+    b.touch_pose()
+    return b
+
+
+def _terrain_of(batch):
+    """the terrain a batch's sensors see"""
+    from wheeledlab_amd.core import LidarScanner
+    return LidarScanner(device=DEV).camera_of(batch)
+
+
+def _camera(field, outside_z=None):
+    from wheeledlab_amd.core import DepthCamera
+    return DepthCamera(field, DEV, outside_z=outside_z)
+
+
+def _oracle_field(cam):
+    """the decoded fp32 heights every kernel sees, as the oracle takes them"""
+    return (cam.height.cpu().numpy(), cam.hf.x0, cam.hf.y0, cam.hf.cell)
+
+
+def _quat(roll, pitch, yaw):
+    from oracle.mathlib import quat_from_euler_xyz
+    e = np.asarray([[roll, pitch, yaw]], np.float32)
+    return quat_from_euler_xyz(e[:, 0], e[:, 1], e[:, 2]).astype(np.float32)
+
+
+def _grid_caster(grid, vertical=None, **kw):
+    from wheeledlab_amd.core import RayCaster
+    from wheeledlab_amd.envs.sensors_cfg import GridPatternCfg, RayCasterCfg
+    return RayCaster(RayCasterCfg(pattern_cfg=GridPatternCfg(**grid), **kw), DEV, vertical=vertical)
+
+
+def _cfg_mount(cfg_kw):
+    """a RayCasterCfg's mount as the reference's keywords"""
+    return dict(offset_pos=cfg_kw.get("offset_pos", (0.0, 0.0, 0.0)), offset_rot=cfg_kw.get("offset_rot", (1.0, 0.0, 0.0, 0.0)),
+                alignment=cfg_kw.get("ray_alignment", "yaw"))
+
+
+def _np(*tensors):
+    torch.cuda.synchronize()
+    out = tuple(t.cpu().numpy() for t in tensors)
+    return out if len(out) > 1 else out[0]
+
+
+# the three table shapes of tests/test_raycaster_cpu.py, each on its own mount and alignment
+MOUNTS = {"grid11x7": dict(offset_pos=(0.6, 0.0, 0.3), offset_rot=(0.9238795, 0.0, 0.0, 0.3826834), ray_alignment="yaw"),
+          "lidar360": dict(offset_pos=(0.1, -0.05, 0.25), offset_rot=(0.9914449, 0.0, 0.1305262, 0.0), ray_alignment="base"),
+          "pinhole8x12": dict(offset_pos=(0.23, 0.0, 0.18), ray_alignment="world")}
+
+
+def _pattern_caster(name, max_distance):
+    """the RayCaster of one of raycaster_reference.patterns(): built from the pattern's config; the lidar fan's starts (a 7 cm ring, which
+    no config describes) replace the table's zeros"""
+    from wheeledlab_amd.core import RayCaster
+    from wheeledlab_amd.envs.sensors_cfg import GridPatternCfg, LidarPatternCfg, PinholeCameraPatternCfg, RayCasterCfg
+    pat = {"grid11x7": GridPatternCfg(size=(1.0, 0.6), resolution=0.1, direction=(0.3, -0.1, -1.0)),
+           "lidar360": LidarPatternCfg(vertical_fov_range=(-8.0, -8.0)),
+           "pinhole8x12": PinholeCameraPatternCfg(width=12, height=8, focal_length=6.0, horizontal_aperture=12.0)}[name]
+    rc = RayCaster(RayCasterCfg(pattern_cfg=pat, max_distance=max_distance, **MOUNTS[name]), DEV)
+    starts, dirs, scale = RR.patterns()[name]
+    rc.ray_starts = torch.as_tensor(np.ascontiguousarray(starts), dtype=torch.float32).to(DEV)
+    np.testing.assert_array_equal(rc.ray_dirs.cpu().numpy(), dirs.astype(np.float32))
+    assert (rc.ray_scale is None) == (scale is None) and not rc.vertical
+    return rc, starts, dirs, scale
+
+
+def _unscaled(dist, hits, scale, max_distance):
+    """the ray parameter of a scaled distance; a miss is what the hit point says it is (max_distance x scale / scale need not round back)"""
+    sc = 1.0 if scale is None else np.asarray(scale, np.float32).astype(np.float64)[None]
+    return np.where(np.isinf(hits[..., 0]), max_distance, dist / sc)
+
+
+# ---- 6. closed forms on the z = 0 plane ------------------------------------------------------------------------------
+
+GRID = dict(size=(1.0, 0.6), resolution=0.1)
+
+
+def test_closed_forms_on_the_plane():
+    starts = _grid_caster(GRID).ray_starts.cpu().numpy().astype(np.float64)
+    pos = np.array([[3.0, -2.0, 0.32], [3.0, -2.0, 0.32], [150.0, 40.0, 0.07]], np.float32)
+    quat = np.concatenate([_quat(0.0, 0.0, 0.0), _quat(0.0, 0.3, 0.0), _quat(0.2, -0.25, 1.1)])
+    b = _posed(pos, quat)
+    assert b.hf is None                                    # a drift batch: the z = 0 plane
+    h = pos[:, 2].astype(np.float64) + 0.25
+    mount = dict(offset_pos=(0.0, 0.0, 0.25), max_distance=30.0)
+    base, hb = _np(*_grid_caster(GRID, ray_alignment="base", **mount).scan(b))
+    np.testing.assert_allclose(base[0], h[0], rtol=1e-6)                     # a level car reads its sensor height on every ray
+    # pitched by 0.3 with base alignment: the sensor at z + 0.25 cos, ray k starts x_k sin lower and leans by 0.3: h_k / cos
+    np.testing.assert_allclose(base[1], (pos[1, 2] + 0.25 * np.cos(0.3) - starts[:, 0] * np.sin(0.3)) / np.cos(0.3), rtol=1e-5)
+    np.testing.assert_allclose(hb[..., 2], 0.0, atol=1e-6)
+    for vertical in (False, None):                         # the walk, and what the host picks for vertical rays: the column form
+        yaw_rc = _grid_caster(GRID, vertical=vertical, ray_alignment="yaw", **mount)
+        assert yaw_rc.vertical == (vertical is None)
+        yaw, hy = _np(*yaw_rc.scan(b))
+        np.testing.assert_allclose(yaw, np.repeat(h[:, None], 77, 1), rtol=1e-6)       # yaw alignment ignores roll and pitch
+        world, hw = _np(*_grid_caster(GRID, vertical=vertical, ray_alignment="world", **mount).scan(b))
+        np.testing.assert_allclose(world, np.repeat(h[:, None], 77, 1), rtol=1e-6)
+        np.testing.assert_allclose(hw[..., :2] - pos[:, None, :2], np.repeat(starts[None, :, :2], 3, 0), atol=2e-5)
+        assert np.abs(hy[2, :, :2] - pos[2, None, :2] - starts[None, :, :2]).max() > 0.1
+
+
+def test_world_alignment_ignores_yaw_on_a_heightfield():
+    """two cars that differ only in yaw read the same, and their hit points do not rotate"""
+    from oracle import heightfield as HF
+    cam = _camera(HF.make_terrain())
+    pos = np.array([[3.0, 4.0, 2.5]] * 2, np.float32)
+    b = _posed(pos, np.concatenate([_quat(0.1, -0.2, 0.4), _quat(0.1, -0.2, -2.0)]))
+    for vertical in (False, None):
+        d, h = _np(*_grid_caster(GRID, vertical=vertical, ray_alignment="world", offset_pos=(0.3, 0.1, 0.5), max_distance=30.0).scan(b, cam))
+        assert np.array_equal(d[0], d[1]) and np.array_equal(h[0], h[1]) and d.std() > 0 and (d < 30.0).all()
+    d, _ = _np(*_grid_caster(GRID, ray_alignment="yaw", offset_pos=(0.3, 0.1, 0.5), max_distance=30.0).scan(b, cam))
+    assert not np.array_equal(d[0], d[1])
+
+
+# ---- 7. every ray against the reference ------------------------------------------------------------------------------
+
+def _fields():
+    from oracle import heightfield as HF
+    yield "bench", HF.make_terrain(), 0.0, None
+    for g in ("G1", "G2", "G3", "G4a", "G4b", "G6"):
+        f = HC.get(g)
+        yield g, f, f.outside_z, f
+
+
+def test_every_ray_matches_the_reference_on_bench_and_non_bench_fields():
+    for i, (name, field, oz, case) in enumerate(_fields()):
+        cam = _camera(field) if case is None else _camera(case.device(DEV))
+        of = _oracle_field(cam)
+        pos, quat = LR.poses(256, seed=80 + i, field=of, outside_z=oz, margin=1.0)
+        b = _posed(pos, quat)
+        for md in (5.0, 30.0):
+            hit_any = miss_any = False
+            for pname in MOUNTS:
+                rc, starts, dirs, scale = _pattern_caster(pname, md)
+                dist, hits = _np(*rc.scan(b, cam))
+                want = RR.distances(pos, quat, starts, dirs, of, md, oz, **_cfg_mount(MOUNTS[pname]))
+                rel, flip = LR.check(_unscaled(dist, hits, scale, md), want, md, (name, pname, md))
+                hit = want < md
+                print(f"raycaster parity {name} {pname} max_distance={md}: hit fraction {hit.mean():.3f}, flips {int(flip.sum())} of "
+                      f"{flip.size}, p99.9 rel err {np.quantile(rel, 0.999):.2e}")
+                assert (dist >= 0).all() and np.isinf(hits[np.isinf(hits).any(-1)]).all()
+                hit_any, miss_any = hit_any or hit.any(), miss_any or (~hit).any()
+            assert hit_any and miss_any, (name, md)
+
+
+# ---- 8. the column form ----------------------------------------------------------------------------------------------
+
+# the elevation scanner's grid 20 m above the car and a look-ahead grid 0.3 m above it
+COLUMNS = {"26x26@20m": (dict(size=(2.5, 2.5), resolution=0.1), dict(offset_pos=(0.0, 0.0, 20.0), ray_alignment="yaw")),
+           "11x7@0.3m": (GRID, dict(offset_pos=(0.6, 0.0, 0.3), offset_rot=(0.9238795, 0.0, 0.0, 0.3826834), ray_alignment="yaw"))}
+
+
+def check_column(dist, hits, pos, quat, starts, field, max_distance, oz, mount, what):
+    """the column form against float64: hit xy and z within raycaster_reference.column_bounds, the distance within the z bound plus two
+    roundings of the start height (its sum and the difference); no ray of the reference misses"""
+    t, o, z = RR.column(pos, quat, starts, field, max_distance, oz, **mount)
+    assert (t < max_distance).all(), what
+    xy_tol, z_tol = RR.column_bounds(field, o)
+    exy = np.abs(hits[..., :2].astype(np.float64) - o[..., :2]).max()
+    above = t > 0
+    ez = np.abs(hits[..., 2].astype(np.float64) - np.where(above, z, o[..., 2])).max()
+    t_tol = z_tol + 2 * float(np.spacing(np.float32(np.abs(o[..., 2]).max())))
+    et = np.abs(dist.astype(np.float64) - t).max()
+    print(f"column form {what}: xy err {exy:.2e} (bound {xy_tol:.2e}), z err {ez:.2e} (bound {z_tol:.2e}), t err {et:.2e} (bound {t_tol:.2e})")
+    assert np.isfinite(hits).all() and exy <= xy_tol and ez <= z_tol + (0 if above.all() else t_tol) and et <= t_tol, what
+
+
+@pytest.mark.parametrize("which", list(COLUMNS))
+def test_column_form_matches_float64_bilinear_and_the_walk(which):
+    from oracle import heightfield as HF
+    grid, cfg_kw = COLUMNS[which]
+    cam = _camera(HF.make_terrain())
+    of = _oracle_field(cam)
+    pos, quat = LR.poses(256, seed=90, field=of)
+    b = _posed(pos, quat)
+    md = 30.0
+    col = _grid_caster(grid, max_distance=md, **cfg_kw)
+    assert col.vertical and col.n_rays == {"26x26@20m": 676, "11x7@0.3m": 77}[which]
+    dist, hits = _np(*col.scan(b, cam))
+    starts = col.ray_starts.cpu().numpy()
+    check_column(dist, hits, pos, quat, starts, of, md, 0.0, _cfg_mount(cfg_kw), which)
+    walk = _grid_caster(grid, vertical=False, max_distance=md, **cfg_kw)
+    assert not walk.vertical
+    wdist, whits = _np(*walk.scan(b, cam))
+    LR.check(dist, wdist, md, ("column vs walk", which))
+    LR.check(wdist, RR.distances(pos, quat, starts, walk.ray_dirs.cpu().numpy(), of, md, 0.0, **_cfg_mount(cfg_kw)), md, ("walk", which))
+
+
+# ---- 9. the fused scanner as a yardstick -----------------------------------------------------------------------------
+
+def test_the_elevation_tasks_fused_scanner_is_reproduced():
+    from wheeledlab_amd import registry, tasks  # noqa: F401
+    from wheeledlab_amd.core import RayCaster
+    n = 64
+    cfg = registry.parse_env_cfg("Isaac-MushrElevationRL-v0", device=DEV, num_envs=n)
+    env = registry.make("Isaac-MushrElevationRL-v0", cfg=cfg)
+    env.reset()
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for _ in range(3):
+        env.step(torch.rand(n, 2, device=DEV, generator=g) * 2 - 1)
+    b = env._batch
+    # poses inside the field: beyond its edge the fused scan reports a miss where the ray caster meets the outside plane, so a car whose
+    # 2.5 m footprint (half diagonal 1.77 m) could leave the grid is pulled in by a plugin's pose write
+    robot = env.scene["robot"]
+    pose = torch.cat([robot.data.root_pos_w, robot.data.root_quat_w], 1)
+    lo = torch.tensor([b.hf.x0, b.hf.y0], device=DEV) + 2.0
+    hi = torch.tensor([b.hf.x0 + (b.hf.heights.shape[1] - 1) * b.hf.cell, b.hf.y0 + (b.hf.heights.shape[0] - 1) * b.hf.cell], device=DEV) - 2.0
+    pose[:, :2] = torch.minimum(torch.maximum(pose[:, :2], lo), hi)
+    robot.write_root_pose_to_sim(pose)
+    fused = env.scene.sensors["height_scanner"].data.ray_hits_w
+    rc = RayCaster(cfg.scene.height_scanner, DEV)
+    assert rc.vertical and rc.n_rays == 676 and rc.alignment == "yaw"
+    dist, hits = rc.scan(b)
+    fused, dist, hits = _np(fused, dist, hits)
+    assert np.isfinite(fused).all() and np.isfinite(hits).all() and (dist < rc.max_distance).all()      # neither side reports a miss
+    st = b.state[:, :n].cpu().numpy()
+    of = _oracle_field(rc.camera_of(b))
+    mount = dict(offset_pos=(0.0, 0.0, 20.0), alignment="yaw")
+    _, o, _ = RR.column(st[0:3].T, st[3:7].T, rc.ray_starts.cpu().numpy(), of, rc.max_distance, b.hf.outside_z, **mount)
+    xy_tol, z_tol = RR.column_bounds(of, o)
+    exy, ez = np.abs(hits[..., :2] - fused[..., :2]).max(), np.abs(hits[..., 2] - fused[..., 2]).max()
+    print(f"fused scanner vs ray caster: xy err {exy:.2e} (bound {xy_tol:.2e}), z err {ez:.2e} (bound {z_tol:.2e})")
+    assert exy <= xy_tol and ez <= z_tol
+    check_column(dist, hits, st[0:3].T, st[3:7].T, rc.ray_starts.cpu().numpy(), of, rc.max_distance, b.hf.outside_z, mount, "elevation env")
+    env.close()
+
+
+# ---- 10. the lidar as a yardstick ------------------------------------------------------------------------------------
+
+def test_a_lidar_pattern_through_the_ray_caster_equals_the_lidar_kernel():
+    """same device functions, same inputs: bit for bit"""
+    from oracle import heightfield as HF
+    from wheeledlab_amd.core import LidarScanner, RayCaster
+    from wheeledlab_amd.envs.sensors_cfg import LidarCfg, LidarPatternCfg, RayCasterCfg
+    pat = LidarPatternCfg(channels=16, vertical_fov_range=(-15.0, 15.0))
+    mount = dict(offset_pos=(0.1, -0.05, 0.25), offset_rot=(0.9914449, 0.0, 0.1305262, 0.0))
+    cam = _camera(HF.make_terrain())
+    pos, quat = LR.poses(256, seed=100, field=_oracle_field(cam), margin=1.0)
+    b = _posed(pos, quat)
+    for yaw_only in (False, True):
+        lidar = LidarScanner(LidarCfg(pattern_cfg=pat, max_range=10.0, attach_yaw_only=yaw_only, **mount), DEV).render(b, camera=cam)
+        rc = RayCaster(RayCasterCfg(pattern_cfg=pat, max_distance=10.0, attach_yaw_only=yaw_only, **mount), DEV)
+        assert rc.n_rays == 16 * 360 and not rc.vertical and float(rc.ray_starts.abs().max()) == 0.0 and rc.ray_scale is None
+        got = rc.render(b, cam)
+        torch.cuda.synchronize()
+        assert torch.equal(got, lidar) and float((got < 10.0).float().mean()) > 0.1 and bool((got == 10.0).any())
+
+
+# ---- 11. the depth camera as a yardstick -----------------------------------------------------------------------------
+
+def _visual_camera_cfg(width, height, **kw):
+    """a RayCasterCameraCfg with the visual camera's intrinsics (scaled to the image size) and mount: optical axis along the body's x"""
+    from wheeledlab_amd.envs.sensors_cfg import PinholeCameraPatternCfg, RayCasterCameraCfg
+    from wheeledlab_amd.params import visual_params
+    p = visual_params()
+    sx, sy = width / 80, height / 60
+    pat = PinholeCameraPatternCfg(width=width, height=height, focal_length=p.fx * sx, horizontal_aperture=float(width),
+                                  vertical_aperture=height * p.fx * sx / (p.fy * sy),
+                                  horizontal_aperture_offset=(p.cx * sx - width / 2) / (p.fx * sx),
+                                  vertical_aperture_offset=(p.cy * sy - height / 2) / (p.fy * sy))
+    return p, RayCasterCameraCfg(pattern_cfg=pat, offset_pos=tuple(p.cam_pos), offset_rot=(0.5, -0.5, 0.5, -0.5), offset_convention="ros", **kw)
+
+
+@pytest.mark.parametrize("width,height", [(80, 60), (40, 30), (23, 17)])
+def test_ray_caster_camera_against_the_reference_and_the_depth_camera(width, height):
+    from wheeledlab_amd.envs.scene import RayCasterCameraView
+    n = 64
+    b = _posed_elev(np.zeros((n, 3), np.float32), np.repeat(_quat(0.0, 0.0, 0.0), n, 0))      # the view scans the batch's own field
+    cam = _terrain_of(b)
+    of = _oracle_field(cam)
+    pos, quat = LR.poses(n, seed=110, field=of)
+    b = _posed_elev(pos, quat, b)
+    far = 40.0
+    p, cfg = _visual_camera_cfg(width, height, max_distance=far)
+    data = RayCasterCameraView(b, cfg).data
+    rc = data.scanner()
+    assert rc.alignment == "base" and rc.n_rays == width * height and not rc.vertical
+    np.testing.assert_allclose(rc.params.offset_quat[:], (1.0, 0.0, 0.0, 0.0), atol=1e-7)           # ros z forward = the body's x
+    plane, euclid = data.output["distance_to_image_plane"], data.output["distance_to_camera"]
+    assert plane.shape == euclid.shape == (n, height, width, 1)
+    dist, hits = rc.scan(b)
+    plane, euclid, dist, hits, scale = _np(plane, euclid, dist, hits, rc.ray_scale)
+    plane, euclid = plane.reshape(n, -1), euclid.reshape(n, -1)
+    miss = np.isinf(hits[..., 0])
+    assert (euclid >= plane).all() and miss.any() and (~miss).any()
+    assert (plane[miss] == far).all() and (euclid[miss] == far).all() and np.array_equal(plane[~miss], dist[~miss])
+    starts, dirs = cfg.pattern_cfg.rays()
+    mount = dict(offset_pos=tuple(p.cam_pos), alignment="base")
+    want = RR.distances(pos, quat, starts, dirs, of, far, 0.0, **mount)
+    LR.check(_unscaled(dist, hits, scale, far), want, far, ("reference", width, height))
+    np.testing.assert_allclose(euclid[~miss], _unscaled(dist, hits, scale, far)[~miss], rtol=3e-7)
+    K = data.intrinsic_matrices.cpu().numpy()
+    sx, sy = width / 80, height / 60
+    np.testing.assert_allclose(K[0], [[p.fx * sx, 0, p.cx * sx], [0, p.fy * sy, p.cy * sy], [0, 0, 1]], rtol=1e-6)
+    assert data.pos_w.shape == (n, 3) and K.shape == (n, 3, 3)
+    np.testing.assert_allclose(data.quat_w_world.cpu().numpy(), quat, atol=1e-6)
+    ros = data.quat_w_ros.cpu().numpy()
+    np.testing.assert_allclose(LR._mat64(ros)[:, :, 2], LR._mat64(quat)[:, :, 0], atol=1e-6)       # the ros frame's z is the optical axis
+    if (width, height) == (80, 60):
+        # the fused camera clips the IMAGE-PLANE distance at its far plane, the ray caster the ray: compare below a far plane that
+        # every ray of the ray caster's range reaches (far x the smallest cosine of the table)
+        near = float(np.floor(far * scale.min()))
+        fused = _np(cam.render(b, near)).reshape(n, -1)
+        LR.check(np.minimum(np.where(miss, far, plane), near), fused, near, "DepthCamera")
+
+
+def test_depth_clipping_behavior_on_a_miss():
+    from wheeledlab_amd.envs.scene import RayCasterCameraView
+    pos = np.array([[0.0, 0.0, 0.2]], np.float32)
+    b = _posed(pos, _quat(0.0, 0.0, 0.3))
+    for mode, want in (("max", 15.0), ("zero", 0.0), ("none", float("inf"))):
+        _, cfg = _visual_camera_cfg(23, 17, max_distance=15.0, depth_clipping_behavior=mode)
+        for key in ("distance_to_image_plane", "distance_to_camera"):
+            img = _np(RayCasterCameraView(b, cfg).data.output[key])[0, :, :, 0]
+            assert (img[:8] == want).all()                                 # the sky: the upper rows look above the horizon of the plane
+            assert np.isfinite(img[-1]).all() and (img[-1] > 0).all() and (img[-1] < 15.0).all()
+    with pytest.raises(KeyError):
+        RayCasterCameraView(b, cfg).data.output["rgb"]
+
+
+# ---- 12. launch edges ------------------------------------------------------------------------------------------------
+
+COUNTS = {1: dict(size=(0.0, 0.0), resolution=0.1), 63: dict(size=(0.8, 0.6), resolution=0.1), 65: dict(size=(1.2, 0.4), resolution=0.1),
+          676: dict(size=(2.5, 2.5), resolution=0.1)}
+
+
+@pytest.mark.parametrize("n_rays", list(COUNTS))
+@pytest.mark.parametrize("form", ["walk", "column"])
+def test_ray_counts_that_are_not_multiples_of_64(n_rays, form):
+    from oracle import heightfield as HF
+    cam = _camera(HF.make_terrain())
+    of = _oracle_field(cam)
+    pos, quat = LR.poses(64, seed=5, field=of)
+    direction = (0.3, -0.1, -1.0) if form == "walk" else (0.0, 0.0, -1.0)
+    mount = dict(offset_pos=(0.1, 0.0, 0.4), ray_alignment="yaw")
+    rc = _grid_caster(dict(direction=direction, **COUNTS[n_rays]), max_distance=30.0, **mount)
+    assert rc.n_rays == n_rays and rc.vertical == (form == "column")
+    n = len(pos)
+    gd = torch.full((n * n_rays + 4096,), float("nan"), device=DEV)
+    gh = torch.full((3 * n * n_rays + 4096,), float("nan"), device=DEV)
+    dist, hits = gd[: n * n_rays].view(n, n_rays), gh[: 3 * n * n_rays].view(n, n_rays, 3)
+    b = _posed(pos, quat)
+    rc.scan(b, cam, dist=dist, hits=hits)
+    torch.cuda.synchronize()
+    assert torch.isnan(gd[n * n_rays:]).all() and torch.isnan(gh[3 * n * n_rays:]).all()            # nothing written past the last row
+    assert not torch.isnan(dist).any() and not torch.isnan(hits).any()
+    want = RR.distances(pos, quat, rc.ray_starts.cpu().numpy(), rc.ray_dirs.cpu().numpy(), of, 30.0, 0.0, **_cfg_mount(mount))
+    LR.check(dist.cpu().numpy(), want, 30.0, (n_rays, form))
+    # either output alone gives the same values, and a second scan the same bits
+    assert torch.equal(rc.render(b, cam), dist) and torch.equal(rc.hits(b, cam), hits)
+    d2, h2 = rc.scan(b, cam)
+    assert torch.equal(d2, dist) and torch.equal(h2, hits)
+
+
+@pytest.mark.parametrize("form", ["walk", "column"])
+def test_one_env_and_more_envs_than_a_grid_dimension(form):
+    from oracle import heightfield as HF
+    cam = _camera(HF.make_terrain())
+    of = _oracle_field(cam)
+    direction = (0.3, -0.1, -1.0) if form == "walk" else (0.0, 0.0, -1.0)
+    mount = dict(offset_pos=(0.1, 0.0, 0.4), ray_alignment="yaw")
+    rc = _grid_caster(dict(direction=direction, **COUNTS[1]), max_distance=30.0, **mount)
+    starts, dirs = rc.ray_starts.cpu().numpy(), rc.ray_dirs.cpu().numpy()
+    pos, quat = LR.poses(70000, seed=8, field=of)
+    one = _np(rc.render(_posed(pos[:1], quat[:1]), cam))
+    LR.check(one, RR.distances(pos[:1], quat[:1], starts, dirs, of, 30.0, 0.0, **_cfg_mount(mount)), 30.0, "n=1")
+    b = _posed(pos, quat)
+    got = _np(rc.render(b, cam))
+    LR.check(got, RR.distances(pos, quat, starts, dirs, of, 30.0, 0.0, **_cfg_mount(mount)), 30.0, "n=70000")
+    assert np.array_equal(got[:1], one)
+
+
+def test_the_pyramid_and_a_depth_render_are_unchanged_by_a_scan():
+    from oracle import heightfield as HF
+    cam = _camera(HF.make_terrain())
+    pos, quat = LR.poses(256, seed=9, field=_oracle_field(cam))
+    b = _posed(pos, quat)
+    pyr, pair = cam.pyramid.clone(), cam.hf.pairs.clone() if hasattr(cam.hf, "pairs") else None
+    before = cam.render(b, 30.0).clone()
+    _pattern_caster("lidar360", 30.0)[0].scan(b, cam)
+    _grid_caster(COUNTS[676], offset_pos=(0.0, 0.0, 20.0), max_distance=30.0).scan(b, cam)
+    after = cam.render(b, 30.0)
+    torch.cuda.synchronize()
+    assert torch.equal(before, after) and torch.equal(pyr.view(torch.int32), cam.pyramid.view(torch.int32))     # (entries are packed words)
+    assert pair is None or torch.equal(pair, cam.hf.pairs)
+
+
+# ---- 13. the env surface ---------------------------------------------------------------------------------------------
+
+FRONT = dict(offset_pos=(0.6, 0.0, 0.3))
+
+
+def _env(task, n):
+    from wheeledlab_amd import registry, tasks  # noqa: F401
+    from wheeledlab_amd.envs import mdp
+    from wheeledlab_amd.envs.managers_cfg import ObservationTermCfg as ObsTerm
+    from wheeledlab_amd.envs.managers_cfg import SceneEntityCfg
+    from wheeledlab_amd.envs.sensors_cfg import GridPatternCfg, RayCasterCfg
+    cfg = registry.parse_env_cfg(task, device=DEV, num_envs=n)
+    cfg.scene.front_scan = RayCasterCfg(pattern_cfg=GridPatternCfg(**GRID), **FRONT)
+    cfg.scene.depth_cam = _visual_camera_cfg(23, 17, max_distance=15.0)[1]
+    cfg.observations.policy.front_scan = ObsTerm(func=mdp.height_scan, params={"sensor_cfg": SceneEntityCfg("front_scan"), "offset": 0.0})
+    return registry.make(task, cfg=cfg)
+
+
+def _count_scans(data):
+    sc = data.scanner()
+    calls = []
+    scan = sc.scan
+
+    def counted(*a, **kw):
+        calls.append(1)
+        return scan(*a, **kw)
+    sc.scan = counted
+    return calls
+
+
+def _front(env):
+    from wheeledlab_amd.envs import mdp
+    from wheeledlab_amd.envs.managers_cfg import SceneEntityCfg
+    return mdp.height_scan(env, SceneEntityCfg("front_scan"), offset=0.0)
+
+
+def test_elevation_env_with_a_front_scan_observation():
+    from wheeledlab_amd.core import RayCaster
+    from wheeledlab_amd.envs.scene import RayCasterView, RayCasterSensorView
+    n, R = 64, 77
+    env = _env("Isaac-MushrElevationRL-v0", n)
+    assert env.observation_manager.group_obs_dim["policy"] == (689 + R,)
+    assert type(env.scene.sensors["height_scanner"]) is RayCasterView and type(env.scene.sensors["front_scan"]) is RayCasterSensorView
+    data = env.scene.sensors["front_scan"].data
+    assert data._cached == (None, None)                                   # the shape probe kept nothing
+    calls = _count_scans(data)
+    obs, _ = env.reset()
+    assert obs["policy"].shape == (n, 689 + R) and len(calls) == 1
+    fresh = lambda: RayCaster(data._cfg, DEV).scan(env._batch)
+    d, h = fresh()
+    assert torch.equal(data.distances, d) and torch.equal(data.ray_hits_w, h) and len(calls) == 1
+    assert torch.equal(obs["policy"][:, 689:], _front(env)) and len(calls) == 1
+    # vertical rays: the height scan is the distance, up to the rounding of the sensor's height (formed once more on the host)
+    torch.testing.assert_close(_front(env), d, rtol=0, atol=2 * float(np.spacing(np.float32(data.pos_w[:, 2].abs().max().item()))))
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for k in range(3):
+        obs, *_ = env.step(torch.rand(n, 2, device=DEV, generator=g) * 2 - 1)
+        for _ in range(3):                                                # however often it is read: one scan per step
+            r = _front(env)
+        assert len(calls) == 2 + k and torch.equal(data.ray_hits_w, fresh()[1])
+        assert torch.isfinite(obs["policy"][:, 689:]).all() and obs["policy"][:, 689:].std() > 0
+    assert data.pos_w.shape == (n, 3) and data.quat_w.shape == (n, 4) and data.ray_hits_w.shape == (n, R, 3)
+    torch.testing.assert_close(data.pos_w[:, None, 2] - data.ray_hits_w[..., 2], r, rtol=0, atol=0)
+    # a reset and a plugin's pose write each invalidate the cached scan
+    env.reset()
+    _front(env)
+    assert len(calls) == 5
+    robot = env.scene["robot"]
+    pose = torch.cat([robot.data.root_pos_w, robot.data.root_quat_w], 1)
+    pose[:, 2] += 0.5
+    robot.write_root_pose_to_sim(pose)
+    lifted = _front(env)
+    assert len(calls) == 6 and torch.equal(lifted, fresh()[0])
+    env.close()
+
+
+def test_drift_env_reads_the_plane_and_visual_depth_env_its_own_field():
+    from wheeledlab_amd.envs import mdp
+    from wheeledlab_amd.envs.managers_cfg import SceneEntityCfg
+    for task in ("Isaac-MushrDriftRL-v0", "Isaac-MushrVisualDepthRL-v0"):
+        n = 64
+        env = _env(task, n)
+        env.reset()
+        for _ in range(3):
+            env.step(torch.rand(n, 2, device=DEV) * 2 - 1)
+        b = env._batch
+        data = env.scene.sensors["front_scan"].data
+        got = _np(_front(env))
+        # the reference's depth observation terms read the ray-caster camera as they are
+        img = mdp.camera_data_depth(env, SceneEntityCfg("depth_cam"))
+        assert img.shape == (n, 17, 23, 1) and torch.equal(img, mdp.raycast_depth(env, SceneEntityCfg("depth_cam")))
+        assert float(img.min()) >= 0.0 and float(img.max()) <= 15.0 and float(img.std()) > 0
+        st = b.state[:, :n].cpu().numpy()
+        starts = data.scanner().ray_starts.cpu().numpy()
+        mount = dict(alignment="yaw", **FRONT)
+        if task == "Isaac-MushrDriftRL-v0":
+            assert b.hf is None
+            np.testing.assert_allclose(got, np.repeat((st[2].astype(np.float64) + 0.3)[:, None], 77, 1), rtol=1e-6)     # its height over z = 0
+        else:
+            assert data.scanner().camera_of(b) is b.camera
+            of = _oracle_field(b.camera)
+            t, o, z = RR.column(st[0:3].T, st[3:7].T, starts, of, 1e6, b.camera.hf.outside_z, **mount)
+            _, z_tol = RR.column_bounds(of, o)
+            assert np.abs(got - t).max() <= z_tol + 2 * float(np.spacing(np.float32(np.abs(o[..., 2]).max()))) and got.std() > 0
+        env.close()
+
+
+def test_two_ppo_iterations_on_the_front_scan_observation():
+    from wheeledlab_amd import registry
+    from wheeledlab_amd.rl import ClipAction, RslRlVecEnvWrapper
+    from wheeledlab_amd.rl.ppo import OnPolicyRunner
+    torch.manual_seed(0)
+    env = _env("Isaac-MushrElevationRL-v0", 256)
+    env.action_space.low, env.action_space.high = -1.0, 1.0
+    runner = OnPolicyRunner(RslRlVecEnvWrapper(ClipAction(env)), registry.load_cfg_from_registry("Isaac-MushrElevationRL-v0",
+                                                                                                   "rsl_rl_cfg_entry_point"), device=DEV)
+    assert runner.actor_critic.actor[0].in_features == 689 + 77 and runner.alg._wide
+    before = [p.detach().clone() for p in runner.actor_critic.parameters()]
+    hist = runner.learn(2, verbose=False)
+    assert len(hist) == 2 and all(np.isfinite(h["value_function"]) and np.isfinite(h["surrogate"]) for h in hist)
+    assert any(not torch.equal(p, q) for p, q in zip(before, runner.actor_critic.parameters()))

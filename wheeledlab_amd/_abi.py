@@ -355,6 +355,23 @@ LIDAR_SIGNATURES = {
     "wl_lidar_scan": (C.c_int, [_P(WlLidarParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _vp, _vp, _vp]),
 }
 
+# include/wheeledlab_amd_raycaster.h: ray-caster sensors over any ray table -- a header of its own, outside the drop-in step boundary
+WL_RAYCASTER_VERSION = 1
+RAYCAST_MAX_RAYS = 1 << 20
+RAYCAST_ALIGNMENTS = {"base": 0, "yaw": 1, "world": 2}
+
+
+class WlRayCastParams(C.Structure):
+    _fields_ = [("offset_pos", C.c_float * 3), ("offset_quat", C.c_float * 4), ("n_rays", C.c_int32), ("max_distance", C.c_float),
+                ("alignment", C.c_int32), ("vertical", C.c_int32)]
+
+
+# every symbol include/wheeledlab_amd_raycaster.h declares
+RAYCASTER_SIGNATURES = {
+    "wl_raycast_version": (C.c_int, []),
+    "wl_raycast_scan": (C.c_int, [_P(WlRayCastParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 # include/wheeledlab_amd_obsnorm.h: empirical observation normalisation -- a header of its own, outside the drop-in step boundary
 WL_OBSNORM_VERSION = 1
 OBSNORM_MAX_DIM = 1 << 20
@@ -390,7 +407,8 @@ def load(path: str | None = None):
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES, **OBSNORM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES, **OBSNORM_SIGNATURES,
+                               **RAYCASTER_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -409,6 +427,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has lidar version {lib.wl_lidar_version()}, python expects {WL_LIDAR_VERSION}: rebuild")
     if lib.wl_obsnorm_version() != WL_OBSNORM_VERSION:
         raise HipExtensionMissing(f"{path} has obsnorm version {lib.wl_obsnorm_version()}, python expects {WL_OBSNORM_VERSION}: rebuild")
+    if lib.wl_raycast_version() != WL_RAYCASTER_VERSION:
+        raise HipExtensionMissing(f"{path} has ray-caster version {lib.wl_raycast_version()}, python expects {WL_RAYCASTER_VERSION}: rebuild")
     _lib = lib
     return lib
 

@@ -17,7 +17,7 @@ from . import _abi as A
 from .field import (DeviceHeightField, FlatPatches, TerrainLevels, _canonical_device, _launch_terrain_generator,  # noqa: F401
                     find_flat_patches, generate_heightfield, mesh_heightfield, pair_table)
 from .params import drift_params
-from .sensors import DepthCamera, LidarScanner, _cached_depth_camera, _field_key  # noqa: F401
+from .sensors import DepthCamera, LidarScanner, RayCaster, _cached_depth_camera, _field_key  # noqa: F401
 from .terrain import synthetic_heightfield
 
 

@@ -321,6 +321,18 @@ def _quat_apply(q: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     return v + 2.0 * (w * c + torch.cross(u, c, dim=-1))
 
 
+def _scan_once_per_step(data, scan):
+    """`scan()` of a sensor's data object, cached in `data._cached` per (batch.step_count, batch.pose_epoch): one scan per env.step(),
+    however often read, and a new one after anything that moved cars without a step (see CameraData); `data.caching` False (the
+    env's shape probe) or a batch without those counters: no caching"""
+    stamp = (getattr(data._b, "step_count", None), getattr(data._b, "pose_epoch", None))
+    if not data.caching or None in stamp:
+        return scan()
+    if data._cached[0] != stamp:
+        data._cached = (stamp, scan())
+    return data._cached[1]
+
+
 class LidarData:
     """`sensor.data` of a scene lidar (envs.sensors_cfg.LidarCfg; an IsaacLab RayCaster with a lidar pattern, un-vendored):
     `output["linear_depth"]` [N, B] -- the ranges `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized` read (mdp_sensors/
@@ -343,12 +355,7 @@ class LidarData:
 
     def ranges(self) -> torch.Tensor:
         """the raw scan of the current poses: max_range on a miss (cached per env step; do not write into it)"""
-        stamp = (getattr(self._b, "step_count", None), getattr(self._b, "pose_epoch", None))
-        if not self.caching or None in stamp:
-            return self.scanner().render(self._b)
-        if self._cached[0] != stamp:
-            self._cached = (stamp, self.scanner().render(self._b))
-        return self._cached[1]
+        return _scan_once_per_step(self, lambda: self.scanner().render(self._b))
 
     @property
     def output(self):
@@ -406,6 +413,127 @@ class LidarView:
     def __init__(self, batch, cfg):
         self.cfg = cfg
         self.data = LidarData(batch, cfg)
+        self.num_instances = batch.n
+
+
+class RayCasterSensorData:
+    """`sensor.data` of a scene ray caster (envs.sensors_cfg.RayCasterCfg with any pattern; IsaacLab's RayCaster, un-vendored), cast by
+    sensors.RayCaster (wl_raycast_scan) against the task's terrain: `ray_hits_w` [N, R, 3] (+inf where a ray meets nothing within
+    max_distance, as Warp's ray caster reports a miss) -- what `mdp.height_scan` reads -- `distances` [N, R] (max_distance on a miss),
+    `pos_w` [N, 3] and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like LidarData."""
+
+    def __init__(self, batch, cfg):
+        self._b, self._cfg, self._scanner = batch, cfg, None
+        self._cached = (None, None)       # ((step_count, pose_epoch), (distances, hits))
+        self.caching = True               # the env's constructor switches it off around its shape probe of the custom terms
+
+    def scanner(self):
+        if self._scanner is None:
+            from ..sensors import RayCaster
+            self._scanner = RayCaster(self._cfg, self._b.device)
+        return self._scanner
+
+    def _scan(self):
+        """(distances, hits) of the current poses (cached per env step; do not write into them)"""
+        return _scan_once_per_step(self, lambda: self.scanner().scan(self._b))
+
+    def _body_quat(self):
+        b = self._b
+        q = b.state[A.S_QW:A.S_QW + 4, : b.n].T
+        align = self.scanner().alignment
+        if align == "base":
+            return q
+        if align == "world":
+            return torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=b.device).expand(b.n, 4)
+        w, x, y, z = q.unbind(-1)          # the yaw alone, as LidarData
+        yaw = torch.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
+        zero = torch.zeros_like(yaw)
+        return torch.stack([torch.cos(0.5 * yaw), zero, zero, torch.sin(0.5 * yaw)], -1)
+
+    @property
+    def pos_w(self):
+        b = self._b
+        off = torch.tensor(self._cfg.offset_pos, dtype=torch.float32, device=b.device).expand(b.n, 3)
+        return b.state[A.S_PX:A.S_PX + 3, : b.n].T + _quat_apply(self._body_quat(), off)
+
+    @property
+    def quat_w(self):
+        """the sensor frame (x forward, y left, z up) in the world"""
+        mount = torch.tensor(self.scanner().params.offset_quat[:], dtype=torch.float32, device=self._b.device)
+        return _quat_mul(self._body_quat(), mount.expand(self._b.n, 4))
+
+    @property
+    def distances(self):
+        return self._scan()[0]
+
+    @property
+    def ray_hits_w(self):
+        return self._scan()[1]
+
+
+class RayCasterSensorView:
+    def __init__(self, batch, cfg):
+        self.cfg = cfg
+        self.data = RayCasterSensorData(batch, cfg)
+        self.num_instances = batch.n
+
+
+class RayCasterCameraData(RayCasterSensorData):
+    """`sensor.data` of a ray-caster camera (envs.sensors_cfg.RayCasterCameraCfg; IsaacLab's RayCasterCamera, un-vendored):
+    `output["distance_to_image_plane"]` / `output["distance_to_camera"]` [N, H, W, 1] -- what `mdp.camera_data_depth` / `raycast_depth`
+    read -- `intrinsic_matrices` [N, 3, 3], `pos_w`, `quat_w_world` / `quat_w_ros` / `quat_w_opengl` [N, 4].  A pixel whose ray meets
+    nothing within max_distance reads what depth_clipping_behavior says: max_distance, 0 or +inf."""
+
+    def __init__(self, batch, cfg):
+        super().__init__(batch, cfg)
+        self.beyond = {"max": float(cfg.max_distance), "zero": 0.0, "none": float("inf")}[cfg.depth_clipping_behavior]
+        self.image_shape = (int(cfg.pattern_cfg.height), int(cfg.pattern_cfg.width))
+
+    @property
+    def output(self):
+        return _RayCasterCameraOutputs(self)
+
+    @property
+    def intrinsic_matrices(self):
+        fx, fy, cx, cy = self._cfg.pattern_cfg.intrinsics()
+        k = torch.tensor([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=torch.float32, device=self._b.device)
+        return k.expand(self._b.n, 3, 3)
+
+    quat_w_world = RayCasterSensorData.quat_w
+
+    def _quat_w_in(self, convention):
+        from .sensors_cfg import CAMERA_CONVENTION_TO_WORLD
+        w, x, y, z = CAMERA_CONVENTION_TO_WORLD[convention]
+        back = torch.tensor([w, -x, -y, -z], dtype=torch.float32, device=self._b.device)
+        return _quat_mul(self.quat_w, back.expand(self._b.n, 4))
+
+    quat_w_ros = property(lambda self: self._quat_w_in("ros"))
+    quat_w_opengl = property(lambda self: self._quat_w_in("opengl"))
+
+
+class _RayCasterCameraOutputs:
+    def __init__(self, data):
+        self._d = data
+
+    def __getitem__(self, key):
+        d = self._d
+        if key not in self.keys():
+            raise KeyError(f"ray-caster camera data type {key!r} is not rendered here (it gives {self.keys()})")
+        dist, hits = d._scan()
+        if key == "distance_to_camera":      # the scan is the image-plane distance: Euclidean distance x the ray's cosine
+            dist = dist / d.scanner().ray_scale
+        # what a miss reads is applied per read, the scan itself is cached
+        dist = torch.where(torch.isinf(hits[..., 0]), torch.full_like(dist, d.beyond), dist)
+        return dist.view(dist.shape[0], *d.image_shape, 1)
+
+    def keys(self):
+        return ["distance_to_image_plane", "distance_to_camera"]
+
+
+class RayCasterCameraView:
+    def __init__(self, batch, cfg):
+        self.cfg = cfg
+        self.data = RayCasterCameraData(batch, cfg)
         self.num_instances = batch.n
 
 
@@ -487,10 +615,18 @@ class SceneView:
             self.sensors["height_scanner"] = RayCasterView(batch, cfg.height_scanner)
         if getattr(cfg, "camera", None) is not None:
             self.sensors["camera"] = CameraView(batch, cfg.camera)
-        from .sensors_cfg import LidarCfg
-        for name, value in (vars(cfg).items() if cfg is not None else ()):     # every lidar of the scene, under its attribute name
+        from .sensors_cfg import LidarCfg, RayCasterCameraCfg, RayCasterCfg
+        # every lidar, ray caster and ray-caster camera of the scene, under its attribute name (the elevation task's fused
+        # height_scanner above keeps its own view)
+        for name, value in (vars(cfg).items() if cfg is not None else ()):
+            if name in self.sensors:
+                continue
             if isinstance(value, LidarCfg):
                 self.sensors[name] = LidarView(batch, value)
+            elif isinstance(value, RayCasterCfg):
+                self.sensors[name] = RayCasterSensorView(batch, value)
+            elif isinstance(value, RayCasterCameraCfg):
+                self.sensors[name] = RayCasterCameraView(batch, value)
         self.terrain = getattr(cfg, "terrain", None)
         if getattr(batch, "levels", None) is not None or getattr(batch, "flat_patches", None):
             self.terrain = TerrainLevelsView(self.terrain, batch)

@@ -4,17 +4,131 @@ from .configclass import MISSING, configclass
 
 @configclass
 class GridPatternCfg:
+    """Parallel rays from a grid of points in the sensor's z = 0 plane, IsaacLab's `GridPatternCfg` field names.  Points per axis:
+    floor((size + 1e-9) / resolution) + 1 at -size / 2 + i resolution (IsaacLab's `arange(-s / 2, s / 2 + 1e-9, res)` [recalled]):
+    2.5 m at 0.1 m is 26 per axis.  `ordering` "xy": x fastest (what RayCasterData documents), "yx": y fastest.  `direction` is
+    normalised; every ray starts in the z = 0 plane whatever the direction."""
     size: tuple = MISSING
     resolution: float = MISSING
     direction: tuple = (0.0, 0.0, -1.0)
+    ordering: str = "xy"
+
+    def counts(self):
+        """(points along x, points along y)"""
+        import math
+        res = float(self.resolution)
+        if not (res > 0 and all(float(s) >= 0 for s in self.size)):
+            raise ValueError(f"grid pattern: resolution > 0 and size >= 0 (got {self})")
+        return tuple(int(math.floor((float(s) + 1e-9) / res)) + 1 for s in self.size[:2])
+
+    def rays(self):
+        """(starts [R, 3], unit directions [R, 3]) in the sensor frame, float64 numpy"""
+        import numpy as np
+        if self.ordering not in ("xy", "yx"):
+            raise ValueError(f"grid pattern ordering {self.ordering!r} ('xy' or 'yx')")
+        nx, ny = self.counts()
+        x = -0.5 * float(self.size[0]) + float(self.resolution) * np.arange(nx)
+        y = -0.5 * float(self.size[1]) + float(self.resolution) * np.arange(ny)
+        if self.ordering == "xy":
+            gy, gx = np.meshgrid(y, x, indexing="ij")
+        else:
+            gx, gy = np.meshgrid(x, y, indexing="ij")
+        starts = np.stack([gx.reshape(-1), gy.reshape(-1), np.zeros(nx * ny)], 1)
+        d = np.asarray(self.direction, np.float64)
+        n = np.linalg.norm(d)
+        if not (np.isfinite(n) and n > 0):
+            raise ValueError(f"grid pattern direction {self.direction} is not a direction")
+        return starts, np.repeat((d / n)[None], nx * ny, 0)
+
+
+@configclass
+class PinholeCameraPatternCfg:
+    """One ray through every pixel centre of a pinhole camera, row-major (IsaacLab's `PinholeCameraPatternCfg` field names; lengths in
+    one unit, as USD's millimetres).  fx = width focal_length / horizontal_aperture, fy = height focal_length / vertical_aperture
+    (`None`: square pixels, horizontal_aperture height / width), cx = width / 2 + horizontal_aperture_offset fx, cy = height / 2 +
+    vertical_aperture_offset fy [IsaacLab-recalled: the inverse of its `from_intrinsic_matrix`].  The rays are given in the WORLD
+    convention of a camera frame (x forward along the optical axis, y left, z up): pixel (row, col) looks along
+    (1, -(col + 0.5 - cx) / fx, -(row + 0.5 - cy) / fy), normalised -- the visual camera's rays (csrc/wl_depth_dev.h)."""
+    focal_length: float = 24.0
+    horizontal_aperture: float = 20.955
+    vertical_aperture: float = None
+    horizontal_aperture_offset: float = 0.0
+    vertical_aperture_offset: float = 0.0
+    width: int = MISSING
+    height: int = MISSING
+
+    def intrinsics(self):
+        """(fx, fy, cx, cy) in pixels"""
+        w, h = int(self.width), int(self.height)
+        va = self.vertical_aperture if self.vertical_aperture is not None else float(self.horizontal_aperture) * h / w
+        if not (w >= 1 and h >= 1 and float(self.focal_length) > 0 and float(self.horizontal_aperture) > 0 and float(va) > 0):
+            raise ValueError(f"pinhole pattern: width, height >= 1, focal length and apertures > 0 (got {self})")
+        fx, fy = w * float(self.focal_length) / float(self.horizontal_aperture), h * float(self.focal_length) / float(va)
+        return fx, fy, w / 2 + float(self.horizontal_aperture_offset) * fx, h / 2 + float(self.vertical_aperture_offset) * fy
+
+    def rays(self):
+        """(starts [H W, 3] (zeros), unit directions [H W, 3]) in the sensor frame (world convention), float64 numpy, row-major"""
+        import numpy as np
+        fx, fy, cx, cy = self.intrinsics()
+        r, c = np.meshgrid(np.arange(int(self.height)), np.arange(int(self.width)), indexing="ij")
+        d = np.stack([np.ones(r.size), -((c.reshape(-1) + 0.5 - cx) / fx), -((r.reshape(-1) + 0.5 - cy) / fy)], 1)
+        return np.zeros_like(d), d / np.linalg.norm(d, axis=1, keepdims=True)
 
 
 @configclass
 class RayCasterCfg:
+    """A ray caster of the scene (sensors.RayCaster, csrc/wl_raycast.hip): `pattern_cfg` is a GridPatternCfg, a LidarPatternCfg (all
+    rays from the sensor origin) or a PinholeCameraPatternCfg.  `ray_alignment` "base" (the body's full rotation turns offset and
+    rays), "yaw" (its yaw alone) or "world" (none); `None`: "yaw" if attach_yaw_only else "base".  Every RayCasterCfg attribute of a
+    scene config becomes `env.scene.sensors[name]` on every task; the elevation task's own `height_scanner` stays the fused scan."""
     prim_path: str = ""
     offset_pos: tuple = (0.0, 0.0, 0.0)
+    offset_rot: tuple = (1.0, 0.0, 0.0, 0.0)       # sensor frame against the body (w, x, y, z)
     attach_yaw_only: bool = True
+    ray_alignment: str = None
     pattern_cfg: GridPatternCfg = GridPatternCfg(size=(1.0, 1.0), resolution=0.1)
+    max_distance: float = 1e6
+    mesh_prim_paths: list = []
+    debug_vis: bool = False
+
+    def alignment(self) -> str:
+        a = self.ray_alignment if self.ray_alignment is not None else ("yaw" if self.attach_yaw_only else "base")
+        if a not in ("base", "yaw", "world"):
+            raise ValueError(f"ray_alignment {a!r} ('base', 'yaw' or 'world')")
+        return a
+
+
+def pattern_rays(pattern_cfg):
+    """(starts, unit directions) [R, 3] float64 of any pattern a ray caster accepts; a lidar pattern's beams leave the origin"""
+    import numpy as np
+    if isinstance(pattern_cfg, LidarPatternCfg):
+        d = pattern_cfg.directions()
+        return np.zeros_like(d), d
+    if isinstance(pattern_cfg, (GridPatternCfg, PinholeCameraPatternCfg)):
+        return pattern_cfg.rays()
+    raise TypeError(f"a ray caster takes a GridPatternCfg, LidarPatternCfg or PinholeCameraPatternCfg, not {type(pattern_cfg).__name__}")
+
+
+# sensor frame in the WORLD convention (x forward, y left, z up) against the same camera's frame in each convention (w, x, y, z):
+# offset_rot_world = offset_rot (x) CAMERA_CONVENTION_TO_WORLD[convention].  "ros": z forward, x right, y down; "opengl": -z forward,
+# x right, y up (IsaacLab's three offset conventions)
+CAMERA_CONVENTION_TO_WORLD = {"world": (1.0, 0.0, 0.0, 0.0), "ros": (0.5, 0.5, -0.5, 0.5), "opengl": (0.5, -0.5, 0.5, 0.5)}
+
+
+@configclass
+class RayCasterCameraCfg:
+    """A depth camera of any resolution and intrinsics as a ray caster (IsaacLab's `RayCasterCameraCfg`): `env.scene.sensors[name]
+    .data.output["distance_to_image_plane" | "distance_to_camera"]` [N, H, W, 1], `intrinsic_matrices`, `pos_w`, `quat_w_ros` /
+    `quat_w_world`.  The body's full rotation turns the camera.  `offset_rot` is read in `offset_convention`; what a pixel beyond
+    `max_distance` reads is `depth_clipping_behavior`'s, as TiledCameraCfg."""
+    prim_path: str = ""
+    pattern_cfg: PinholeCameraPatternCfg = PinholeCameraPatternCfg(width=80, height=60)
+    data_types: list = ["distance_to_image_plane"]
+    offset_pos: tuple = (0.0, 0.0, 0.0)
+    offset_rot: tuple = (1.0, 0.0, 0.0, 0.0)
+    offset_convention: str = "ros"
+    max_distance: float = 1e6
+    depth_clipping_behavior: str = "max"
     mesh_prim_paths: list = []
     debug_vis: bool = False
 

@@ -1,6 +1,6 @@
 """The sensors that read a DeviceHeightField from the poses of any batch: DepthCamera (the visual task's pinhole camera as a depth
-image) and LidarScanner (range scans), and the per-batch cache of cameras (_cached_depth_camera, keyed by _field_key).  A sensor
-takes a batch as an argument; this module imports field, never core.
+image), LidarScanner (range scans) and RayCaster (any ray table: grids, lidar fans, pinhole images), and the per-batch cache of
+cameras (_cached_depth_camera, keyed by _field_key).  A sensor takes a batch as an argument; this module imports field, never core.
 """
 from __future__ import annotations
 
@@ -47,7 +47,23 @@ class DepthCamera:
         return out
 
 
-class LidarScanner:
+class _TerrainSensor:
+    """what LidarScanner and RayCaster share: which terrain a batch's cars stand on"""
+    _plane = None
+
+    def camera_of(self, batch) -> DepthCamera:
+        """the terrain the batch's cars stand on, as CameraData does it: the visual-depth task's own camera, the elevation task's
+        heightfield, else the z = 0 plane (a 3 x 3 zero grid: beyond it the outside plane is z = 0 as well)"""
+        if getattr(batch, "camera", None) is not None:
+            return batch.camera
+        if batch.hf is not None:
+            return _cached_depth_camera(batch, batch.hf)
+        if self._plane is None:       # one tensor per sensor: the batch's camera cache keys on it
+            self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
+        return _cached_depth_camera(batch, self._plane)
+
+
+class LidarScanner(_TerrainSensor):
     """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
     (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
     field and pyramid come from the batch's cached DepthCamera, i.e. from the batch's DeviceHeightField (which owns the one pyramid).
@@ -75,18 +91,6 @@ class LidarScanner:
             raise ValueError(f"lidar offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
         self.params = A.WlLidarParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
                                       self.n_beams, self.max_range, int(bool(cfg.attach_yaw_only)))
-        self._plane = None
-
-    def camera_of(self, batch) -> DepthCamera:
-        """the terrain the batch's cars stand on, as CameraData does it: the visual-depth task's own camera, the elevation task's
-        heightfield, else the z = 0 plane (a 3 x 3 zero grid: beyond it the outside plane is z = 0 as well)"""
-        if getattr(batch, "camera", None) is not None:
-            return batch.camera
-        if batch.hf is not None:
-            return _cached_depth_camera(batch, batch.hf)
-        if self._plane is None:       # one tensor per scanner: the batch's camera cache keys on it
-            self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
-        return _cached_depth_camera(batch, self._plane)
 
     def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
         """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
@@ -97,6 +101,85 @@ class LidarScanner:
         A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr,
                                        self.beam_dirs.data_ptr(), out.data_ptr(), A.stream(self.device)), "wl_lidar_scan")
         return out
+
+
+def _quat_mul(a, b):
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return (aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+            aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw)
+
+
+class RayCaster(_TerrainSensor):
+    """A ray caster (envs.sensors_cfg.RayCasterCfg or RayCasterCameraCfg) casting its table of rays against the terrain from the poses
+    of ANY batch (wl_raycast_scan).  Owns the table, built once from the pattern: `ray_starts` / `ray_dirs` [R, 3] in the sensor
+    frame and, for a pinhole pattern, `ray_scale` [R] (each ray's cosine to the optical axis: distances come out as distances to
+    the image plane).  `vertical` -- every direction exactly (0, 0, -1), alignment yaw or world, mount about z only -- is decided here
+    and selects the kernel's column form (one bilinear sample per ray instead of a walk); `vertical=False` forces the walk.
+    scan() -> (distances [n, R], hits [n, R, 3]): the distance clipped at max_distance (max_distance on a miss, 0 from under the
+    terrain; times ray_scale), the hit point (+inf on a miss)."""
+
+    def __init__(self, cfg, device="cuda:0", vertical: bool | None = None):
+        import numpy as np
+
+        from .envs.sensors_cfg import CAMERA_CONVENTION_TO_WORLD, PinholeCameraPatternCfg, RayCasterCameraCfg, pattern_rays
+        self.lib = A.load()
+        self.device = _canonical_device(device)
+        if self.device.type != "cuda":
+            raise A.HipExtensionMissing("RayCaster needs a HIP device; there is no CPU path")
+        self.cfg = cfg
+        starts, dirs = pattern_rays(cfg.pattern_cfg)
+        self.n_rays = int(dirs.shape[0])
+        if not 1 <= self.n_rays <= A.RAYCAST_MAX_RAYS:
+            raise ValueError(f"a ray pattern of {self.n_rays} rays (1 .. {A.RAYCAST_MAX_RAYS})")
+        self.max_distance = float(cfg.max_distance)
+        if not (math.isfinite(self.max_distance) and self.max_distance > 0):
+            raise ValueError(f"ray caster max_distance must be positive and finite, got {cfg.max_distance}")
+        q = tuple(float(v) for v in cfg.offset_rot)
+        is_camera = isinstance(cfg, RayCasterCameraCfg)
+        if is_camera:
+            if cfg.offset_convention not in CAMERA_CONVENTION_TO_WORLD:
+                raise ValueError(f"offset_convention {cfg.offset_convention!r} (one of {sorted(CAMERA_CONVENTION_TO_WORLD)})")
+            q = _quat_mul(q, CAMERA_CONVENTION_TO_WORLD[cfg.offset_convention])
+        qn = math.sqrt(sum(v * v for v in q))
+        if not (math.isfinite(qn) and qn > 0):
+            raise ValueError(f"ray caster offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
+        self.alignment = "base" if is_camera else cfg.alignment()
+        column = bool((dirs == np.array([0.0, 0.0, -1.0])).all()) and self.alignment in ("yaw", "world") and q[1] == 0.0 and q[2] == 0.0
+        if vertical and not column:
+            raise ValueError("the column form needs directions (0, 0, -1), yaw or world alignment and a mount about z alone")
+        self.vertical = column if vertical is None else bool(vertical)
+        to_dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).contiguous().to(self.device)
+        self.ray_starts, self.ray_dirs = to_dev(starts), to_dev(dirs)
+        # image-plane distance = Euclidean distance x the ray's x component (the optical axis is the sensor's +x)
+        self.ray_scale = to_dev(dirs[:, 0]) if isinstance(cfg.pattern_cfg, PinholeCameraPatternCfg) else None
+        self.params = A.WlRayCastParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
+                                        self.n_rays, self.max_distance, A.RAYCAST_ALIGNMENTS[self.alignment], int(self.vertical))
+
+    def scan(self, batch, camera: DepthCamera | None = None, dist: torch.Tensor | bool = True, hits: torch.Tensor | bool = True):
+        """one launch over the batch's current poses -> (distances or None, hits or None); `dist` / `hits`: a tensor to fill, True for
+        a new one, False to leave that output out; `camera`: another terrain (a DepthCamera) than the batch's own"""
+        cam = camera if camera is not None else self.camera_of(batch)
+        if dist is True:
+            dist = torch.empty(batch.n, self.n_rays, dtype=torch.float32, device=self.device)
+        if hits is True:
+            hits = torch.empty(batch.n, self.n_rays, 3, dtype=torch.float32, device=self.device)
+        dist, hits = (None if dist is False else dist), (None if hits is False else hits)
+        for t, shape in ((dist, (batch.n, self.n_rays)), (hits, (batch.n, self.n_rays, 3))):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.shape == shape)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        A.check(self.lib.wl_raycast_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr, self.ray_starts.data_ptr(),
+                                         None if self.vertical else self.ray_dirs.data_ptr(), ptr(self.ray_scale), ptr(dist), ptr(hits),
+                                         A.stream(self.device)), "wl_raycast_scan")
+        return dist, hits
+
+    def render(self, batch, camera: DepthCamera | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """distances [batch.n, R]"""
+        return self.scan(batch, camera, dist=True if out is None else out, hits=False)[0]
+
+    def hits(self, batch, camera: DepthCamera | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """hit points [batch.n, R, 3] in the world, +inf on a miss"""
+        return self.scan(batch, camera, dist=False, hits=True if out is None else out)[1]
 
 
 def _field_key(heightfield) -> tuple:
