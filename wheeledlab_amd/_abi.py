@@ -386,6 +386,24 @@ OBSNORM_SIGNATURES = {
     "wl_obsnorm_fold": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/wheeledlab_amd_history.h: observation history -- a header of its own, outside the drop-in step boundary
+WL_OBSHIST_VERSION = 1
+OBSHIST_MAX_TERMS = 64
+OBSHIST_MAX_FRAMES = 64
+OBSHIST_MAX_DIM = 1 << 20
+
+
+class WlObsHistoryTerm(C.Structure):
+    _fields_ = [("src_off", C.c_int32), ("width", C.c_int32), ("frames", C.c_int32), ("dst_off", C.c_int32)]
+
+
+# every symbol include/wheeledlab_amd_history.h declares
+OBSHIST_SIGNATURES = {
+    "wl_obs_history_version": (C.c_int, []),
+    "wl_obs_history_width": (C.c_int64, [_P(WlObsHistoryTerm), _i32, _i32]),
+    "wl_obs_history_push": (C.c_int, [_i32, _i32, _vp, _i64, _P(WlObsHistoryTerm), _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -408,7 +426,7 @@ def load(path: str | None = None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES, **OBSNORM_SIGNATURES,
-                               **RAYCASTER_SIGNATURES}.items():
+                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -429,6 +447,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has obsnorm version {lib.wl_obsnorm_version()}, python expects {WL_OBSNORM_VERSION}: rebuild")
     if lib.wl_raycast_version() != WL_RAYCASTER_VERSION:
         raise HipExtensionMissing(f"{path} has ray-caster version {lib.wl_raycast_version()}, python expects {WL_RAYCASTER_VERSION}: rebuild")
+    if lib.wl_obs_history_version() != WL_OBSHIST_VERSION:
+        raise HipExtensionMissing(f"{path} has observation-history version {lib.wl_obs_history_version()}, python expects {WL_OBSHIST_VERSION}: rebuild")
     _lib = lib
     return lib
 

@@ -224,6 +224,8 @@ class DriftBatch(_EnvBatch):
     """n drift envs resident on one GPU (csrc/wl_drift.hip)."""
 
     OBS_DIM = 14
+    OBS_TERM_WIDTHS = (3, 3, 3, 3, 2)      # root_pos_w | root_euler_xyz | base_lin_vel | base_ang_vel | last_action
+    assert sum(OBS_TERM_WIDTHS) == OBS_DIM
     LANES = (0, 1, 2, 4)           # 2: lane form with the scalar wheel loop (drift only)
     _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_drift_reset", "wl_drift_step", "wl_drift_rollout", "wl_drift_rollout_persistent"
     _PERSISTENT_NEEDS_ROWS = False
@@ -296,6 +298,9 @@ class ElevBatch(_EnvBatch):
     """n elevation-task envs on one GPU (same SoA state matrix; rows WL_S_CMD_* carry the goal command)."""
 
     OBS_DIM = A.ELEV_OBS_DIM
+    # goal_relative_xyz (x, y) | root_euler_xyz | base_lin_vel | base_ang_vel | last_action | world_height_map
+    OBS_TERM_WIDTHS = (2, 3, 3, 3, 2, A.ELEV_SCAN_N * A.ELEV_SCAN_N)
+    assert sum(OBS_TERM_WIDTHS) == OBS_DIM
     _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_elev_reset", "wl_elev_step", "wl_elev_rollout", "wl_elev_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params: A.WlElevParams | None = None, seed: int = 42,
@@ -362,6 +367,8 @@ class VisualBatch(_EnvBatch):
     """n visual-task envs on one GPU: flat black/white traversability plane + ray-cast grey camera."""
 
     OBS_DIM = A.VIS_OBS_DIM
+    OBS_TERM_WIDTHS = (A.VIS_NPIX, 3, 3, 2)      # camera | base_lin_vel | base_ang_vel | last_action
+    assert sum(OBS_TERM_WIDTHS) == OBS_DIM
     _C_RESET, _C_STEP, _C_ROLLOUT, _C_PERSISTENT = "wl_visual_reset", "wl_visual_step", "wl_visual_rollout", "wl_visual_rollout_persistent"
 
     def __init__(self, n_envs: int, device="cuda:0", params=None, seed: int = 42, env_offset: int = 0, trav_map=None,
@@ -425,6 +432,8 @@ class VisualDepthBatch(VisualBatch):
     cells = the terrain's 40 m square, generated like the reference's from the seed)."""
 
     OBS_DIM = A.VISDEPTH_OBS_DIM
+    OBS_TERM_WIDTHS = (A.VISDEPTH_NPIX, 3, 3, 2)      # depth | base_lin_vel | base_ang_vel | last_action
+    assert sum(OBS_TERM_WIDTHS) == OBS_DIM
     _C_RESET = "wl_visual_reset_hf"
 
     def __init__(self, n_envs: int, device="cuda:0", params=None, seed: int = 42, env_offset: int = 0, trav_map=None,

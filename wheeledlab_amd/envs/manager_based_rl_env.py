@@ -22,6 +22,7 @@ from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
 from ..field import assemble_terrain
 from .configclass import fields_of
 from .flatten import flatten_cfg
+from .history import ObsHistory, resolve as resolve_history
 from .scene import SceneView
 
 
@@ -149,8 +150,15 @@ class ObservationManager:
         self.group_obs_dim = {"policy": (env._batch.OBS_DIM,)}      # grown by the env once its custom terms are sized
         self.active_terms = {"policy": [k for k, v in fields_of(env.cfg.observations.policy) if hasattr(v, "func")]}
 
-    def compute(self):
-        return {"policy": self._env._with_custom_obs(self._env._batch.observe())}
+    def compute(self, update_history: bool = False):
+        """the current observation.  With observation history: the stacked rows as they stand -- reading pushes nothing, and
+        `update_history` (IsaacLab's argument) is accepted and changes nothing: only step() / collect_step() advance the history"""
+        env = self._env
+        if env._history is not None:
+            if not env._history.filled:       # read before the first reset: every frame is the current one
+                env._history.push(env._with_custom_obs(env._batch.observe()), env._batch.terminated, fresh=True)
+            return {"policy": env._history.current()}
+        return {"policy": env._with_custom_obs(env._batch.observe())}
 
 
 def episode_log_keys(reward_slots, term_names):
@@ -283,17 +291,30 @@ class ManagerBasedRLEnv:
         # into the runner's storage) are off whenever any kind of custom term is registered
         self._has_custom_rewards = bool(self._custom_rew or self._custom_term or self._custom_obs)
         self._obs_dim = self._batch.OBS_DIM
+        self._history = None
+        custom_widths = []
         if self._custom_obs:
             # shape probe on the un-reset state: nothing it renders may be kept (the scene camera caches per step)
             cams = [s.data for s in self.scene.sensors.values() if hasattr(s.data, "caching")]
             for c in cams:
                 c.caching = False
-            self._obs_dim += sum(self._eval_obs_term(t).shape[1] for _, t in self._custom_obs)
+            custom_widths = [int(self._eval_obs_term(t).shape[1]) for _, t in self._custom_obs]
+            self._obs_dim += sum(custom_widths)
             for c in cams:
                 c.caching = True
             self.observation_manager.group_obs_dim["policy"] = (self._obs_dim,)
             self.single_observation_space = {"policy": Box(-math.inf, math.inf, (self._obs_dim,))}
             self.observation_space = {"policy": Box(-math.inf, math.inf, (self.num_envs, self._obs_dim))}
+        # observation history (envs/history.py): with any term keeping more than one frame the env owns the stacked rows; without,
+        # nothing is built and no path below changes
+        obs_terms = [(k, v) for k, v in fields_of(cfg.observations.policy) if hasattr(v, "func")]
+        layout = resolve_history(cfg.observations.policy, obs_terms, list(self._batch.OBS_TERM_WIDTHS) + custom_widths)
+        if layout is not None:
+            assert layout.D == self._obs_dim
+            self._history = ObsHistory(layout, self.num_envs, self.device)
+            self.observation_manager.group_obs_dim["policy"] = layout.shape
+            self.single_observation_space = {"policy": Box(-math.inf, math.inf, layout.shape)}
+            self.observation_space = {"policy": Box(-math.inf, math.inf, (self.num_envs, *layout.shape))}
         self._has_curriculum = bool(flat.curriculum)
         self._clip_actions = False
         self._sim_step_counter = 0
@@ -346,7 +367,10 @@ class ManagerBasedRLEnv:
         self.extras = {}
         for t in self._custom_epsum.values():
             t.zero_()
-        self.obs_buf = {"policy": self._with_custom_obs(self._batch.observe())}
+        obs = self._with_custom_obs(self._batch.observe())
+        if self._history is not None:         # every frame of every env is the reset frame
+            obs = self._history.push(obs, self._batch.terminated, fresh=True)
+        self.obs_buf = {"policy": obs}
         return self.obs_buf, self.extras
 
     def redeal_patches(self, epoch: int):
@@ -379,6 +403,8 @@ class ManagerBasedRLEnv:
         self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
+        if self._history is not None:         # the flags the step returns: an env they name starts over with this frame
+            obs = self._history.push(obs, terminated, truncated)
         self._curriculum_at_boundary(lambda: terminated | truncated)
         if self.cfg.sync_episode_log:
             if bool((terminated | truncated).any()):
@@ -408,8 +434,14 @@ class ManagerBasedRLEnv:
         self.action_manager.prev_action = a
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()
-        b.rollout(storage.actions[k:k + 1], storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
-                  storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
+        if self._history is None:
+            b.rollout(storage.actions[k:k + 1], storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
+                      storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
+        else:
+            # the raw row into the batch's own, then ONE launch from stacked row k to stacked row k + 1 of the storage
+            b.rollout(storage.actions[k:k + 1], b.obs.unsqueeze(0), storage.rewards[k:k + 1],
+                      storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
+            self._history.push_into(b.obs, storage.observations[k], storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
@@ -441,7 +473,7 @@ class ManagerBasedRLEnv:
 
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
-        return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards
+        return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._history is None
                 and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
 
     def collect_rollout(self, actor_critic, storage):
@@ -450,6 +482,8 @@ class ManagerBasedRLEnv:
         observation rows in LDS); observation row 0 of the storage must hold the current observation.  The critic's values
         are NOT filled in (not needed to step): evaluate storage.observations in one batched pass afterwards.  The rollout is
         cut at curriculum boundaries exactly as rollout_policy() cuts the drift task's; call finish_collection() after it."""
+        if self._history is not None:
+            raise ValueError("observation history is pushed between steps; use step() or collect_step()")
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
         b = self._batch
@@ -459,8 +493,11 @@ class ManagerBasedRLEnv:
     def finish_collection(self, storage, n_steps: int | None = None):
         """after the last collect_step(): the env's own observation buffer and episode log catch up with the storage"""
         b, K = self._batch, storage.n_steps if n_steps is None else n_steps
-        b.obs.copy_(storage.observations[K])
-        self.obs_buf = {"policy": b.obs}
+        if self._history is not None:         # (b.obs already holds the last raw row)
+            self.obs_buf = {"policy": self._history.adopt(storage.observations[K])}
+        else:
+            b.obs.copy_(storage.observations[K])
+            self.obs_buf = {"policy": b.obs}
         self.extras["log"] = self._episode_log(None) if b.metrics_slots == 1 else EpisodeLog(
             self.episode_metrics(window=K, reduce_ranks=False), None, self._log_keys, self.max_episode_length_s)
 
@@ -474,6 +511,8 @@ class ManagerBasedRLEnv:
             raise NotImplementedError("fused policy rollouts exist for the drift task (14-dim observation)")
         if self._has_custom_rewards:
             raise ValueError("custom (torch) reward terms run between steps; use step()")
+        if self._history is not None:
+            raise ValueError("observation history is pushed between steps; use step() or collect_step()")
         b, K = self._batch, storage.n_steps
         self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))

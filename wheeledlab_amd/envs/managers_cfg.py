@@ -72,12 +72,19 @@ class ObservationTermCfg(ManagerTermBaseCfg):
     noise = None
     clip = None
     scale = None
+    # frames of this term the policy sees, oldest first (0 and 1: the current frame alone); envs/history.py
+    history_length: int = 0
+    flatten_history_dim: bool = True
 
 
 @configclass
 class ObservationGroupCfg:
     concatenate_terms: bool = True
     enable_corruption: bool = False
+    # not None: overrides history_length AND flatten_history_dim of every term of the group; flatten_history_dim False gives
+    # [N, history_length, D] (time-major) instead of the term-major flat row
+    history_length = None
+    flatten_history_dim: bool = True
 
 
 @configclass

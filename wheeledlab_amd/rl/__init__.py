@@ -48,7 +48,11 @@ class RslRlVecEnvWrapper:
         self.device = self.unwrapped.device
         self.max_episode_length = self.unwrapped.max_episode_length
         self.num_actions = self.unwrapped.action_manager.total_action_dim
-        self.num_obs = self.unwrapped.observation_manager.group_obs_dim["policy"][0]
+        shape = self.unwrapped.observation_manager.group_obs_dim["policy"]
+        if len(shape) != 1:
+            raise ValueError(f"RslRlVecEnvWrapper needs a flat policy observation, the group gives {tuple(shape)} per env: set "
+                             "observations.policy.flatten_history_dim=True")
+        self.num_obs = shape[0]
         self.num_privileged_obs = 0
         self.env.reset()
 
