@@ -26,7 +26,9 @@ extern "C" {
 #endif
 
 #define WL_ABI_VERSION 24
-/* Counts layout changes INSIDE an ABI version (wl_revision(); the python loader checks both).  1: WlElevParams.levels. */
+/* Counts layout changes INSIDE an ABI version (wl_revision(); the python loader checks both).  1: WlElevParams.levels.
+ * Still 1 with WL_FLAG_STEP_LAUNCHES and wl_drift_rollout's launch plan: a new flag bit and fewer launches for the same
+ * results change no layout, and a library without them refuses the bit (WL_EINVAL) instead of misreading it. */
 #define WL_ABI_REVISION 1
 
 enum WlStatus { WL_OK = 0, WL_EINVAL = -1, WL_ELAUNCH = -2, WL_EALIGN = -3, WL_ENODEV = -4 };
@@ -178,7 +180,10 @@ typedef struct WlEnvBuffers {
 #define WL_FLAG_STREAM 1       /* streaming forms: rows / observation rows / outputs written with non-temporal (sc1 nt) stores; */
                                /* drift: the lane-per-env streaming instantiation (`lanes` must not be 4)                        */
 #define WL_FLAG_NO_STREAM 2    /* cache-allocating stores whatever the batch size                                                */
-#define WL_FLAG_MASK 3
+#define WL_FLAG_STEP_LAUNCHES 32 /* wl_drift_rollout: one launch of the step kernel per step whatever the launch plan would   */
+                               /* choose (probes and tests of the step kernel; the other tasks ignore it).  Bits 4, 8 and 16  */
+                               /* belonged to retired forms and stay refused                                                     */
+#define WL_FLAG_MASK (WL_FLAG_STREAM | WL_FLAG_NO_STREAM | WL_FLAG_STEP_LAUNCHES)
 
 /* ---- outputs of one step -------------------------------------------------------------------------------- */
 typedef struct WlStepOut {
@@ -214,9 +219,16 @@ int wl_drift_step(const WlDriftParams* p, const WlEnvBuffers* b, const float* ac
 /*
  * K consecutive fused steps with pre-staged actions [K][n][2]; outputs of step k are written at
  * obs + k*obs_step_stride (floats), reward + k*vec_step_stride, terminated/truncated + k*vec_step_stride
- * (strides 0 = overwrite).  This is the rollout inner loop of the reference's runner
+ * (strides 0 = overwrite; `dones` may be NULL).  This is the rollout inner loop of the reference's runner
  * (modified_rsl_rl_runner.py:70-73) minus the policy.
+ * Same results as n_steps calls of wl_drift_step (outputs, state, episode_len bit for bit; the metric accumulators up to
+ * the order of their float atomics), in as few launches as the metric ring allows: with ONE metric accumulator
+ * (metrics_slots == 1), n_steps >= 2 and a batch that steps in the quad form (`lanes` 0 up to 32 768 envs, or 4; not
+ * WL_FLAG_STREAM) the steps run as launches of the persistent rollout kernel, at most WL_DRIFT_ROLLOUT_CHUNK_STEPS each, the envs' rows in
+ * registers from step to step.  With a metric ring (metrics_slots > 1: step k's counts belong in slot k % R, cleared
+ * behind a kernel boundary), a forced lane form, one step, or WL_FLAG_STEP_LAUNCHES: one launch of the step kernel per step.
  */
+#define WL_DRIFT_ROLLOUT_CHUNK_STEPS 1024   /* steps one launch of the rollout kernel covers at most in wl_drift_rollout */
 int wl_drift_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const float* actions, const WlStepOut* out,
                      int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps, uint64_t seed,
                      uint64_t step0, void* stream);

@@ -1,6 +1,8 @@
 """Workload for rocprofv3 --pmc / --kernel-trace passes: K launches of one task's hot kernel(s) at n envs exactly as bench.py
 launches them, nothing else on the GPU.
   pmc_run.py <n> <K> [lanes]                 fused drift step (rollout storage, no int64 `dones` row)  [round-1/2 form]
+                                             one launch of the step kernel per step (FLAG_STEP_LAUNCHES); WL_ROLLOUT_PLAN=1:
+                                             as bench.py's rollout() calls run, by wl_drift_rollout's launch plan
   pmc_run.py drift|elev|visual|depth <n> <K> [lanes]
 elev / visual: K env.step()s (outputs overwritten in place, as bench.py's other_tasks section); depth: K renders of the
 depth camera over n elevation-task cars standing on the synthetic terrain (bench.py's depth section)."""
@@ -25,8 +27,8 @@ if task == "drift":
     env.reset()
     if lanes:
         env.set_lanes(lanes)   # force a step-kernel form (WlEnvBuffers.lanes)
-    if flags:
-        env.set_flags(flags)
+    from wheeledlab_amd._abi import FLAG_STEP_LAUNCHES
+    env.set_flags(flags | (0 if os.environ.get("WL_ROLLOUT_PLAN") == "1" else FLAG_STEP_LAUNCHES))
     a = torch.rand(K, n, 2, device=dev) * 2 - 1
     obs = torch.zeros(K, n, 14, device=dev)
     rew = torch.zeros(K, n, device=dev)

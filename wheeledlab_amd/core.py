@@ -135,7 +135,8 @@ class _EnvBatch:
 
     def set_flags(self, flags: int = 0):
         """WlEnvBuffers.flags (_abi.FLAG_*): force an instantiation the launchers otherwise pick from the batch size -- the
-        streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa)."""
+        streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa).
+        FLAG_STEP_LAUNCHES keeps DriftBatch.rollout() on one step-kernel launch per step (probes and tests of that kernel)."""
         self._bufs.flags = int(flags)
 
     def set_lanes(self, lanes: int = 0):
@@ -174,7 +175,8 @@ class _EnvBatch:
     def rollout(self, actions: torch.Tensor, obs_out=None, rew_out=None, term_out=None, trunc_out=None, dones_out=None,
                 persistent: bool = False):
         """K fused steps with pre-staged actions [K, n, 2]; optional [K, ...] output storage (else the batch's own rows,
-        overwritten).  persistent=True runs them as ONE launch with the state in registers (_C_PERSISTENT: quad form,
+        overwritten): one launch per step (DriftBatch: fewer where the results allow, see its rollout()).
+        persistent=True runs them as ONE launch with the state in registers (_C_PERSISTENT: quad form,
         n <= 32 768; the elevation scan / the visual camera of step k overlapped with step k + 1); same results."""
         self._rollout(actions, (obs_out, rew_out, term_out, trunc_out, dones_out), persistent)
 
@@ -262,8 +264,12 @@ class DriftBatch(_EnvBatch):
     def rollout(self, actions: torch.Tensor, obs_out: torch.Tensor | None = None, rew_out: torch.Tensor | None = None,
                 term_out: torch.Tensor | None = None, trunc_out: torch.Tensor | None = None, persistent: bool = False,
                 dones_out: torch.Tensor | None = None):
-        """K fused steps with pre-staged actions [K,n,2]; optional [K,...] output storage (else overwrite).
-        persistent=True runs them as ONE launch with the state held in registers (wl_drift_rollout_persistent)."""
+        """K fused steps with pre-staged actions [K,n,2]; optional [K,...] output storage (else overwrite).  Same results as K
+        calls of step(), in as few launches as the metric ring allows (wl_drift_rollout): with metrics_slots == 1, K >= 2 and a
+        batch that steps in the quad form, launches of the persistent rollout kernel (<= 1024 steps each, the state in registers
+        from step to step); with a metric ring, a forced lane / streaming form or FLAG_STEP_LAUNCHES, one launch per step.
+        persistent=True asks for ONE launch outright (wl_drift_rollout_persistent): on a metric ring it folds the K steps'
+        counts into one slot."""
         self._rollout(actions, (obs_out, rew_out, term_out, trunc_out, dones_out), persistent)
 
     def rollout_policy(self, actor_critic, storage, evaluate_critic: bool = True, start: int = 0, count: int | None = None):

@@ -310,6 +310,42 @@ int wl_drift_step(const WlDriftParams* p, const WlEnvBuffers* b, const float* ac
     return launch_status();
 }
 
+// one drift_rollout_kernel launch: `n_steps` steps from `step0` with the envs' rows in registers (actions / out: those of step0)
+static void launch_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const VehDerived& vd, const float2* actions, const WlStepOut& out,
+                           int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps, uint64_t seed, uint64_t step0,
+                           hipStream_t stream) {
+    const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
+    launch_quad(b->n_envs, [&](auto qb, int qgrid) {
+        drift_rollout_kernel<FlatGround, decltype(qb)::value><<<qgrid, qb.value, 0, stream>>>(
+            *p, *b, actions, out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, vd, ms);
+    });
+}
+
+// wl_drift_rollout's launch plan.  The caller hands over all n_steps actions and nothing but the next step reads the state in
+// between, so the steps run as drift_rollout_kernel launches (the rows in registers: no launch boundary, row store and cold row
+// read per step) wherever that computes what n_steps launches of the step kernel compute:
+//   - the quad form is the one the batch would step in (the rollout kernel is a quad kernel; a forced lane or streaming form
+//     stays what the caller forced);
+//   - ONE metric accumulator.  With a ring of R > 1 slots the stepped form leaves step k's counts in slot k % R, and each launch
+//     clears the next slot behind a kernel boundary; inside one launch there is no grid-wide order in which a slot could be
+//     cleared between two steps, so a ring keeps its per-step launches (wl_drift_rollout_persistent folds the steps into one
+//     slot instead: its own contract);
+//   - WL_FLAG_STEP_LAUNCHES is not set (probes and tests of the step kernel);
+//   - at most WL_ROLLOUT_PLAN_MAX_ENVS envs.
+// One launch covers at most kRolloutChunkSteps steps (~3.5 ms at 4096 envs), so that a very long call does not hold the
+// device for seconds while other streams wait; the chunks continue at step0 + done, their output rows at step_out_at(done).
+constexpr int32_t kRolloutChunkSteps = WL_DRIFT_ROLLOUT_CHUNK_STEPS;
+#ifndef WL_ROLLOUT_PLAN_MAX_ENVS
+#define WL_ROLLOUT_PLAN_MAX_ENVS 32768   // = WL_QUAD_MAX_ENVS: the one-launch form wins at every quad size.  us per step of 128-step
+                                         // rollout() calls (tools/ab_probe.py drift<n> / driftplan<n>, best of 4 blocks, 3 rounds
+                                         // within 0.03 us), per-step launches / launch plan: 1024 envs 5.75 / 3.23, 4096 envs
+                                         // 6.06 / 3.36, 16 384 envs 7.68 / 3.31, 32 768 envs 10.24 / 4.73
+#endif
+static bool plan_one_launch(const WlEnvBuffers* b, int32_t n_steps) {
+    return n_steps >= 2 && use_quad(b) && !(b->flags & (WL_FLAG_STREAM | WL_FLAG_STEP_LAUNCHES)) && b->metrics_slots == 1 &&
+           b->n_envs <= WL_ROLLOUT_PLAN_MAX_ENVS;
+}
+
 int wl_drift_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const float* actions, const WlStepOut* out,
                      int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps, uint64_t seed, uint64_t step0,
                      void* stream) {
@@ -318,6 +354,13 @@ int wl_drift_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const float*
     if (!actions || !step_out_ok(out) || n_steps < 0) return WL_EINVAL;
     clear_error();
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
+    if (plan_one_launch(b, n_steps)) {
+        for (int32_t done = 0; done < n_steps; done += kRolloutChunkSteps)
+            launch_rollout(p, b, vd, (const float2*)(actions + (int64_t)done * b->n_envs * 2), step_out_at(*out, done, obs_step_stride, vec_step_stride),
+                           obs_step_stride, vec_step_stride, std::min(kRolloutChunkSteps, n_steps - done), seed, step0 + (uint64_t)done,
+                           (hipStream_t)stream);
+        return launch_status();
+    }
     for (int k = 0; k < n_steps; ++k)
         launch_step(p, b, vd, (const float2*)(actions + (int64_t)k * b->n_envs * 2), nullptr, step_out_at(*out, k, obs_step_stride, vec_step_stride),
                     seed, step0 + (uint64_t)k, (hipStream_t)stream);
@@ -333,11 +376,7 @@ int wl_drift_rollout_persistent(const WlDriftParams* p, const WlEnvBuffers* b, c
     if (ring_aliases(b, n_steps)) return WL_EINVAL;
     clear_error();
     const VehDerived vd = derive_vehicle(p->vehicle, p->sim_dt, p->decimation);
-    const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
-    launch_quad(b->n_envs, [&](auto qb, int qgrid) {
-        drift_rollout_kernel<FlatGround, decltype(qb)::value><<<qgrid, qb.value, 0, (hipStream_t)stream>>>(
-            *p, *b, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, vd, ms);
-    });
+    launch_rollout(p, b, vd, (const float2*)actions, *out, obs_step_stride, vec_step_stride, n_steps, seed, step0, (hipStream_t)stream);
     return launch_status();
 }
 

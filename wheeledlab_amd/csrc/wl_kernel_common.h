@@ -257,7 +257,8 @@ inline void launch_quad(int n_envs, F&& launch) {
 #ifndef WL_LOWREG_WAVES
 #define WL_LOWREG_WAVES 5   // .. and fenced
 #endif
-// WlEnvBuffers.flags: valid combinations only (a flag and its opposite together are refused)
+// WlEnvBuffers.flags: valid combinations only (a flag and its opposite together are refused; WL_FLAG_STEP_LAUNCHES goes with
+// either: it chooses how wl_drift_rollout launches, not a kernel form)
 inline bool flags_ok(const WlEnvBuffers* b) {
     const int f = b->flags;
     if (f & ~WL_FLAG_MASK) return false;
