@@ -28,7 +28,8 @@ extern "C" {
 #define WL_ABI_VERSION 24
 /* Counts layout changes INSIDE an ABI version (wl_revision(); the python loader checks both).  1: WlElevParams.levels.
  * Still 1 with WL_FLAG_STEP_LAUNCHES and wl_drift_rollout's launch plan: a new flag bit and fewer launches for the same
- * results change no layout, and a library without them refuses the bit (WL_EINVAL) instead of misreading it. */
+ * results change no layout, and a library without them refuses the bit (WL_EINVAL) instead of misreading it.  Likewise
+ * WL_FLAG_ROLLOUT_ONE_ROLE and the two-role rollout kernel behind the same entry points. */
 #define WL_ABI_REVISION 1
 
 enum WlStatus { WL_OK = 0, WL_EINVAL = -1, WL_ELAUNCH = -2, WL_EALIGN = -3, WL_ENODEV = -4 };
@@ -183,7 +184,11 @@ typedef struct WlEnvBuffers {
 #define WL_FLAG_STEP_LAUNCHES 32 /* wl_drift_rollout: one launch of the step kernel per step whatever the launch plan would   */
                                /* choose (probes and tests of the step kernel; the other tasks ignore it).  Bits 4, 8 and 16  */
                                /* belonged to retired forms and stay refused                                                     */
-#define WL_FLAG_MASK (WL_FLAG_STREAM | WL_FLAG_NO_STREAM | WL_FLAG_STEP_LAUNCHES)
+#define WL_FLAG_ROLLOUT_ONE_ROLE 64 /* rollout kernel launches (wl_drift_rollout's plan, wl_drift_rollout_persistent): the      */
+                               /* single-role kernel whatever the env count -- one wavefront per 16 envs does the whole step;  */
+                               /* without the bit, up to WL_ROLLOUT_SPLIT_MAX_ENVS envs (csrc/wl_drift.hip) run the two-role   */
+                               /* kernel: a state and an output wavefront per 16 envs, pipelined across steps.  Same results   */
+#define WL_FLAG_MASK (WL_FLAG_STREAM | WL_FLAG_NO_STREAM | WL_FLAG_STEP_LAUNCHES | WL_FLAG_ROLLOUT_ONE_ROLE)
 
 /* ---- outputs of one step -------------------------------------------------------------------------------- */
 typedef struct WlStepOut {
@@ -225,7 +230,8 @@ int wl_drift_step(const WlDriftParams* p, const WlEnvBuffers* b, const float* ac
  * the order of their float atomics), in as few launches as the metric ring allows: with ONE metric accumulator
  * (metrics_slots == 1), n_steps >= 2 and a batch that steps in the quad form (`lanes` 0 up to 32 768 envs, or 4; not
  * WL_FLAG_STREAM) the steps run as launches of the persistent rollout kernel, at most WL_DRIFT_ROLLOUT_CHUNK_STEPS each, the envs' rows in
- * registers from step to step.  With a metric ring (metrics_slots > 1: step k's counts belong in slot k % R, cleared
+ * registers from step to step (up to WL_ROLLOUT_SPLIT_MAX_ENVS envs and without WL_FLAG_ROLLOUT_ONE_ROLE: the two-role form of
+ * that kernel, the output work of step k on a second wavefront beside step k + 1).  With a metric ring (metrics_slots > 1: step k's counts belong in slot k % R, cleared
  * behind a kernel boundary), a forced lane form, one step, or WL_FLAG_STEP_LAUNCHES: one launch of the step kernel per step.
  */
 #define WL_DRIFT_ROLLOUT_CHUNK_STEPS 1024   /* steps one launch of the rollout kernel covers at most in wl_drift_rollout */
@@ -239,6 +245,7 @@ int wl_drift_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const float*
  * K calls of wl_drift_step.  Episode metrics of all K steps accumulate into ring slot (step0 % R) and slot
  * ((step0 + K) % R) is cleared for the next launch (K % R must not be 0 when R > 1).  For pre-staged action sequences
  * (open-loop evaluation, sampling-based MPC); a policy in the loop needs wl_drift_step or wl_drift_rollout_policy.
+ * Kernel form: as in wl_drift_rollout (two roles up to WL_ROLLOUT_SPLIT_MAX_ENVS envs unless WL_FLAG_ROLLOUT_ONE_ROLE).
  */
 int wl_drift_rollout_persistent(const WlDriftParams* p, const WlEnvBuffers* b, const float* actions,
                                 const WlStepOut* out, int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps,

@@ -2,7 +2,8 @@
 gpurun_variants/lib_*.so (tools/build_variants.sh).   usage: ab_probe.py workload[,workload...] [repeat]
 workloads: drift4096 drift65536 drift1m elev4096 elevobs262144 elevstep262144 elevstep1m visual4096 depth4096 vdtask4096
 drift<n>: the step kernel, one launch per step (FLAG_STEP_LAUNCHES: without it rollout() runs <= 32 768 envs as launches of the
-persistent rollout kernel); driftplan<n>: rollout() as a caller gets it, by wl_drift_rollout's launch plan.  n: a number, 1m, 4m."""
+persistent rollout kernel); driftplan<n>: rollout() as a caller gets it, by wl_drift_rollout's launch plan (the two-role rollout
+kernel where the plan picks it); driftone<n>: the same with FLAG_ROLLOUT_ONE_ROLE, the single-role rollout kernel.  n: a number, 1m, 4m."""
 import glob, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,11 +34,11 @@ def timed(fn, reps, per=1, warm=2, blocks=4):
 def run(name):
     from wheeledlab_amd.core import DepthCamera, DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
     if name.startswith("drift"):
-        plan = name.startswith("driftplan")
-        n = int(name[9 if plan else 5:].replace("1m", "1048576").replace("4m", "4194304"))
+        plan, one = name.startswith("driftplan"), name.startswith("driftone")
+        n = int(name[9 if plan else 8 if one else 5:].replace("1m", "1048576").replace("4m", "4194304"))
         env = DriftBatch(n, device=dev, seed=42)
         env.set_dones_output(False)
-        env.set_flags(0 if plan else A.FLAG_STEP_LAUNCHES)
+        env.set_flags(0 if plan else A.FLAG_ROLLOUT_ONE_ROLE if one else A.FLAG_STEP_LAUNCHES)
         env.reset()
         K = 128 if n <= 65536 else 8
         a = torch.rand(K, n, 2, device=dev) * 2 - 1

@@ -30,6 +30,7 @@ M_EPSUM0, M_RESETS, M_TIMEOUTS, M_TERM0, M_NONFINITE, M_EPLEN, M_COUNT = 0, 8, 9
 # WlEnvBuffers.flags (WL_FLAG_*): force an instantiation the launchers otherwise pick from the batch size
 FLAG_STREAM, FLAG_NO_STREAM = 1, 2
 FLAG_STEP_LAUNCHES = 32   # wl_drift_rollout: one step-kernel launch per step, whatever its launch plan would choose
+FLAG_ROLLOUT_ONE_ROLE = 64   # rollout-kernel launches: the single-role kernel, whatever the env count (A/B runs, tests)
 DRIFT_ROLLOUT_CHUNK_STEPS = 1024   # WL_DRIFT_ROLLOUT_CHUNK_STEPS: steps per launch of the rollout kernel in wl_drift_rollout, at most
 M_SHARDS = 32   # WL_M_SHARDS: an accumulator vector is [M_SHARDS][M_COUNT], its value the sum over shards
 # WlDriftRewTerm

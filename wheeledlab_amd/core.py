@@ -136,7 +136,8 @@ class _EnvBatch:
     def set_flags(self, flags: int = 0):
         """WlEnvBuffers.flags (_abi.FLAG_*): force an instantiation the launchers otherwise pick from the batch size -- the
         streaming (non-temporal store) forms or the cache-allocating forms.  0 = by size.  What the tests use to run the large-batch forms at small sizes (and vice versa).
-        FLAG_STEP_LAUNCHES keeps DriftBatch.rollout() on one step-kernel launch per step (probes and tests of that kernel)."""
+        FLAG_STEP_LAUNCHES keeps DriftBatch.rollout() on one step-kernel launch per step (probes and tests of that kernel);
+        FLAG_ROLLOUT_ONE_ROLE keeps its rollout-kernel launches on the single-role kernel (A/B runs, tests of the two-role kernel)."""
         self._bufs.flags = int(flags)
 
     def set_lanes(self, lanes: int = 0):

@@ -144,6 +144,141 @@ __global__ void __launch_bounds__(kBlock) drift_rollout_kernel(const WlDriftPara
     store_rows<LANES>(S, b, p, e, wid, lead, r);
 }
 
+// The same rollout on TWO wavefront roles, pipelined across steps.  A block is 128 threads for 16 envs: wavefront 0 owns the envs'
+// rows and runs the state half of every step (drift_state_half: what step k + 1 waits for), wavefront 1 runs the output half
+// (drift_output_half: rewards, sums, metrics, observation, every store) of step k on the same 16 quads -- same lane <-> (env,
+// wheel) mapping, so every DPP quad_perm stays valid -- WHILE wavefront 0 steps k + 1.  The single-role kernel's limit is one
+// wavefront's instruction chain; this takes the ~40 % of it that the next step does not need off that chain.
+// Hand-off through LDS, two slots each way, slot index = step parity:
+//   snap[k & 1]: written by the state wavefront in step k (DriftSnap: the post-physics state, the flags, the push increments),
+//                read by the output wavefront after barrier k;
+//   drw[k & 1]:  step k's DriftEventDraws, written by the output wavefront (which draws every step's StepDraws, one step ahead:
+//                the state wavefront runs no Philox block) before barrier k - 1, read by the state wavefront in step k.
+// ONE barrier per step (plus one that primes step 0's draws): the output wavefront has finished reading snap[k & 1] when it
+// arrives at barrier k + 1 and the state wavefront writes that slot next after barrier k + 1; likewise the state wavefront has
+// read drw[k & 1] before barrier k and the output wavefront writes it next (step k + 2's draws) after barrier k.
+// Ownership: the state wavefront loads and stores every row but the episode sums, and owns episode_len and the action prefetch;
+// the output wavefront loads the episode sums at launch, stores them at the end, and makes every output store and metric add.
+constexpr int kSplitEnvs = 16;    // envs per block: one wavefront of quads per role
+constexpr int kSplitBlock = 128;
+constexpr int kSnapVec = 6, kDrawVec = 3;   // 16-byte words per env of a snap / drw slot
+
+WL_DEV void snap_publish(float4* slot, int q, const DriftSnap& s) {   // the quad's lead lane writes the env's record
+    float4* w = slot + q * kSnapVec;
+    w[0] = make_float4(s.pos.x, s.pos.y, s.pos.z, s.q.w);
+    w[1] = make_float4(s.q.x, s.q.y, s.q.z, s.v.x);
+    w[2] = make_float4(s.v.y, s.v.z, s.wb.x, s.wb.y);
+    w[3] = make_float4(s.wb.z, s.wwz, s.th, s.a0);
+    w[4] = make_float4(s.a1, __int_as_float(s.ep_len), __int_as_float(s.flags), s.dvx);
+    w[5] = make_float4(s.dvy, s.dwz_hf, s.dwz_lf, 0.f);
+}
+WL_DEV DriftSnap snap_read(const float4* slot, int q) {   // every lane of the quad reads the same words (LDS broadcast)
+    const float4* w = slot + q * kSnapVec;
+    const float4 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4], w5 = w[5];
+    DriftSnap s;
+    s.pos = v3(w0.x, w0.y, w0.z), s.q = Quat{w0.w, w1.x, w1.y, w1.z}, s.v = v3(w1.w, w2.x, w2.y), s.wb = v3(w2.z, w2.w, w3.x);
+    s.wwz = w3.y, s.th = w3.z, s.a0 = w3.w, s.a1 = w4.x, s.ep_len = __float_as_int(w4.y), s.flags = __float_as_int(w4.z);
+    s.dvx = w4.w, s.dvy = w5.x, s.dwz_hf = w5.y, s.dwz_lf = w5.z;
+    return s;
+}
+WL_DEV void draws_publish(float4* slot, int q, const DriftEventDraws& d) {
+    float4* w = slot + q * kDrawVec;
+    w[0] = make_float4(d.rx, d.ry, d.rqw, d.rqz);
+    w[1] = make_float4(d.rt_hf, d.rt_lf, d.lf_kick, d.lf_timer);
+    w[2] = make_float4(d.hf.x, d.hf.y, d.hf.z, d.hf.w);
+}
+WL_DEV DriftEventDraws draws_read(const float4* slot, int q) {
+    const float4* w = slot + q * kDrawVec;
+    const float4 w0 = w[0], w1 = w[1], w2 = w[2];
+    DriftEventDraws d;
+    d.rx = w0.x, d.ry = w0.y, d.rqw = w0.z, d.rqz = w0.w, d.rt_hf = w1.x, d.rt_lf = w1.y, d.lf_kick = w1.z, d.lf_timer = w1.w;
+    d.hf = F4{w2.x, w2.y, w2.z, w2.w};
+    return d;
+}
+
+template <class Ground>
+__global__ void __launch_bounds__(kSplitBlock) drift_rollout_split_kernel(const WlDriftParams p_arg, const WlEnvBuffers b,
+                                                                          const float2* __restrict__ actions, const WlStepOut out,
+                                                                          const int64_t obs_step_stride, const int64_t vec_step_stride,
+                                                                          const int n_steps, const uint64_t seed, const uint64_t step0,
+                                                                          const Ground ground, const VehDerived vd_arg, const MetricSlots slots) {
+    __shared__ float4 snap[2][kSplitEnvs * kSnapVec];
+    __shared__ float4 drw[2][kSplitEnvs * kDrawVec];
+    WlDriftParams p = p_arg;
+    VehDerived vd = vd_arg;
+    const int role = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // wave-uniform: 0 state, 1 output
+    const int wid = threadIdx.x & 3, q = (threadIdx.x & 63) >> 2;
+    const int e_quad = blockIdx.x * kSplitEnvs + q;
+    if (b.metrics_slots > 1) clear_metric_slot(b, slots.next);
+    // Both wavefronts of a block serve the same 16 envs, so a block past the batch leaves as a whole (the grid has none).  In a
+    // partly filled block the quads past the batch stay in the loop -- a wavefront that left would be missing at the barriers --
+    // stepping a copy of the batch's last env with every store and atomic masked (`live`).
+    if (blockIdx.x * kSplitEnvs >= b.n_envs) return;
+    const bool live = e_quad < b.n_envs;
+    const int e = live ? e_quad : b.n_envs - 1;
+    const bool lead = wid == 0;
+    const Rows S = make_rows(b.state, b.stride);
+    const uint32_t gid = (uint32_t)(b.env_offset + e);
+    // BARRIER INVARIANT: each wavefront executes exactly n_steps + 1 block barriers -- one before the loop, one per iteration, at
+    // the top level of the loop body.  n_steps is a kernel argument, uniform over the block; no barrier sits behind a test of env
+    // state, `lead`, `wid`, `live` or e < n_envs.  The role test is wave-uniform and both roles' loops have the same trip count.
+    if (role == 0) {
+        pin_state_params_vgpr(p, vd);
+        EnvConst ec;
+        DriftRows r;
+        load_env_const(S, p.vehicle, vd, e, ec);
+        load_rows<4>(S, b, p, e, wid, r);    // (the episode-sum rows it requests are the output wavefront's: dead here, dropped)
+        float2 a_next = n_steps > 0 ? actions[e] : make_float2(0.f, 0.f);
+        __syncthreads();                     // step 0's draws are in drw[0]
+        for (int k = 0; k < n_steps; ++k) {
+            const float2 a = a_next;
+            if (k + 1 < n_steps) a_next = actions[(int64_t)(k + 1) * b.n_envs + e];   // prefetch: hidden behind the physics
+            const DriftEventDraws dr = draws_read(drw[k & 1], q);                        // used in the rare branches only
+            const DriftSnap sn = drift_state_half(p, vd, ground, ec, r, a, wid, dr);
+            if (lead) snap_publish(snap[k & 1], q, sn);
+            __syncthreads();                 // barrier k: snap[k & 1] is complete; drw[(k + 1) & 1] holds step k + 1's draws
+        }
+        if (live) {
+            WlDriftParams ps = p;
+            ps.log_episode_sums = 0;         // the episode-sum rows are stored by the output wavefront
+            store_rows<4>(S, b, ps, e, wid, lead, r);
+        }
+    } else {
+        pin_output_params_vgpr(p);
+        const MetricSink<4> ms{nullptr, metric_shard(b, slots.cur)};
+        float epsum[WL_DR_NTERMS];
+#pragma unroll
+        for (int i = 0; i < WL_DR_NTERMS; ++i) epsum[i] = S.ld(WL_S_EPSUM0 + i, e);
+        StepDraws d = draw_step(p, b.ref_poses, gid, step0, seed, wid);
+        ResetDraw rd = quad_reset_draw(p, d);
+        const DriftEventDraws ev0 = event_draws(rd, d);   // (DPP quad broadcasts: by the whole quad, not behind `lead`)
+        if (lead) draws_publish(drw[0], q, ev0);
+        __syncthreads();
+        for (int k = 0; k < n_steps; ++k) {
+            WlStepOut o = out;
+            o.obs += k * obs_step_stride;
+            o.reward += k * vec_step_stride;
+            o.terminated += k * vec_step_stride;
+            o.truncated += k * vec_step_stride;
+            if (o.dones) o.dones += k * vec_step_stride;
+            // step k + 1's draws (after the last step: a block nobody reads), published before barrier k
+            const StepDraws dn = draw_step(p, b.ref_poses, gid, step0 + (uint64_t)(k + 1), seed, wid);
+            const ResetDraw rdn = quad_reset_draw(p, dn);
+            const DriftEventDraws evn = event_draws(rdn, dn);
+            if (lead) draws_publish(drw[(k + 1) & 1], q, evn);
+            __syncthreads();                 // barrier k
+            const DriftSnap sn = snap_read(snap[k & 1], q);
+            drift_output_half(p, o, sn, rd, d.z, epsum, e, wid, live, ms);
+            d = dn;
+            rd = rdn;
+        }
+        if (live && lead && p.log_episode_sums) {
+#pragma unroll
+            for (int i = 0; i < WL_DR_NTERMS; ++i) S.st(WL_S_EPSUM0 + i, e, epsum[i]);
+        }
+    }
+}
+
 // ---- terms only, on caller-supplied state tensors (parity entry point) -----------------------------------
 __global__ void __launch_bounds__(kBlock) drift_mdp_kernel(const WlDriftParams p, int n, int64_t stride,
                                                            const float* __restrict__ pos, const float* __restrict__ quat,
@@ -310,11 +445,30 @@ int wl_drift_step(const WlDriftParams* p, const WlEnvBuffers* b, const float* ac
     return launch_status();
 }
 
-// one drift_rollout_kernel launch: `n_steps` steps from `step0` with the envs' rows in registers (actions / out: those of step0)
+// Rollout-kernel launches of up to WL_ROLLOUT_SPLIT_MAX_ENVS envs run the two-role kernel (drift_rollout_split_kernel), larger ones
+// and WL_FLAG_ROLLOUT_ONE_ROLE the single-role kernel.  MEASURED crossover: us per step of 128-step rollout() calls
+// (tools/ab_probe.py driftone<n> / driftplan<n>, best of 4 blocks, 3 rounds within 0.03 us), one role / two roles: 1024 envs
+// 3.20 / 2.43, 4096 envs 3.36 / 2.45, 8192 envs 3.37 / 2.69, 16 384 envs 3.29 / 2.74, 24 576 envs 4.68 / 4.21, 32 768 envs
+// 4.70 / 6.81.  The two-role kernel has two wavefronts per 16 envs and 142 VGPRs: three wavefronts fit a SIMD, so 24 576 envs
+// (3072 wavefronts on 1024 SIMDs) still run in one round and 32 768 (4096 wavefronts) do not -- the single-role kernel's 2048 do.
+// Nothing between 24 576 and 32 768 was measured: the threshold is the last size that was.
+#ifndef WL_ROLLOUT_SPLIT_MAX_ENVS
+#define WL_ROLLOUT_SPLIT_MAX_ENVS 24576
+#endif
+static bool use_split_rollout(const WlEnvBuffers* b) {
+    return !(b->flags & WL_FLAG_ROLLOUT_ONE_ROLE) && b->n_envs <= WL_ROLLOUT_SPLIT_MAX_ENVS;
+}
+
+// one rollout-kernel launch: `n_steps` steps from `step0` with the envs' rows in registers (actions / out: those of step0)
 static void launch_rollout(const WlDriftParams* p, const WlEnvBuffers* b, const VehDerived& vd, const float2* actions, const WlStepOut& out,
                            int64_t obs_step_stride, int64_t vec_step_stride, int32_t n_steps, uint64_t seed, uint64_t step0,
                            hipStream_t stream) {
     const MetricSlots ms = metric_slots(b, step0, (uint64_t)n_steps);
+    if (use_split_rollout(b)) {
+        drift_rollout_split_kernel<FlatGround><<<(b->n_envs + kSplitEnvs - 1) / kSplitEnvs, kSplitBlock, 0, stream>>>(
+            *p, *b, actions, out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, vd, ms);
+        return;
+    }
     launch_quad(b->n_envs, [&](auto qb, int qgrid) {
         drift_rollout_kernel<FlatGround, decltype(qb)::value><<<qgrid, qb.value, 0, stream>>>(
             *p, *b, actions, out, obs_step_stride, vec_step_stride, n_steps, seed, step0, FlatGround{}, vd, ms);

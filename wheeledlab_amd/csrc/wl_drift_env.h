@@ -576,6 +576,222 @@ WL_DEV void drift_env_step(const WlDriftParams& p, const WlEnvBuffers& b, const 
     }
 }
 
+// ---- drift_env_step<4> in two halves, for a kernel that runs them on two wavefronts (drift_rollout_split_kernel, wl_drift.hip) ----
+// The STATE half is what step k + 1 waits for: action term, physics, guard, terminations, the reset's and the pushes' state
+// changes, timers, ep_len.  The OUTPUT half is everything else: body-frame velocity, the lane-parallel atan2, rewards, episode
+// sums, metric adds, the observation frame carried through reset and pushes, noise, the observation row and every store.  Same
+// arithmetic, order and rounding as drift_env_step<4>; a value both halves need crosses in a DriftSnap and is never computed
+// twice (under -ffp-contract=fast a second copy may contract differently), except what is spelled out fma by fma (mat_from_quat).
+// Every field is replicated on the quad's four lanes.
+struct DriftSnap {
+    V3 pos;               // post-physics, PRE-reset: what the rewards and terminations are computed on
+    Quat q;
+    V3 v, wb;
+    float wwz, th;
+    float a0, a1;         // the action as the action term left it (ClipAction applied)
+    int ep_len;           // incremented, pre-reset (the episode-length metric)
+    int flags;            // kSnap*
+    float dvx, dvy, dwz_hf, dwz_lf;   // the push increments the state half applied (0 without the push)
+};
+enum { kSnapFinite = 1, kSnapTerminated = 2, kSnapTruncated = 4, kSnapHf = 8, kSnapLf = 16 };
+// what the state half's rare branches take from the step's draws (the output wavefront draws and publishes them one step ahead):
+// the reset as drawn (quad_reset_draw, explicit fmas: nothing to contract), the pushes as raw uniforms -- the increments are
+// computed where drift_env_step computes them, next to the additions they feed
+struct DriftEventDraws {
+    float rx, ry, rqw, rqz, rt_hf, rt_lf;   // reset pose (z = 0), quaternion (x = y = 0), re-armed timers
+    float lf_kick, lf_timer;                // quad_lf_draw
+    F4 hf;                                  // quad_hf_draw
+};
+WL_DEV DriftEventDraws event_draws(const ResetDraw& rd, const StepDraws& d) {
+    DriftEventDraws ev;
+    ev.rx = rd.pos.x, ev.ry = rd.pos.y, ev.rqw = rd.q.w, ev.rqz = rd.q.z, ev.rt_hf = rd.timer_hf, ev.rt_lf = rd.timer_lf;
+    quad_lf_draw(d, ev.lf_kick, ev.lf_timer);
+    ev.hf = quad_hf_draw(d);
+    return ev;
+}
+
+template <class Ground>
+WL_DEV DriftSnap drift_state_half(const WlDriftParams& p, const VehDerived& vd, const Ground& ground, EnvConst& ec, DriftRows& r,
+                                  float2 a, int wid, const DriftEventDraws& dr) {
+    const WlVehicleParams& vp = p.vehicle;
+    float v_t, delta;
+    process_action(p.action, a.x, a.y, v_t, delta);
+    joint_targets(p.action, v_t, delta, ec.steer_target, ec.wheel_target);
+    env_const_lane(ec, vp, vd, wid);
+    VehState s;
+    s.q = r.q;
+    s.v = r.v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s.wheel[i] = r.wheel[i];
+    s.th = r.th;
+    s.om = r.om;
+    {
+        const Mat3 R = mat_from_quat(s.q);
+        s.x = r.pos + vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
+        s.wb = mul_t(R, r.ww);
+    }
+    vehicle_integrate<4, Ground, true, -1>(vp, vd, ec, s, ground, wid);
+    const Mat3 R = mat_from_quat(s.q);
+    V3 ww = mul(R, s.wb);
+    V3 pos = s.x - vp.cg_z * v3(R.r0.z, R.r1.z, R.r2.z);
+    const float wheel_sum = quad_sum(s.wheel[0]);
+    const float chk_in[16] = {pos.x, pos.y, pos.z, s.q.w, s.q.x, s.q.y, s.q.z, s.v.x, s.v.y, s.v.z, ww.x, ww.y, ww.z, wheel_sum, s.th, s.om};
+    const bool finite = __builtin_isfinite(sum16(chk_in));
+    const bool terminated = !finite || cart_off_track(pos.x, pos.y, p.straight, p.r_in, p.r_out);
+    int ep_len = r.ep_len + 1;
+    const bool truncated = ep_len >= p.max_episode_length;
+    const float step_dt = p.sim_dt * (float)p.decimation;
+    DriftSnap sn;
+    sn.pos = pos, sn.q = s.q, sn.v = s.v, sn.wb = s.wb, sn.wwz = ww.z, sn.th = s.th, sn.a0 = a.x, sn.a1 = a.y, sn.ep_len = ep_len;
+    sn.flags = (finite ? kSnapFinite : 0) | (terminated ? kSnapTerminated : 0) | (truncated ? kSnapTruncated : 0);
+    sn.dvx = sn.dvy = sn.dwz_hf = sn.dwz_lf = 0.f;
+    float a0 = a.x, a1 = a.y, timer_hf = r.timer_hf, timer_lf = r.timer_lf;
+    const float lf_next = timer_lf - step_dt;
+    const bool done = terminated || truncated;
+    if (done) {
+        if (!finite) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s.wheel[i] = 0.f;
+            s.th = s.om = 0.f;
+        }
+        pos = v3(dr.rx, dr.ry, 0.f);
+        s.q = Quat{dr.rqw, 0.f, 0.f, dr.rqz};
+        s.v = v3(0.f, 0.f, 0.f);
+        ww = v3(0.f, 0.f, 0.f);
+        timer_hf = dr.rt_hf;
+        timer_lf = dr.rt_lf;
+        ep_len = 0;
+        a0 = a1 = 0.f;
+    }
+    bool hf_due = false;
+    if (p.enable_pushes) {
+        timer_hf -= step_dt;
+        hf_due = timer_hf < 1e-6f;
+        if (hf_due) {
+            const F4 u = dr.hf;
+            const float dvx = (2.f * u.x - 1.f) * p.hf_vel_x, dvy = (2.f * u.y - 1.f) * p.hf_vel_y, dwz = (2.f * u.z - 1.f) * p.hf_vel_yaw;
+            s.v.x += dvx;
+            s.v.y += dvy;
+            ww.z += dwz;
+            sn.dvx = dvx, sn.dvy = dvy, sn.dwz_hf = dwz;
+            sn.flags |= kSnapHf;
+            timer_hf = fmaf(u.w, p.hf_interval[1] - p.hf_interval[0], p.hf_interval[0]);
+        }
+        timer_lf = done ? timer_lf - step_dt : lf_next;
+        if (timer_lf < 1e-6f) {
+            const float dwz = (2.f * dr.lf_kick - 1.f) * p.lf_vel_yaw;
+            ww.z += dwz;
+            sn.dwz_lf = dwz;
+            sn.flags |= kSnapLf;
+            timer_lf = fmaf(dr.lf_timer, p.lf_interval[1] - p.lf_interval[0], p.lf_interval[0]);
+        }
+    }
+    r.pos = pos;
+    r.q = s.q;
+    r.v = s.v;
+    r.ww = ww;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.wheel[i] = s.wheel[i];
+    r.th = s.th;
+    r.om = s.om;
+    r.a0 = a0;
+    r.a1 = a1;
+    r.timer_hf = timer_hf;
+    r.timer_lf = timer_lf;
+    r.ep_len = ep_len;
+    return sn;
+}
+
+// `rd`: this step's reset as the output wavefront drew it (the values the state half was handed); `z`: this lane's four normals;
+// `epsum`: the env's episode sums (the output half's own rows); `live`: the quad serves an env of the batch (stores, atomics)
+WL_DEV void drift_output_half(const WlDriftParams& p, const WlStepOut& out, const DriftSnap& sn, const ResetDraw& rd, const float z[4],
+                              float epsum_rows[WL_DR_NTERMS], int e, int wid, bool live, const MetricSink<4>& ms) {
+    const bool lead = wid == 0 && live;
+    const bool finite = sn.flags & kSnapFinite, terminated = sn.flags & kSnapTerminated, truncated = sn.flags & kSnapTruncated;
+    float epsum[WL_DR_NTERMS];
+#pragma unroll
+    for (int i = 0; i < WL_DR_NTERMS; ++i) epsum[i] = p.log_episode_sums ? epsum_rows[i] : 0.f;
+    V3 pos = sn.pos;
+    const Mat3 R = mat_from_quat(sn.q);
+    V3 vb = mul_t(R, sn.v);
+    float slip_angle;
+    V3 euler;
+    {
+        // drift_env_step<4> writes these sums of two products as plain expressions and leaves the choice of the product that is
+        // fused into the addition to the compiler; here, with q arriving from LDS, it chose the other one for the roll argument
+        // (a last-bit difference that wrap_2pi turns into 0 against 2 pi when the roll is a rounding error around 0).  Spelled out
+        // as the fmas every kernel built on drift_env_step<4> has: one rounding of each second product, nothing left to choose.
+        const Quat q = sn.q;
+        const float sp = 2.f * fmaf(q.w, q.y, -(q.z * q.x));
+        const float ay = quad_pick(wid, opaque(vb.y), opaque(2.f * fmaf(q.y, q.z, q.w * q.x)), opaque(sp), opaque(2.f * fmaf(q.x, q.y, q.w * q.z)));
+        const float ax = quad_pick(wid, opaque(vb.x), opaque(fmaf(fmaf(q.x, q.x, q.y * q.y), -2.f, 1.f)), opaque(fsqrt(fmaxf(fmaf(-sp, sp, 1.f), 0.f))),
+                                   opaque(fmaf(fmaf(q.z, q.z, q.y * q.y), -2.f, 1.f)));
+        const float ang = atan2_fast(ay, ax);
+        slip_angle = quad_bcast<0>(ang);
+        euler = v3(wrap_2pi(quad_bcast<1>(ang)), wrap_2pi(quad_bcast<2>(ang)), wrap_2pi(quad_bcast<3>(ang)));
+    }
+    const int ep_len = sn.ep_len;
+    DriftTerms tm = drift_terms(p, pos, vb, sn.wb, sn.wwz, sn.th, terminated, truncated, slip_angle);
+    const float step_dt = p.sim_dt * (float)p.decimation;
+    float reward = 0.f;
+#pragma unroll
+    for (int i = 0; i < WL_DR_NTERMS; ++i) {
+        const float w = p.weight[i];
+        const float c = (w != 0.f && finite) ? tm.t[i] * w * step_dt : 0.f;
+        reward += c;
+        epsum[i] += c;
+    }
+    if (lead) {
+        out.reward[e] = reward;
+        out.terminated[e] = terminated ? 1 : 0;
+        out.truncated[e] = truncated ? 1 : 0;
+        if (out.dones) out.dones[e] = (terminated || truncated) ? 1 : 0;
+    }
+    Mat3 Ro = R;
+    V3 wb_o = sn.wb;
+    float a0 = sn.a0, a1 = sn.a1;
+    const bool done = terminated || truncated;
+    if (done) {
+        if (lead) {
+#pragma unroll
+            for (int i = 0; i < WL_DR_NTERMS; ++i) ms.add(WL_M_EPSUM0 + i, epsum[i]);
+            ms.add(WL_M_RESETS, 1.f);
+            if (truncated) ms.add(WL_M_TIMEOUTS, 1.f);
+            if (terminated) ms.add(WL_M_TERM0, 1.f);
+            if (!finite) ms.add(WL_M_NONFINITE, 1.f);
+            ms.add(WL_M_EPLEN, (float)ep_len);
+        }
+#pragma unroll
+        for (int i = 0; i < WL_DR_NTERMS; ++i) epsum[i] = 0.f;
+        pos = rd.pos;
+        euler = v3(0.f, 0.f, rd.yaw - WL_TWO_PI * floorf(rd.yaw * WL_INV_TWO_PI));
+        vb = v3(0.f, 0.f, 0.f);
+        wb_o = v3(0.f, 0.f, 0.f);
+        const float cy = fmaf(rd.q.w, rd.q.w, -rd.q.z * rd.q.z), sy = 2.f * rd.q.w * rd.q.z;
+        Ro = Mat3{v3(cy, -sy, 0.f), v3(sy, cy, 0.f), v3(0.f, 0.f, 1.f)};
+        a0 = a1 = 0.f;
+    }
+    if (sn.flags & kSnapHf) {
+        const float dvx = sn.dvx, dvy = sn.dvy, dwz = sn.dwz_hf;
+        vb = v3(fmaf(Ro.r0.x, dvx, fmaf(Ro.r1.x, dvy, vb.x)), fmaf(Ro.r0.y, dvx, fmaf(Ro.r1.y, dvy, vb.y)),
+                fmaf(Ro.r0.z, dvx, fmaf(Ro.r1.z, dvy, vb.z)));
+        wb_o = fma3(dwz, Ro.r2, wb_o);
+    }
+    if (sn.flags & kSnapLf) wb_o = fma3(sn.dwz_lf, Ro.r2, wb_o);
+#pragma unroll
+    for (int i = 0; i < WL_DR_NTERMS; ++i) epsum_rows[i] = epsum[i];
+    Noise12 nz;
+    if (p.enable_corruption) {
+        nz = gather_quad_noise(z);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) nz.z[k] = 0.f;
+    }
+    float o[14];
+    obs_values(o, p, pos, euler, vb, wb_o, a0, a1, nz);
+    if (live) store_obs_quad(out.obs + (int64_t)e * kObsDim, wid, o);
+}
+
 // Persistent kernels keep every parameter live across the whole rollout loop: ~130 uniform dwords against 102 SGPRs, so
 // the compiler parks the overflow in lanes of a VGPR and pays a v_readlane (+ hazard nops) per use -- ~600 extra
 // instructions per env-step.  gfx950 has no scalar float ALU, so float parameters are only ever VALU operands anyway:
@@ -608,6 +824,36 @@ WL_DEV void pin_params_vgpr(WlDriftParams& p, VehDerived& d) {
                    &d.inv_wlim, &d.mot_b, &d.r2, &d.inv_A0, &d.hg, &d.inv_g2x, &d.inv_g2y, &d.inv_g2z, &d.cgx, &d.cgy, &d.cgz};
 #pragma unroll
     for (float* f : df) pin_vgpr(*f);
+}
+
+// the two-role rollout kernel: each wavefront role pins what its half reads
+WL_DEV void pin_state_params_vgpr(WlDriftParams& p, VehDerived& d) {      // drift_state_half
+    pin_vgpr(p.sim_dt);
+    WlActionParams& a = p.action;
+    pin_vgpr(a.scale), pin_vgpr(a.offset), pin_vgpr(a.base_length), pin_vgpr(a.base_width), pin_vgpr(a.wheel_radius);
+    WlVehicleParams& v = p.vehicle;
+    float* vf[] = {&v.gravity, &v.half_wheelbase_f, &v.half_wheelbase_r, &v.half_track, &v.wheel_radius, &v.wheel_z, &v.cg_z,
+                   &v.gyr_x, &v.gyr_y, &v.gyr_z, &v.wheel_inertia, &v.wheel_damping, &v.susp_k, &v.susp_c, &v.ground_mu_s,
+                   &v.ground_mu_d, &v.slip_peak, &v.v_min, &v.motor_sat, &v.motor_limit, &v.motor_vel_limit, &v.steer_kp,
+                   &v.steer_kd, &v.steer_effort, &v.steer_vel_limit, &v.steer_inertia, &v.susp_fmax};
+#pragma unroll
+    for (float* f : vf) pin_vgpr(*f);
+    float* pf[] = {&p.straight, &p.r_in, &p.r_out, &p.hf_vel_x, &p.hf_vel_y, &p.hf_vel_yaw, &p.lf_vel_yaw};
+#pragma unroll
+    for (float* f : pf) pin_vgpr(*f);
+    pin_vgpr(p.hf_interval), pin_vgpr(p.lf_interval);
+    float* df[] = {&d.h, &d.inv_h, &d.half_h, &d.steer_a, &d.steer_b, &d.steer_J_h, &d.steer_h_J, &d.zrel, &d.Iw_h, &d.A0,
+                   &d.inv_wlim, &d.mot_b, &d.r2, &d.inv_A0, &d.hg, &d.inv_g2x, &d.inv_g2y, &d.inv_g2z, &d.cgx, &d.cgy, &d.cgz};
+#pragma unroll
+    for (float* f : df) pin_vgpr(*f);
+}
+WL_DEV void pin_output_params_vgpr(WlDriftParams& p) {                    // draw_step, quad_reset_draw, drift_output_half
+    pin_vgpr(p.sim_dt);
+    float* pf[] = {&p.straight, &p.r_line, &p.slip_min, &p.slip_max, &p.slip_min_vx, &p.speed_target, &p.speed_offset,
+                   &p.tlgr_thresh, &p.ctd_offset, &p.ctd_p, &p.pos_noise, &p.yaw_noise};
+#pragma unroll
+    for (float* f : pf) pin_vgpr(*f);
+    pin_vgpr(p.weight), pin_vgpr(p.noise_std), pin_vgpr(p.hf_interval), pin_vgpr(p.lf_interval);
 }
 
 WL_DEV void keep_scalar_fields(WlDriftParams& v, const WlDriftParams&) {

@@ -257,8 +257,8 @@ inline void launch_quad(int n_envs, F&& launch) {
 #ifndef WL_LOWREG_WAVES
 #define WL_LOWREG_WAVES 5   // .. and fenced
 #endif
-// WlEnvBuffers.flags: valid combinations only (a flag and its opposite together are refused; WL_FLAG_STEP_LAUNCHES goes with
-// either: it chooses how wl_drift_rollout launches, not a kernel form)
+// WlEnvBuffers.flags: valid combinations only (a flag and its opposite together are refused; WL_FLAG_STEP_LAUNCHES and
+// WL_FLAG_ROLLOUT_ONE_ROLE go with either: they choose how the rollout entry points launch, not a step-kernel form)
 inline bool flags_ok(const WlEnvBuffers* b) {
     const int f = b->flags;
     if (f & ~WL_FLAG_MASK) return false;
