@@ -1,16 +1,18 @@
 /* wheeledlab_amd_raycaster.h -- a ray caster: any table of rays cast from every env's sensor against the terrain solid the depth
  * camera sees (IsaacLab's RayCaster / RayCasterCamera over the terrain: grid, lidar and pinhole patterns are tables of this entry).
  *
- * Not part of the drop-in step boundary (include/wheeledlab_amd.h): a scan is an observation read between steps.  Conventions of
- * wheeledlab_amd_lidar.h: device pointers, `stream` a hipStream_t (NULL = the default stream), return 0 (WL_OK) or a negative WL_E*
- * code, every argument validated before any launch.  wl_lidar_scan is the special case ray_starts = 0, ray_scale = NULL, dist_out only.
+ * Not part of the drop-in step boundary (include/wheeledlab_amd.h): a scan is an observation read between steps, like the scene
+ * camera's depth image.  Same conventions as that header: device pointers, `stream` a hipStream_t (NULL = the default stream), return 0
+ * (WL_OK) or a negative WL_E* code, every argument validated before any launch.  A lidar scan is the case ray_starts = NULL (every beam
+ * leaves the sensor origin), ray_scale = NULL, dist_out only: dist_out[e][k] is then the range of beam k.
  *
  * Sensor frame.  Env e's root pose is read from rows WL_S_PX.. / WL_S_QW.. of b->state.  With R = the body's rotation (alignment 0,
- * "base"), its yaw alone (1, "yaw": the heading of the body's x axis in the world xy plane, the lidar's yaw_only rotation), or the
+ * "base"), its yaw alone (1, "yaw": the heading of the body's x axis in the world xy plane, atan2(2 (w z + x y), 1 - 2 (y^2 + z^2)),
+ * the angle IsaacLab's yaw_quat keeps: roll and pitch are dropped, and a body pointing straight up or down keeps heading 0), or the
  * identity (2, "world"), and mount = the rotation of offset_quat:   origin o = pos + R offset_pos,   rotation M = R mount.
- * This is the lidar's rule.  IsaacLab's ray caster turns offset_pos by the FULL body rotation and leaves the directions unrotated in
- * its yaw mode [recalled, not checked against its source]; for the vertical rays that mode exists for, both rules agree whenever
- * offset_pos lies on the body z axis and the body is level, and differ by the offset's tilt otherwise.
+ * One R turns both the offset and the rays.  IsaacLab's ray caster turns offset_pos by the FULL body rotation and leaves the
+ * directions unrotated in its yaw mode [recalled, not checked against its source]; for the vertical rays that mode exists for, both
+ * rules agree whenever offset_pos lies on the body z axis and the body is level, and differ by the offset's tilt otherwise.
  *
  * Ray k.  Start o + M ray_starts[k], direction M ray_dirs[k] (ray_dirs are unit vectors: the ray parameter is a Euclidean distance).
  *
@@ -34,7 +36,7 @@
 extern "C" {
 #endif
 
-#define WL_RAYCASTER_VERSION 1
+#define WL_RAYCASTER_VERSION 2   /* 2: ray_starts may be NULL (every ray leaves the sensor origin) */
 #define WL_RAYCAST_MAX_RAYS (1 << 20)   /* n_rays: 1 .. WL_RAYCAST_MAX_RAYS */
 
 #define WL_RAYCAST_ALIGN_BASE 0
@@ -52,12 +54,12 @@ typedef struct WlRayCastParams {
 
 /* One cast per env of b (b->n_envs envs; 0: nothing is launched):
  *   hf, pyramid   the terrain and its bound pyramid (wl_heightfield_build_pyramid), as wl_visual_depth takes them
- *   ray_starts    float [n_rays][3], sensor frame
+ *   ray_starts    float [n_rays][3], sensor frame; NULL without p->vertical: all zero, every ray leaves the sensor origin (no loads)
  *   ray_dirs      float [n_rays][3], unit vectors in the sensor frame; NULL if and only if p->vertical
  *   ray_scale     float [n_rays] or NULL
  *   dist_out      float [n_envs][n_rays] or NULL
  *   hits_out      float [n_envs][n_rays][3] or NULL
- * WL_EINVAL: a NULL pointer (p, b, b->state, hf, pyramid, ray_starts, ray_dirs without vertical, both outputs), ray_dirs given
+ * WL_EINVAL: a NULL pointer (p, b, b->state, hf, pyramid, ray_starts with vertical, ray_dirs without, both outputs), ray_dirs given
  * with vertical, n_rays outside [1, WL_RAYCAST_MAX_RAYS], max_distance not positive and finite, a non-finite or zero mount pose,
  * alignment outside 0 .. 2, vertical outside 0 .. 1 or with alignment 0 or a tilted mount or a field without its pair table, a
  * heightfield wl_visual_depth refuses, a batch the state rows cannot address, n_envs * ceil(n_rays / 64) beyond 2^31 - 1;

@@ -14,7 +14,7 @@ using std::min;
 #include "pyramid_host.h"
 
 extern "C" {
-// pos [n][3], quat [n][4] of the roots; starts, dirs [n_rays][3] (dirs unused with p->vertical); scale [n_rays] or NULL;
+// pos [n][3], quat [n][4] of the roots; starts, dirs [n_rays][3] (starts NULL: all zero; dirs unused with p->vertical); scale [n_rays] or NULL;
 // dist [n][n_rays], hits [n][n_rays][3].  The mount quaternion is normalised and the results are stored as wl_raycast_scan does.
 int hs_raycast(const WlRayCastParams* p, const WlHeightField* hf, int n, const float* pos, const float* quat, const float* starts,
                const float* dirs, const float* scale, float* dist, float* hits) {
@@ -32,9 +32,9 @@ int hs_raycast(const WlRayCastParams* p, const WlHeightField* hf, int n, const f
     const Mat3 mount = mat_from_quat(Quat{q.offset_quat[0], q.offset_quat[1], q.offset_quat[2], q.offset_quat[3]});
     for (int e = 0; e < n; ++e) {
         const Quat r{quat[4 * e], quat[4 * e + 1], quat[4 * e + 2], quat[4 * e + 3]};
-        const LidarPose s = raycast_frame(q, mount, v3(pos[3 * e], pos[3 * e + 1], pos[3 * e + 2]), r);
+        const SensorFrame s = raycast_frame(q, mount, v3(pos[3 * e], pos[3 * e + 1], pos[3 * e + 2]), r);
         for (int k = 0; k < q.n_rays; ++k) {
-            const V3 st = v3(starts[3 * k], starts[3 * k + 1], starts[3 * k + 2]);
+            const V3 st = starts ? v3(starts[3 * k], starts[3 * k + 1], starts[3 * k + 2]) : v3(0.f, 0.f, 0.f);
             const RayCastHit h = q.vertical ? raycast_column(gr, s, st, q.max_distance)
                                             : raycast_walk(g, py, hd, mem, s, st, v3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]), q.max_distance);
             const size_t at = (size_t)e * q.n_rays + k;

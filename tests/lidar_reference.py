@@ -3,7 +3,7 @@ with a 1 x 1 image (cx = cy = 0.5, the camera at the root) casts exactly ONE ray
 and with a unit direction that ray's parameter at the hit is its range.  So every beam becomes one "camera": the sensor origin as the
 root position, and a quaternion whose +x axis is the beam's world direction (built in float64, rounded to float32).
 
-The sensor frame is restated here in float64 from the header's definition (include/wheeledlab_amd_lidar.h): origin = pos + R offset,
+The sensor frame is restated here in float64 from the header's definition (include/wheeledlab_amd_raycaster.h): origin = pos + R offset,
 rotation R mount, with R the body's rotation or, with yaw_only, its yaw alone."""
 from types import SimpleNamespace
 

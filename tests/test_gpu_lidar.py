@@ -1,4 +1,4 @@
-"""The lidar on the GPU (wl_lidar_scan through core.LidarScanner and the scene's LidarData): closed forms on the plane, every beam
+"""The lidar on the GPU (wl_raycast_scan through core.LidarScanner and the scene's LidarData): closed forms on the plane, every beam
 against the float64 reference (tests/lidar_reference.py: oracle/depth.c, one ray per beam) on the bench field, the non-bench fields
 of tests/heightfield_cases.py and a mesh course, the launch's edges, the env surface (`cfg.scene.lidar` + the reference's
 `lidar_ranges_normalized` observation) and a short PPO run on the scan.  Yardstick of tests/test_gpu_depth_parity.py: the 0.999

@@ -260,8 +260,9 @@ def test_the_elevation_tasks_fused_scanner_is_reproduced():
 
 # ---- 10. the lidar as a yardstick ------------------------------------------------------------------------------------
 
-def test_a_lidar_pattern_through_the_ray_caster_equals_the_lidar_kernel():
-    """same device functions, same inputs: bit for bit"""
+def test_a_lidar_scanner_equals_a_ray_caster_built_by_hand_from_its_pattern_and_mount():
+    """LidarScanner's translation of a LidarCfg (pattern, mount, attach_yaw_only, max_range) against the RayCasterCfg written out by
+    hand: same kernel, same inputs, bit for bit"""
     from oracle import heightfield as HF
     from wheeledlab_amd.core import LidarScanner, RayCaster
     from wheeledlab_amd.envs.sensors_cfg import LidarCfg, LidarPatternCfg, RayCasterCfg
@@ -277,6 +278,23 @@ def test_a_lidar_pattern_through_the_ray_caster_equals_the_lidar_kernel():
         got = rc.render(b, cam)
         torch.cuda.synchronize()
         assert torch.equal(got, lidar) and float((got < 10.0).float().mean()) > 0.1 and bool((got == 10.0).any())
+
+
+def test_a_lidar_that_points_straight_down_on_a_yaw_mount_is_still_walked():
+    """one channel at -90 degrees with attach_yaw_only: every direction is vertical, which would select the column form in a
+    RayCaster left to choose; a LidarScanner forces the walk, and its ranges are the lidar reference's"""
+    from oracle import heightfield as HF
+    from wheeledlab_amd.core import LidarScanner
+    from wheeledlab_amd.envs.sensors_cfg import LidarCfg, LidarPatternCfg
+    cam = _camera(HF.make_terrain())
+    pos, quat = LR.poses(4, seed=101, field=_oracle_field(cam))
+    pat = LidarPatternCfg(channels=1, vertical_fov_range=(-90.0, -90.0))
+    sc = LidarScanner(LidarCfg(pattern_cfg=pat, attach_yaw_only=True), DEV)
+    assert sc.vertical is False and sc.n_beams == 360
+    got = _np(sc.render(_posed(pos, quat), camera=cam))
+    want = LR.ranges(pos, quat, pat.directions(), _oracle_field(cam), 10.0, yaw_only=True)
+    LR.check(got, want, 10.0, "straight down, yaw mount")
+    assert (want < 10.0).all() and (got > 0).all()
 
 
 # ---- 11. the depth camera as a yardstick -----------------------------------------------------------------------------

@@ -1,29 +1,16 @@
-"""CPU checks of the lidar: the beam pattern's count and order, LidarCfg's defaults, the lidar header's layout and symbols, every
-argument refusal of wl_lidar_scan before any launch, and the device's per-beam functions (wl_lidar_dev.h) compiled for the host and
-held to the float64 reference (tests/lidar_reference.py: oracle/depth.c one ray per beam)."""
-import ctypes as C
+"""CPU checks of the lidar: the beam pattern's count and order, LidarCfg's defaults, the scene's views, and the device's per-ray
+functions (wl_raycast_dev.h) compiled for the host, driven with a lidar's table (no starts) and held to the float64 reference
+(tests/lidar_reference.py: oracle/depth.c one ray per beam).  The C entry a lidar scans through is the ray caster's
+(tests/test_raycaster_cpu.py: layout, symbols, every argument refusal)."""
 import math
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from tests import heightfield_cases as HC
 from tests import lidar_reference as LR
-from wheeledlab_amd import _abi as A
-
-HEADER = os.path.join(ROOT, "include", "wheeledlab_amd_lidar.h")
-CLANG = os.environ.get("WL_HOST_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-
-
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    return A.load()
+from tests import raycaster_host as RH
+from tests.raycaster_host import hostlib  # noqa: F401  (the fixture)
 
 
 # ---- pattern and config ----------------------------------------------------------------------------------------------
@@ -105,105 +92,14 @@ def test_scene_registers_every_lidar_under_its_attribute_name():
                                     task="elevation").sensors
 
 
-# ---- the C boundary --------------------------------------------------------------------------------------------------
-
-def test_lidar_params_layout_matches_header(tmp_path):
-    fields = [n for n, _ in A.WlLidarParams._fields_]
-    probe = tmp_path / "probe.c"
-    body = " ".join(f'printf("%zu ", offsetof(WlLidarParams, {n}));' for n in fields)
-    probe.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wheeledlab_amd_lidar.h"\n'
-                     f'int main(){{{body} printf("%zu %d %d %d\\n", sizeof(WlLidarParams), (int)WL_LIDAR_VERSION, (int)WL_LIDAR_MAX_BEAMS,'
-                     ' (int)WL_ABI_VERSION); return 0;}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(probe), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = [getattr(A.WlLidarParams, n).offset for n in fields] + [C.sizeof(A.WlLidarParams), A.WL_LIDAR_VERSION, A.LIDAR_MAX_BEAMS,
-                                                                   A.WL_ABI_VERSION]
-    assert got == want and A.WL_ABI_VERSION == 24
-
-
-def test_lidar_symbols_exported_and_bound():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(wl_[a-z0-9_]+)\s*\(", src))
-    assert declared == set(A.LIDAR_SIGNATURES)
-    assert not declared & (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES))    # outside the step boundary
-    lib = _lib()
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None
-    assert lib.wl_lidar_version() == 1 == A.WL_LIDAR_VERSION
-
-
-def test_lidar_scan_refuses_bad_arguments_without_a_gpu():
-    """every defect alone is refused with its code before anything is launched (no GPU here: a launch would fail as WL_ELAUNCH)"""
-    lib = _lib()
-    fake = 1 << 20                 # never dereferenced: every call below returns before any launch
-    P, B, H = A.WlLidarParams, A.WlEnvBuffers, A.WlHeightField
-    params = lambda pos=(0.0, 0.0, 0.2), quat=(1.0, 0.0, 0.0, 0.0), nb=360, mr=10.0, yaw=0: P((C.c_float * 3)(*pos), (C.c_float * 4)(*quat),
-                                                                                             nb, mr, yaw)
-    bufs = lambda state=fake, stride=128, n=100: B(state, fake, None, fake, stride, n, 0, 1, 0, 0)
-    field = lambda nx=800, ny=800, cell=0.05, zs=2.0 ** -13, h=fake: H(h, nx, ny, -20.0, -20.0, cell, 0.0, zs, None)
-    good = dict(p=params(), b=bufs(), hf=field(), pyr=fake, dirs=fake, out=fake)
-
-    def call(**kw):
-        a = {**good, **kw}
-        ref = lambda s: C.byref(s) if s is not None else None
-        return lib.wl_lidar_scan(ref(a["p"]), ref(a["b"]), ref(a["hf"]), a["pyr"], a["dirs"], a["out"], None)
-    inf, nan = float("inf"), float("nan")
-    assert call(b=bufs(n=0)) == 0                                          # n == 0: WL_OK, nothing launched
-    assert call(b=bufs(n=0), p=params(nb=A.LIDAR_MAX_BEAMS)) == 0
-    for k in ("p", "b", "hf"):
-        assert call(**{k: None}) == -1, k
-    for k in ("pyr", "dirs", "out"):
-        assert call(**{k: None}) == -1, k
-    assert call(b=bufs(state=None)) == -1 and call(hf=field(h=None)) == -1
-    for nb in (0, -1, A.LIDAR_MAX_BEAMS + 1):
-        assert call(p=params(nb=nb)) == -1, nb
-    for mr in (0.0, -1.0, inf, nan):
-        assert call(p=params(mr=mr)) == -1, mr
-    for pos in ((nan, 0.0, 0.0), (0.0, inf, 0.0)):
-        assert call(p=params(pos=pos)) == -1
-    for quat in ((0.0, 0.0, 0.0, 0.0), (nan, 0.0, 0.0, 0.0), (inf, 0.0, 0.0, 0.0), (1e30, 1e30, 0.0, 0.0)):
-        assert call(p=params(quat=quat)) == -1, quat
-    # the heightfield checks of wl_visual_depth
-    for f in (field(nx=1), field(ny=1), field(cell=0.0), field(cell=inf), field(zs=0.0), field(zs=nan), field(nx=16386, ny=4),
-              field(nx=4, ny=16386)):
-        assert call(hf=f) == -1
-    assert call(b=bufs(n=-1)) == -1
-    assert call(b=bufs(stride=64, n=100)) == -1                            # stride below n
-    assert call(b=bufs(stride=1 << 24, n=100)) == -1                       # rows beyond one 32-bit buffer resource
-    assert call(b=bufs(stride=200064, n=200000), p=params(nb=A.LIDAR_MAX_BEAMS)) == -1      # more waves than a grid holds
-    for k, v in (("pyr", fake + 2), ("dirs", fake + 1), ("out", fake + 2)):
-        assert call(**{k: v}) == -3, k
-    assert call(b=bufs(state=fake + 2)) == -3
-
-
 # ---- the device functions on the host --------------------------------------------------------------------------------
 
-@pytest.fixture(scope="module")
-def hostlib(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("no clang++ to build the host simulation")
-    out = tmp_path_factory.mktemp("host_sim") / "libwl_lidar_host.so"
-    subprocess.run([CLANG, "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                    "-I", os.path.join(ROOT, "tests", "host_sim", "hip_stub"), "-I", os.path.join(ROOT, "wheeledlab_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_sim", "lidar_host.cpp"), "-o", str(out)], check=True)
-    lib = C.CDLL(str(out))
-    lib.hs_lidar.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    return lib
-
-
 def host_scan(hostlib, field, pos, quat, dirs, max_range, outside_z=0.0, z_scale=None, offset_pos=(0.0, 0.0, 0.18),
-              offset_rot=(1.0, 0.0, 0.0, 0.0), yaw_only=False, steps=False):
-    from tests import depth_cases as DC
-    hfs, _keep = DC.hf_struct(field, outside_z, z_scale)
-    d = np.ascontiguousarray(dirs, np.float32)
-    p = A.WlLidarParams((C.c_float * 3)(*offset_pos), (C.c_float * 4)(*offset_rot), len(d), max_range, int(yaw_only))
-    out = np.zeros((len(pos), len(d)), np.float32)
-    st = np.zeros((len(pos), len(d)), np.int32) if steps else None
-    assert hostlib.hs_lidar(C.byref(p), C.byref(hfs), len(pos), np.ascontiguousarray(pos).ctypes.data,
-                            np.ascontiguousarray(quat).ctypes.data, d.ctypes.data, out.ctypes.data,
-                            None if st is None else st.ctypes.data) == 0
-    return (out, st) if steps else out
+              offset_rot=(1.0, 0.0, 0.0, 0.0), yaw_only=False):
+    """ranges [n, B]: the ray caster's host simulation without a start table (every beam leaves the sensor origin), as LidarScanner
+    calls the kernel"""
+    return RH.host_scan(hostlib, field, pos, quat, None, dirs, max_range, outside_z, z_scale, offset_pos=offset_pos,
+                        offset_rot=offset_rot, alignment="yaw" if yaw_only else "base")[0]
 
 
 @pytest.mark.parametrize("max_range", [10.0, 30.0])

@@ -78,8 +78,7 @@ def test_history_symbols_exported_and_bound():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(wl_[a-z0-9_]+)\s*\(", src))
     assert declared == set(A.OBSHIST_SIGNATURES) == {"wl_obs_history_version", "wl_obs_history_width", "wl_obs_history_push"}
-    others = (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES) | set(A.LIDAR_SIGNATURES) | set(A.OBSNORM_SIGNATURES)
-              | set(A.RAYCASTER_SIGNATURES))
+    others = set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES) | set(A.OBSNORM_SIGNATURES) | set(A.RAYCASTER_SIGNATURES)
     assert not declared & others
     lib = _lib()
     for name in declared:

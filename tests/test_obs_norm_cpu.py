@@ -31,7 +31,7 @@ def test_obsnorm_symbols_exported_and_bound():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(wl_[a-z0-9_]+)\s*\(", src))
     assert declared == set(A.OBSNORM_SIGNATURES)
-    assert not declared & (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES) | set(A.LIDAR_SIGNATURES))
+    assert not declared & (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES) | set(A.RAYCASTER_SIGNATURES))
     lib = _lib()
     for name in declared:
         assert getattr(lib, name).argtypes is not None

@@ -5,7 +5,6 @@ one ray per table entry; a float64 bilinear for the column form).  Yardstick for
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,10 +14,10 @@ from conftest import ROOT
 from tests import heightfield_cases as HC
 from tests import lidar_reference as LR
 from tests import raycaster_reference as RR
+from tests.raycaster_host import host_scan, hostlib  # noqa: F401  (the fixture)
 from wheeledlab_amd import _abi as A
 
 HEADER = os.path.join(ROOT, "include", "wheeledlab_amd_raycaster.h")
-CLANG = os.environ.get("WL_HOST_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 
 
 def _lib():
@@ -173,11 +172,13 @@ def test_raycast_symbols_exported_and_bound():
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(wl_[a-z0-9_]+)\s*\(", src))
     assert declared == set(A.RAYCASTER_SIGNATURES) == {"wl_raycast_scan", "wl_raycast_version"}
-    assert not declared & (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES) | set(A.LIDAR_SIGNATURES))
+    assert not declared & (set(A.SIGNATURES) | set(A.VIEWER_SIGNATURES) | set(A.TERRAIN_SIGNATURES))
     lib = _lib()
     for name in declared:
         assert getattr(lib, name).argtypes is not None
-    assert lib.wl_raycast_version() == 1 == A.WL_RAYCASTER_VERSION
+    assert lib.wl_raycast_version() == 2 == A.WL_RAYCASTER_VERSION
+    for gone in ("wl_lidar_scan", "wl_lidar_version"):      # the lidar scans through wl_raycast_scan: its own entry is retired
+        assert not hasattr(lib, gone), gone
 
 
 def test_raycast_scan_refuses_bad_arguments_without_a_gpu():
@@ -205,8 +206,11 @@ def test_raycast_scan_refuses_bad_arguments_without_a_gpu():
     for al in (1, 2):
         assert call(b=empty, p=params(al=al)) == 0 and call(b=empty, p=params(al=al, vert=1), dirs=None) == 0
     assert call(b=empty, p=params(al=1, vert=1, quat=(0.8, 0.0, 0.0, 0.6)), dirs=None) == 0          # a mount about z
-    for k in ("p", "b", "hf", "pyr", "starts", "dirs"):
+    for k in ("p", "b", "hf", "pyr", "dirs"):
         assert call(**{k: None}) == -1, k
+    # no start table: every ray leaves the sensor origin -- legal in the general form only
+    assert call(b=empty, starts=None) == 0 and call(b=empty, starts=None, hits=None, scale=fake) == 0
+    assert call(starts=None, p=params(al=1, vert=1), dirs=None) == -1 and call(b=empty, starts=None, p=params(al=1, vert=1), dirs=None) == -1
     assert call(dist=None, hits=None) == -1                                # both outputs NULL
     assert call(b=bufs(state=None)) == -1 and call(hf=field(h=None)) == -1
     for nr in (0, -1, A.RAYCAST_MAX_RAYS + 1):
@@ -240,37 +244,13 @@ def test_raycast_scan_refuses_bad_arguments_without_a_gpu():
     for k, v in (("pyr", fake + 2), ("starts", fake + 1), ("dirs", fake + 2), ("scale", fake + 1), ("dist", fake + 2), ("hits", fake + 3)):
         assert call(**{k: v}) == -3, k
     assert call(b=bufs(state=fake + 2)) == -3
+    # a lidar's shape of the call: no start table, distances only, no scale
+    lidar = dict(starts=None, scale=None, hits=None)
+    assert call(b=empty, **lidar) == 0 and call(**lidar, dist=None) == -1 and call(**lidar, dist=fake + 2) == -3
+    assert call(**lidar, dirs=None) == -1 and call(**lidar, dirs=fake + 1) == -3 and call(**lidar, p=params(md=inf)) == -1
 
 
 # ---- 5. the device functions on the host -----------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def hostlib(tmp_path_factory):
-    if not (os.path.exists(CLANG) or shutil.which(CLANG)):
-        pytest.skip("no clang++ to build the host simulation")
-    out = tmp_path_factory.mktemp("host_sim") / "libwl_raycaster_host.so"
-    subprocess.run([CLANG, "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                    "-I", os.path.join(ROOT, "tests", "host_sim", "hip_stub"), "-I", os.path.join(ROOT, "wheeledlab_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "host_sim", "raycaster_host.cpp"), "-o", str(out)], check=True)
-    lib = C.CDLL(str(out))
-    lib.hs_raycast.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-    return lib
-
-
-def host_scan(hostlib, field, pos, quat, starts, dirs, max_distance, outside_z=0.0, z_scale=None, scale=None, vertical=False,
-              offset_pos=(0.0, 0.0, 0.0), offset_rot=(1.0, 0.0, 0.0, 0.0), alignment="base"):
-    """-> (dist [n, R], hits [n, R, 3]) of the device functions on the host"""
-    from tests import depth_cases as DC
-    hfs, _keep = DC.hf_struct(field, outside_z, z_scale)
-    s, d = np.ascontiguousarray(starts, np.float32), np.ascontiguousarray(dirs, np.float32)
-    sc = None if scale is None else np.ascontiguousarray(scale, np.float32)
-    p = A.WlRayCastParams((C.c_float * 3)(*offset_pos), (C.c_float * 4)(*offset_rot), len(s), max_distance, A.RAYCAST_ALIGNMENTS[alignment],
-                          int(vertical))
-    dist, hits = np.zeros((len(pos), len(s)), np.float32), np.zeros((len(pos), len(s), 3), np.float32)
-    assert hostlib.hs_raycast(C.byref(p), C.byref(hfs), len(pos), np.ascontiguousarray(pos).ctypes.data, np.ascontiguousarray(quat).ctypes.data,
-                              s.ctypes.data, d.ctypes.data, None if sc is None else sc.ctypes.data, dist.ctypes.data, hits.ctypes.data) == 0
-    return dist, hits
-
 
 def _fields():
     from oracle import heightfield as HF
@@ -318,6 +298,22 @@ def test_walked_rays_on_the_host_match_the_oracle(hostlib, max_distance):
             check_hits(dist, hits, *RR.world_rays(pos, quat, starts, dirs, **mount), scale, max_distance)
             hit_any, miss_any = hit_any or (want < max_distance).any(), miss_any or (want >= max_distance).any()
         assert hit_any and miss_any, name
+
+
+def test_no_start_table_on_the_host_equals_a_table_of_zeros(hostlib):
+    """a lidar fan on the bench field, tilted mount, base and yaw alignment: the same bits with and without the start table"""
+    from oracle import heightfield as HF
+    from wheeledlab_amd.envs.sensors_cfg import LidarPatternCfg
+    field = HF.make_terrain()
+    pos, quat = LR.poses(16, seed=80, field=field, margin=1.0)
+    dirs = LidarPatternCfg(channels=4, vertical_fov_range=(-15.0, 5.0), horizontal_res=3.0).directions()
+    for alignment in ("base", "yaw"):
+        mount = dict(offset_pos=(0.1, -0.05, 0.25), offset_rot=(0.9914449, 0.0, 0.1305262, 0.0), alignment=alignment)
+        table = host_scan(hostlib, field, pos, quat, np.zeros_like(dirs), dirs, 10.0, **mount)
+        none = host_scan(hostlib, field, pos, quat, None, dirs, 10.0, **mount)
+        for a, b in zip(table, none):
+            np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+        assert (table[0] < 10.0).any() and (table[0] == 10.0).any()
 
 
 # the elevation scanner's grid 20 m above the car and a look-ahead grid 0.3 m above it (30 m: past the relief of every field here, so that no column misses)

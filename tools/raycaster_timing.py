@@ -10,6 +10,8 @@ Workload: the bench field, 4096 envs of an ElevBatch after a reset and a few ste
   observe       ElevBatch.observe() of the same batch: the task's own fused scan -- exists in a parent checkout too
   rc_camera     a 60 x 80 ray-caster camera with the visual camera's intrinsics and mount, 20 m
   depth_camera  DepthCamera.render at 20 m (the tiled kernel) -- exists in a parent checkout too
+  lidar         a default LidarCfg (1 x 360 beams, 10 m) through LidarScanner.render -- exists in a parent checkout too
+  lidar_plane   the same over the z = 0 plane of a DriftBatch (launch- and store-bound) -- exists in a parent checkout too
 
 `--root DIR` measures another checkout of the package (the parent commit's, built there): the configurations it has.
 
@@ -73,6 +75,12 @@ def main():
         flat_image = image.view(n, -1)
         runs.update(column=lambda: column.render(batch, cam, out=grid_out), walk=lambda: walk.render(batch, cam, out=grid_out),
                     rc_camera=lambda: rc_cam.render(batch, cam, out=flat_image))
+    if hasattr(core, "LidarScanner"):
+        lidar = core.LidarScanner(device=dev)
+        drift = core.DriftBatch(n, device=dev, seed=3)
+        drift.reset()
+        ranges = torch.empty(n, lidar.n_beams, dtype=torch.float32, device=dev)
+        runs.update(lidar=lambda: lidar.render(batch, out=ranges, camera=cam), lidar_plane=lambda: lidar.render(drift, out=ranges))
     for fn in runs.values():
         for _ in range(10):
             fn()

@@ -342,24 +342,8 @@ TERRAIN_SIGNATURES = {
     "wl_flat_patch_deal": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp]),
 }
 
-# include/wheeledlab_amd_lidar.h: lidar range scans -- a header of its own, outside the drop-in step boundary (WL_ABI_VERSION)
-WL_LIDAR_VERSION = 1
-LIDAR_MAX_BEAMS = 1 << 20
-
-
-class WlLidarParams(C.Structure):
-    _fields_ = [("offset_pos", C.c_float * 3), ("offset_quat", C.c_float * 4), ("n_beams", C.c_int32), ("max_range", C.c_float),
-                ("yaw_only", C.c_int32)]
-
-
-# every symbol include/wheeledlab_amd_lidar.h declares
-LIDAR_SIGNATURES = {
-    "wl_lidar_version": (C.c_int, []),
-    "wl_lidar_scan": (C.c_int, [_P(WlLidarParams), _P(WlEnvBuffers), _P(WlHeightField), _vp, _vp, _vp, _vp]),
-}
-
 # include/wheeledlab_amd_raycaster.h: ray-caster sensors over any ray table -- a header of its own, outside the drop-in step boundary
-WL_RAYCASTER_VERSION = 1
+WL_RAYCASTER_VERSION = 2
 RAYCAST_MAX_RAYS = 1 << 20
 RAYCAST_ALIGNMENTS = {"base": 0, "yaw": 1, "world": 2}
 
@@ -428,7 +412,7 @@ def load(path: str | None = None):
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **LIDAR_SIGNATURES, **OBSNORM_SIGNATURES,
+    for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **OBSNORM_SIGNATURES,
                                **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
@@ -444,8 +428,6 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has viewer version {lib.wl_viewer_version()}, python expects {WL_VIEWER_VERSION}: rebuild")
     if lib.wl_terrain_version() != WL_TERRAIN_VERSION:
         raise HipExtensionMissing(f"{path} has terrain version {lib.wl_terrain_version()}, python expects {WL_TERRAIN_VERSION}: rebuild")
-    if lib.wl_lidar_version() != WL_LIDAR_VERSION:
-        raise HipExtensionMissing(f"{path} has lidar version {lib.wl_lidar_version()}, python expects {WL_LIDAR_VERSION}: rebuild")
     if lib.wl_obsnorm_version() != WL_OBSNORM_VERSION:
         raise HipExtensionMissing(f"{path} has obsnorm version {lib.wl_obsnorm_version()}, python expects {WL_OBSNORM_VERSION}: rebuild")
     if lib.wl_raycast_version() != WL_RAYCASTER_VERSION:

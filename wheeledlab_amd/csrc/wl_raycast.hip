@@ -1,12 +1,16 @@
 // wl_raycast.hip -- the ray caster (include/wheeledlab_amd_raycaster.h) for gfx950: any table of rays from every env's sensor against
-// the terrain solid.  The walk, the pyramid, the yaw rule and the bilinear sampler are the depth camera's, the lidar's and the contact
-// samplers', included unchanged; this file maps table entries to lanes and stores what they report.
+// the terrain solid.  The walk and the pyramid are the depth camera's (wl_depth_dev.h::cast_ray: the bound pyramid, then the exact
+// bilinear-patch intersection; with a unit direction the ray parameter at the hit is the Euclidean range), the bilinear sampler the
+// contact samplers', included unchanged; this file maps table entries to lanes and stores what they report.  A lidar is a table of
+// this entry: zero starts, no scale, distances only (sensors.LidarScanner).
 //
-// General form.  The lidar's mapping (wl_lidar.hip), for its reason: block = ONE wavefront = 64 consecutive rays of one env -- walk
-// lengths vary a lot from wave to wave, and the dispatcher refills a single-wave block's slot the moment it is done.  env x wave is
-// flattened into blockIdx.x (n > 65 535 envs).  The pose is read and the sensor frame built once per wave (wave-uniform); each lane
-// loads its start and direction, walks its ray and stores its distance and / or hit point non-temporally, so that the scan does not
-// push the pyramid out of L2 (the depth kernel's measured rule).
+// General form.  Block = ONE wavefront = 64 consecutive rays of one env (a lidar fan is channel-major: neighbouring lanes are
+// neighbouring azimuths of one channel, whose ground tracks cross neighbouring cells -- the lanes walk together and share cache
+// lines).  Single-wavefront blocks for the depth kernel's reason (wl_depth.hip): walk lengths vary a lot from wave to wave, and the
+// dispatcher refills a single-wave block's slot the moment it is done.  env x wave is flattened into blockIdx.x (n > 65 535 envs).
+// The pose is read and the sensor frame built once per wave (wave-uniform); each lane loads its start and direction, walks its ray and
+// stores its distance and / or hit point non-temporally (consecutive lanes, consecutive floats of dist[e]), so that the scan does not
+// push the pyramid and the heights out of L2 (the depth kernel's measured rule).
 //
 // Column form (p.vertical).  Lane = ray, same flattening, no pyramid access, no barriers, no LDS: the lane's world (x, y) from the
 // yaw rotation of its start, one 8-byte pair-table gather (hf_corners), the bilinear blend.  Block = 64 as well: a wave is ~300
@@ -30,7 +34,7 @@ struct RayCastOut {
     float* hits;          // [n_envs][n_rays][3] or nullptr
 };
 
-WL_DEV LidarPose wave_frame(const WlRayCastParams& p, const WlEnvBuffers& b, int e) {
+WL_DEV SensorFrame wave_frame(const WlRayCastParams& p, const WlEnvBuffers& b, int e) {
     const Rows S = make_rows(b.state, b.stride);
     const Quat q{S.ld(WL_S_QW, e), S.ld(WL_S_QX, e), S.ld(WL_S_QY, e), S.ld(WL_S_QZ, e)};
     const Mat3 mount = mat_from_quat(Quat{p.offset_quat[0], p.offset_quat[1], p.offset_quat[2], p.offset_quat[3]});
@@ -52,10 +56,12 @@ __global__ void __launch_bounds__(64) raycast_walk_kernel(const WlRayCastParams 
                                                           const float* __restrict__ starts, const float* __restrict__ dirs,
                                                           const RayCastOut out, const int waves) {
     const int e = blockIdx.x / waves, w = blockIdx.x - e * waves;
-    const LidarPose s = wave_frame(p, b, e);
+    const SensorFrame s = wave_frame(p, b, e);
     const int k = w * 64 + (int)threadIdx.x;
     if (k >= p.n_rays) return;
-    const V3 st = v3(starts[3 * k], starts[3 * k + 1], starts[3 * k + 2]), d = v3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
+    // no start table (wave-uniform): every ray leaves the sensor origin, and the lane loads its direction alone
+    const V3 st = starts ? v3(starts[3 * k], starts[3 * k + 1], starts[3 * k + 2]) : v3(0.f, 0.f, 0.f);
+    const V3 d = v3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
     const FieldMem mem{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(buf), 0, (int)buf_bytes, 0x00020000)};
     store_ray(p, out, e, k, raycast_walk(g, py, pyramid_head(g, py, mem), mem, s, st, d, p.max_distance));
 }
@@ -63,7 +69,7 @@ __global__ void __launch_bounds__(64) raycast_walk_kernel(const WlRayCastParams 
 __global__ void __launch_bounds__(64) raycast_column_kernel(const WlRayCastParams p, const WlEnvBuffers b, const HeightFieldGround gr,
                                                             const float* __restrict__ starts, const RayCastOut out, const int waves) {
     const int e = blockIdx.x / waves, w = blockIdx.x - e * waves;
-    const LidarPose s = wave_frame(p, b, e);
+    const SensorFrame s = wave_frame(p, b, e);
     const int k = w * 64 + (int)threadIdx.x;
     if (k >= p.n_rays) return;
     store_ray(p, out, e, k, raycast_column(gr, s, v3(starts[3 * k], starts[3 * k + 1], starts[3 * k + 2]), p.max_distance));
@@ -79,7 +85,7 @@ int wl_raycast_version(void) { return WL_RAYCASTER_VERSION; }
 
 int wl_raycast_scan(const WlRayCastParams* p, const WlEnvBuffers* b, const WlHeightField* hf, const float* pyramid, const float* ray_starts,
                     const float* ray_dirs, const float* ray_scale, float* dist_out, float* hits_out, void* stream) {
-    if (!p || !b || !b->state || !pyramid || !ray_starts || (!dist_out && !hits_out) || b->n_envs < 0) return WL_EINVAL;
+    if (!p || !b || !b->state || !pyramid || (!dist_out && !hits_out) || b->n_envs < 0) return WL_EINVAL;
     if (p->n_rays < 1 || p->n_rays > WL_RAYCAST_MAX_RAYS || !(p->max_distance > 0.f && p->max_distance < INFINITY)) return WL_EINVAL;
     if (p->alignment < WL_RAYCAST_ALIGN_BASE || p->alignment > WL_RAYCAST_ALIGN_WORLD || (p->vertical != 0 && p->vertical != 1)) return WL_EINVAL;
     float qn = 0.f;
@@ -88,6 +94,7 @@ int wl_raycast_scan(const WlRayCastParams* p, const WlEnvBuffers* b, const WlHei
         if (!std::isfinite(p->offset_pos[i])) return WL_EINVAL;
     if (!(qn > 0.f && qn < INFINITY)) return WL_EINVAL;
     if ((ray_dirs == nullptr) != (p->vertical == 1)) return WL_EINVAL;      // directions: NULL if and only if the column form
+    if (!ray_starts && p->vertical) return WL_EINVAL;                       // starts: NULL (all zero) in the general form only
     if (p->vertical && (p->alignment == WL_RAYCAST_ALIGN_BASE || p->offset_quat[1] != 0.f || p->offset_quat[2] != 0.f)) return WL_EINVAL;
     int rc = heightfield_args_ok(hf, HF_PYRAMID);
     if (rc != WL_OK) return rc;

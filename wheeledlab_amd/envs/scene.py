@@ -299,11 +299,18 @@ class _CameraOutputs:
         return ["distance_to_image_plane"]
 
 
-class CameraView:
+class SensorView:
+    """`env.scene.sensors[name]`: the sensor's config and its `data` object, of the subclass's `data_class`"""
+    data_class = None
+
     def __init__(self, batch, cfg):
         self.cfg = cfg
-        self.data = CameraData(batch, cfg)
+        self.data = self.data_class(batch, cfg)
         self.num_instances = batch.n
+
+
+class CameraView(SensorView):
+    data_class = CameraData
 
 
 def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -333,104 +340,24 @@ def _scan_once_per_step(data, scan):
     return data._cached[1]
 
 
-class LidarData:
-    """`sensor.data` of a scene lidar (envs.sensors_cfg.LidarCfg; an IsaacLab RayCaster with a lidar pattern, un-vendored):
-    `output["linear_depth"]` [N, B] -- the ranges `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized` read (mdp_sensors/
-    observations.py:25-58) -- rendered by the lidar kernel (sensors.LidarScanner, wl_lidar_scan) against the task's terrain;
-    `ray_hits_w` [N, B, 3] (+inf where a beam meets nothing within max_range, as Warp's ray caster reports a miss); `pos_w` [N, 3]
-    and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like CameraData."""
-
-    def __init__(self, batch, cfg):
-        self._b, self._cfg, self._scanner = batch, cfg, None
-        self._cached = (None, None)       # ((step_count, pose_epoch), ranges): see CameraData
-        self.caching = True               # the env's constructor switches it off around its shape probe of the custom terms
-        self.max_range = float(cfg.max_range)
-        self.beyond = {"max": None, "zero": 0.0, "none": float("inf")}[cfg.miss_value]
-
-    def scanner(self):
-        if self._scanner is None:
-            from ..sensors import LidarScanner
-            self._scanner = LidarScanner(self._cfg, self._b.device)
-        return self._scanner
-
-    def ranges(self) -> torch.Tensor:
-        """the raw scan of the current poses: max_range on a miss (cached per env step; do not write into it)"""
-        return _scan_once_per_step(self, lambda: self.scanner().render(self._b))
-
-    @property
-    def output(self):
-        return _LidarOutputs(self)
-
-    def _body_quat(self):
-        b = self._b
-        q = b.state[A.S_QW:A.S_QW + 4, : b.n].T
-        if not self._cfg.attach_yaw_only:
-            return q
-        # the yaw alone (IsaacLab's yaw_quat): the heading of the body's x axis in the world xy plane
-        w, x, y, z = q.unbind(-1)
-        yaw = torch.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
-        zero = torch.zeros_like(yaw)
-        return torch.stack([torch.cos(0.5 * yaw), zero, zero, torch.sin(0.5 * yaw)], -1)
-
-    @property
-    def pos_w(self):
-        b = self._b
-        off = torch.tensor(self._cfg.offset_pos, dtype=torch.float32, device=b.device).expand(b.n, 3)
-        return b.state[A.S_PX:A.S_PX + 3, : b.n].T + _quat_apply(self._body_quat(), off)
-
-    @property
-    def quat_w(self):
-        mount = torch.tensor(self.scanner().params.offset_quat[:], dtype=torch.float32, device=self._b.device)
-        return _quat_mul(self._body_quat(), mount.expand(self._b.n, 4))
-
-    @property
-    def ray_hits_w(self):
-        r = self.ranges()
-        q = self.quat_w
-        d = _quat_apply(q[:, None, :].expand(-1, r.shape[1], -1), self.scanner().beam_dirs[None].expand(r.shape[0], -1, -1))
-        hits = self.pos_w[:, None, :] + r[..., None] * d
-        return torch.where((r >= self.max_range)[..., None], torch.full_like(hits, float("inf")), hits)
-
-
-class _LidarOutputs:
-    def __init__(self, data):
-        self._d = data
-
-    def __getitem__(self, key):
-        if key != "linear_depth":
-            raise KeyError(f"lidar data type {key!r} is not rendered here (the scan gives 'linear_depth')")
-        d = self._d
-        r = d.ranges()
-        if d.beyond is not None:      # what a miss reads is applied per read, the scan itself is cached
-            r = torch.where(r >= d.max_range, torch.full_like(r, d.beyond), r)
-        return r
-
-    def keys(self):
-        return ["linear_depth"]
-
-
-class LidarView:
-    def __init__(self, batch, cfg):
-        self.cfg = cfg
-        self.data = LidarData(batch, cfg)
-        self.num_instances = batch.n
-
-
 class RayCasterSensorData:
     """`sensor.data` of a scene ray caster (envs.sensors_cfg.RayCasterCfg with any pattern; IsaacLab's RayCaster, un-vendored), cast by
     sensors.RayCaster (wl_raycast_scan) against the task's terrain: `ray_hits_w` [N, R, 3] (+inf where a ray meets nothing within
     max_distance, as Warp's ray caster reports a miss) -- what `mdp.height_scan` reads -- `distances` [N, R] (max_distance on a miss),
-    `pos_w` [N, 3] and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like LidarData."""
+    `pos_w` [N, 3] and `quat_w` [N, 4] (w, x, y, z) of the sensor.  One scan per (step_count, pose_epoch), like CameraData."""
 
     def __init__(self, batch, cfg):
         self._b, self._cfg, self._scanner = batch, cfg, None
         self._cached = (None, None)       # ((step_count, pose_epoch), (distances, hits))
         self.caching = True               # the env's constructor switches it off around its shape probe of the custom terms
 
+    def _new_scanner(self):
+        from ..sensors import RayCaster
+        return RayCaster(self._cfg, self._b.device)
+
     def scanner(self):
         if self._scanner is None:
-            from ..sensors import RayCaster
-            self._scanner = RayCaster(self._cfg, self._b.device)
+            self._scanner = self._new_scanner()
         return self._scanner
 
     def _scan(self):
@@ -438,14 +365,17 @@ class RayCasterSensorData:
         return _scan_once_per_step(self, lambda: self.scanner().scan(self._b))
 
     def _body_quat(self):
-        b = self._b
+        """what turns the sensor, by the config's alignment (no scanner, no device): the body's rotation ("base": a ray-caster camera,
+        a lidar without attach_yaw_only), its yaw alone (IsaacLab's yaw_quat: the heading of the body's x axis in the world xy plane)
+        or nothing ("world")"""
+        b, cfg = self._b, self._cfg
         q = b.state[A.S_QW:A.S_QW + 4, : b.n].T
-        align = self.scanner().alignment
+        align = cfg.alignment() if hasattr(cfg, "alignment") else "yaw" if getattr(cfg, "attach_yaw_only", False) else "base"
         if align == "base":
             return q
         if align == "world":
             return torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=b.device).expand(b.n, 4)
-        w, x, y, z = q.unbind(-1)          # the yaw alone, as LidarData
+        w, x, y, z = q.unbind(-1)
         yaw = torch.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
         zero = torch.zeros_like(yaw)
         return torch.stack([torch.cos(0.5 * yaw), zero, zero, torch.sin(0.5 * yaw)], -1)
@@ -471,11 +401,58 @@ class RayCasterSensorData:
         return self._scan()[1]
 
 
-class RayCasterSensorView:
+class LidarData(RayCasterSensorData):
+    """`sensor.data` of a scene lidar (envs.sensors_cfg.LidarCfg; an IsaacLab RayCaster with a lidar pattern, un-vendored):
+    `output["linear_depth"]` [N, B] -- the ranges `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized` read (mdp_sensors/
+    observations.py:25-58) -- scanned by sensors.LidarScanner (the ray caster's walk, distances only) against the task's terrain;
+    `ray_hits_w` [N, B, 3] rebuilt from the ranges (+inf where a beam meets nothing within max_range, as Warp's ray caster reports a
+    miss); `pos_w`, `quat_w` and the one scan per (step_count, pose_epoch) are the ray caster's."""
+
     def __init__(self, batch, cfg):
-        self.cfg = cfg
-        self.data = RayCasterSensorData(batch, cfg)
-        self.num_instances = batch.n
+        super().__init__(batch, cfg)
+        self.max_range = float(cfg.max_range)
+        self.beyond = {"max": None, "zero": 0.0, "none": float("inf")}[cfg.miss_value]
+
+    def _new_scanner(self):
+        from ..sensors import LidarScanner
+        return LidarScanner(self._cfg, self._b.device)
+
+    def _scan(self):
+        """(ranges, None): the observation path pays for the distances alone"""
+        return _scan_once_per_step(self, lambda: (self.scanner().render(self._b), None))
+
+    def ranges(self) -> torch.Tensor:
+        """the raw scan of the current poses: max_range on a miss (cached per env step; do not write into it)"""
+        return self._scan()[0]
+
+    @property
+    def output(self):
+        return _LidarOutputs(self)
+
+    @property
+    def ray_hits_w(self):
+        r = self.ranges()
+        q = self.quat_w
+        d = _quat_apply(q[:, None, :].expand(-1, r.shape[1], -1), self.scanner().beam_dirs[None].expand(r.shape[0], -1, -1))
+        hits = self.pos_w[:, None, :] + r[..., None] * d
+        return torch.where((r >= self.max_range)[..., None], torch.full_like(hits, float("inf")), hits)
+
+
+class _LidarOutputs:
+    def __init__(self, data):
+        self._d = data
+
+    def __getitem__(self, key):
+        if key != "linear_depth":
+            raise KeyError(f"lidar data type {key!r} is not rendered here (the scan gives 'linear_depth')")
+        d = self._d
+        r = d.ranges()
+        if d.beyond is not None:      # what a miss reads is applied per read, the scan itself is cached
+            r = torch.where(r >= d.max_range, torch.full_like(r, d.beyond), r)
+        return r
+
+    def keys(self):
+        return ["linear_depth"]
 
 
 class RayCasterCameraData(RayCasterSensorData):
@@ -530,11 +507,16 @@ class _RayCasterCameraOutputs:
         return ["distance_to_image_plane", "distance_to_camera"]
 
 
-class RayCasterCameraView:
-    def __init__(self, batch, cfg):
-        self.cfg = cfg
-        self.data = RayCasterCameraData(batch, cfg)
-        self.num_instances = batch.n
+class LidarView(SensorView):
+    data_class = LidarData
+
+
+class RayCasterSensorView(SensorView):
+    data_class = RayCasterSensorData
+
+
+class RayCasterCameraView(SensorView):
+    data_class = RayCasterCameraData
 
 
 class TerrainLevelsView:

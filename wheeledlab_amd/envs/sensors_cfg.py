@@ -198,7 +198,7 @@ class LidarPatternCfg:
 
 @configclass
 class LidarCfg:
-    """A lidar of the scene: range scans of every env against the terrain (sensors.LidarScanner, csrc/wl_lidar.hip), exposed as
+    """A lidar of the scene: range scans of every env against the terrain (sensors.LidarScanner, csrc/wl_raycast.hip), exposed as
     `env.scene.sensors[name].data` with `output["linear_depth"]` [N, B] -- what `mdp.lidar_ranges` / `mdp.lidar_ranges_normalized`
     read, the latter with `min_range` / `max_range` -- and `ray_hits_w`, `pos_w`, `quat_w`.  Opt-in: `cfg.scene.lidar = LidarCfg()`.
     Terrain only (the heightfield of the elevation and visual-depth tasks, the z = 0 plane of the others), not other cars.

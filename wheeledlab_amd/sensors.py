@@ -47,8 +47,21 @@ class DepthCamera:
         return out
 
 
-class _TerrainSensor:
-    """what LidarScanner and RayCaster share: which terrain a batch's cars stand on"""
+def _quat_mul(a, b):
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return (aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+            aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw)
+
+
+class RayCaster:
+    """A ray caster (envs.sensors_cfg.RayCasterCfg or RayCasterCameraCfg) casting its table of rays against the terrain from the poses
+    of ANY batch (wl_raycast_scan).  Owns the table, built once from the pattern: `ray_starts` / `ray_dirs` [R, 3] in the sensor
+    frame (`ray_starts` None: all zero, no table is loaded) and, for a pinhole pattern, `ray_scale` [R] (each ray's cosine to the
+    optical axis: distances come out as distances to the image plane).  `vertical` -- every direction exactly (0, 0, -1), alignment yaw or world, mount about z only -- is decided here
+    and selects the kernel's column form (one bilinear sample per ray instead of a walk); `vertical=False` forces the walk.
+    scan() -> (distances [n, R], hits [n, R, 3]): the distance clipped at max_distance (max_distance on a miss, 0 from under the
+    terrain; times ray_scale), the hit point (+inf on a miss)."""
     _plane = None
 
     def camera_of(self, batch) -> DepthCamera:
@@ -61,63 +74,6 @@ class _TerrainSensor:
         if self._plane is None:       # one tensor per sensor: the batch's camera cache keys on it
             self._plane = (torch.zeros(3, 3, dtype=torch.float32, device=self.device), -1.0, -1.0, 1.0)
         return _cached_depth_camera(batch, self._plane)
-
-
-class LidarScanner(_TerrainSensor):
-    """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch (wl_lidar_scan): owns the beam table
-    (unit vectors in the sensor frame, built once from the pattern) and the launch parameters.  The terrain is the depth camera's:
-    field and pyramid come from the batch's cached DepthCamera, i.e. from the batch's DeviceHeightField (which owns the one pyramid).
-    render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
-    the terrain (what a miss reads in the scene is LidarData's business)."""
-
-    def __init__(self, cfg=None, device="cuda:0"):
-        from .envs.sensors_cfg import LidarCfg
-        self.lib = A.load()
-        self.device = _canonical_device(device)
-        if self.device.type != "cuda":
-            raise A.HipExtensionMissing("LidarScanner needs a HIP device; there is no CPU path")
-        self.cfg = cfg = cfg if cfg is not None else LidarCfg()
-        dirs = cfg.pattern_cfg.directions()
-        self.n_beams = int(dirs.shape[0])
-        if not 1 <= self.n_beams <= A.LIDAR_MAX_BEAMS:
-            raise ValueError(f"a lidar pattern of {self.n_beams} beams (1 .. {A.LIDAR_MAX_BEAMS})")
-        self.beam_dirs = torch.as_tensor(dirs, dtype=torch.float32).contiguous().to(self.device)
-        self.max_range = float(cfg.max_range)
-        if not (math.isfinite(self.max_range) and self.max_range > 0):
-            raise ValueError(f"lidar max_range must be positive and finite, got {cfg.max_range}")
-        q = [float(v) for v in cfg.offset_rot]
-        qn = math.sqrt(sum(v * v for v in q))
-        if not (math.isfinite(qn) and qn > 0):
-            raise ValueError(f"lidar offset_rot must be a non-zero quaternion, got {cfg.offset_rot}")
-        self.params = A.WlLidarParams((C.c_float * 3)(*[float(v) for v in cfg.offset_pos]), (C.c_float * 4)(*[v / qn for v in q]),
-                                      self.n_beams, self.max_range, int(bool(cfg.attach_yaw_only)))
-
-    def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
-        """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
-        cam = camera if camera is not None else self.camera_of(batch)
-        if out is None:
-            out = torch.empty(batch.n, self.n_beams, dtype=torch.float32, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape == (batch.n, self.n_beams)
-        A.check(self.lib.wl_lidar_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr,
-                                       self.beam_dirs.data_ptr(), out.data_ptr(), A.stream(self.device)), "wl_lidar_scan")
-        return out
-
-
-def _quat_mul(a, b):
-    aw, ax, ay, az = a
-    bw, bx, by, bz = b
-    return (aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
-            aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw)
-
-
-class RayCaster(_TerrainSensor):
-    """A ray caster (envs.sensors_cfg.RayCasterCfg or RayCasterCameraCfg) casting its table of rays against the terrain from the poses
-    of ANY batch (wl_raycast_scan).  Owns the table, built once from the pattern: `ray_starts` / `ray_dirs` [R, 3] in the sensor
-    frame and, for a pinhole pattern, `ray_scale` [R] (each ray's cosine to the optical axis: distances come out as distances to
-    the image plane).  `vertical` -- every direction exactly (0, 0, -1), alignment yaw or world, mount about z only -- is decided here
-    and selects the kernel's column form (one bilinear sample per ray instead of a walk); `vertical=False` forces the walk.
-    scan() -> (distances [n, R], hits [n, R, 3]): the distance clipped at max_distance (max_distance on a miss, 0 from under the
-    terrain; times ray_scale), the hit point (+inf on a miss)."""
 
     def __init__(self, cfg, device="cuda:0", vertical: bool | None = None):
         import numpy as np
@@ -168,7 +124,7 @@ class RayCaster(_TerrainSensor):
         for t, shape in ((dist, (batch.n, self.n_rays)), (hits, (batch.n, self.n_rays, 3))):
             assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.shape == shape)
         ptr = lambda t: None if t is None else t.data_ptr()
-        A.check(self.lib.wl_raycast_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr, self.ray_starts.data_ptr(),
+        A.check(self.lib.wl_raycast_scan(C.byref(self.params), C.byref(batch._bufs), C.byref(cam._hf), cam._pyr, ptr(self.ray_starts),
                                          None if self.vertical else self.ray_dirs.data_ptr(), ptr(self.ray_scale), ptr(dist), ptr(hits),
                                          A.stream(self.device)), "wl_raycast_scan")
         return dist, hits
@@ -180,6 +136,31 @@ class RayCaster(_TerrainSensor):
     def hits(self, batch, camera: DepthCamera | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
         """hit points [batch.n, R, 3] in the world, +inf on a miss"""
         return self.scan(batch, camera, dist=False, hits=True if out is None else out)[1]
+
+
+class LidarScanner(RayCaster):
+    """A lidar (envs.sensors_cfg.LidarCfg) scanning the terrain from the poses of ANY batch: the RayCaster of its beam pattern -- every
+    beam from the sensor origin (`ray_starts` None: no start table), attach_yaw_only as yaw or base alignment, max_range as
+    max_distance -- always walked: a fan that points straight down on a yaw mount stays a lidar, it does not switch to the column
+    form.  `cfg` is the LidarCfg.
+    render() -> ranges [n, B], the raw scan: the hit's Euclidean range clipped at max_range, max_range on a miss, 0 from under
+    the terrain (what a miss reads in the scene is LidarData's business)."""
+
+    def __init__(self, cfg=None, device="cuda:0"):
+        from .envs.sensors_cfg import LidarCfg, RayCasterCfg
+        lidar = cfg if cfg is not None else LidarCfg()
+        super().__init__(RayCasterCfg(pattern_cfg=lidar.pattern_cfg, offset_pos=lidar.offset_pos, offset_rot=lidar.offset_rot,
+                                      attach_yaw_only=bool(lidar.attach_yaw_only), max_distance=lidar.max_range), device, vertical=False)
+        self.cfg = lidar
+        self.ray_starts = None        # every beam leaves the sensor origin: no start table, the kernel loads none
+
+    n_beams = property(lambda self: self.n_rays)
+    beam_dirs = property(lambda self: self.ray_dirs)
+    max_range = property(lambda self: self.max_distance)
+
+    def render(self, batch, out: torch.Tensor | None = None, camera: DepthCamera | None = None) -> torch.Tensor:
+        """ranges [batch.n, B] of the batch's current poses; `camera`: another terrain (a DepthCamera) than the batch's own"""
+        return super().render(batch, camera, out)
 
 
 def _field_key(heightfield) -> tuple:
