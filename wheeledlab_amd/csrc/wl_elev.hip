@@ -42,546 +42,34 @@ __device__ unsigned long long wl_timeline[2048][16];
 #include "wl_actor_dev.h"
 #include "wl_rng.h"
 #include "wl_implicit_task.h"
+#include "wl_elev_scan_dev.h"   // the height scan: an env's lattice frame, a ray, a quad of rays
+#include "wl_elev_env.h"        // one env's step: terms, reset draws, levels, bookkeeping, elev_env_step
 
 namespace {
-
-enum ElevStream : uint32_t { ES_RESET = 0, ES_CMD_RESET = 1, ES_CMD_RESAMPLE = 2, ES_LEVEL = 3 /* the terrain curriculum's wrap draw */ };
-
-// cos / sin of the yaw of IsaacLab's yaw_quat(q) without the atan2 round trip
-WL_DEV void yaw_cs(Quat q, float& c, float& s) {
-    // every multiply-add spelled out: under -ffp-contract=fast the compiler picks WHICH product of a sum of products it fuses per
-    // inlining site, and two sites of one kernel then round differently (round 4: the first and the later envs of a persistent
-    // scan block disagreed in the last bit)
-    const float a = fmaf(-2.f, fmaf(q.z, q.z, q.y * q.y), 1.f), hb = fmaf(q.w, q.z, q.x * q.y), b = hb + hb;
-    const float inv = rsq(fmaf(a, a, b * b));
-    c = a * inv;
-    s = b * inv;
-}
-
-WL_DEV float sym(float u, float a) { return (2.f * u - 1.f) * a; }
-
-// torch.nan_to_num(x, nan=0) (:55): nan -> 0, and +-inf -> +-FLT_MAX (its default posinf / neginf)
-WL_DEV float nan_to_num(float x) { return x != x ? 0.f : fminf(fmaxf(x, -3.40282347e38f), 3.40282347e38f); }
-
-struct ElevTerms {
-    float t[WL_ER_NTERMS];
-    bool flag[WL_ET_NTERMS];
-};
-
-// elevation mdp terms (citations: mushr_elevation_env_cfg.py)
-WL_DEV ElevTerms elev_terms(const WlElevParams& p, V3 pos, float up_dot, V3 vb, V3 vw, float wheel_sum, float cbx, float cby,
-                            bool timed_out) {
-    ElevTerms r;
-    const float gx = cbx - pos.x, gy = cby - pos.y;   // goal vector: base-frame command minus world position (:50-55 quirk)
-    r.flag[WL_ET_BELOW_MIN_HEIGHT] = pos.z < p.min_height;                                            // :356-359
-    r.flag[WL_ET_STUCK] = fminf(vb.x, p.stuck_vel_cap) < p.stuck_min_vel && wheel_sum > p.stuck_wheel_spin;   // :342-347
-    // :217-222, 339-340: rad2deg(arccos(R33)) > 60 in fp32 is 60.000004 at R33 = 0.5 exactly, so the tie counts as rolled over
-    r.flag[WL_ET_ROLLOVER] = up_dot <= p.upright_cos;
-    const float g2 = fmaf(gx, gx, gy * gy);
-    // :268-273: torch.norm of a 2-vector is the correctly rounded sqrt of fma(y, y, x * x) -- that product order, not v_sqrt_f32
-    r.flag[WL_ET_AT_GOAL] = sqrtf(fmaf(gy, gy, gx * gx)) < p.goal_dist;
-    r.t[WL_ER_GOAL_PROGRESS] = p.progress_offset + fmaf(vw.x, gx, vw.y * gy) * rsq(g2);   // :239-249
-    const float z = pos.z - p.elev_z0;
-    r.t[WL_ER_HIGHER_ELEVATION] = clampf((z > p.elev_min && vb.x > p.elev_min_vel) ? z : 0.f, 0.f, 1.f);       // :166-173
-    r.t[WL_ER_FALLING] = vb.z > p.fall_vel ? 1.f : 0.f;                                               // :251-254
-    r.t[WL_ER_STUCK_PENALTY] = (r.flag[WL_ET_STUCK] && !timed_out) ? 1.f : 0.f;                       // :301-305
-    return r;
-}
-
-// the 13 proprioceptive observation values of ElevationObsCfg.ConcatObs (:61-73), written straight into the env's
-// observation row by the lane-per-env kernels (step / prop); the block-per-env scan kernel adds the 676 map values
-template <int LANES>
-WL_DEV void write_elev_prop(const WlElevParams& p, float* __restrict__ row, V3 pos, Quat q, V3 vb, V3 wb, float cbx, float cby,
-                            float a0, float a1, int wid, bool lead, float* row2 = nullptr /* a second copy (the collector's LDS tile) */) {
-    V3 eu;
-    if constexpr (LANES == 4) {   // roll / pitch / yaw as one lane-parallel atan2 (asin x = atan2(x, sqrt(1 - x^2)))
-        const float sp = 2.f * (q.w * q.y - q.z * q.x);
-        const float ay = wid == 1 ? 2.f * (q.w * q.x + q.y * q.z) : wid == 2 ? sp : 2.f * (q.w * q.z + q.x * q.y);
-        const float ax = wid == 1 ? 1.f - 2.f * (q.x * q.x + q.y * q.y) : wid == 2 ? fsqrt(fmaxf(1.f - sp * sp, 0.f))
-                                                                                  : 1.f - 2.f * (q.y * q.y + q.z * q.z);
-        const float ang = atan2_fast(ay, ax);
-        eu = v3(wrap_2pi(quad_bcast<1>(ang)), wrap_2pi(quad_bcast<2>(ang)), wrap_2pi(quad_bcast<3>(ang)));
-    } else {
-        eu = euler_xyz_from_quat(q);
-    }
-    if (!lead) return;
-    const float gx = cbx - pos.x, gy = cby - pos.y;
-    const float v[13] = {nan_to_num(gx), nan_to_num(gy),
-                         eu.x, eu.y, eu.z,
-                         clampf(vb.x, -p.obs_clip, p.obs_clip), clampf(vb.y, -p.obs_clip, p.obs_clip), clampf(vb.z, -p.obs_clip, p.obs_clip),
-                         clampf(wb.x, -p.obs_clip, p.obs_clip), clampf(wb.y, -p.obs_clip, p.obs_clip), clampf(wb.z, -p.obs_clip, p.obs_clip),
-                         clampf(a0, -1.f, 1.f), clampf(a1, -1.f, 1.f)};
-#pragma unroll
-    for (int i = 0; i < 13; ++i) row[i] = v[i];
-    if (row2) {
-#pragma unroll
-        for (int i = 0; i < 13; ++i) row2[i] = v[i];
-    }
-}
-
-struct ElevReset {
-    V3 pos;
-    Quat q;
-    float vx, vy, tgt_x, tgt_y, tgt_h;
-};
-
-// ---- terrain curriculum (WlTerrainLevels; IsaacLab TerrainImporter.update_env_origins + mdp.terrain_levels) -------------------------
-// a + b as an addition of its own: under -ffp-contract=fast `origin + (2 u - 1) a` becomes an fma at one inlining site and not at
-// the next (see yaw_cs), and every form must place a spawn on the same bits
-WL_DEV float add_unfused(float a, float b) {
-    float r;
-    {
-#pragma clang fp contract(off)
-        r = a + b;
-    }
-    return r;
-}
-struct TileOrigin {
-    float x, y;
-};
-// the centre of tile (level, type[e]); both indices clamped to the table
-WL_DEV TileOrigin tile_origin(const WlTerrainLevels& tl, int e, int level) {
-    const int row = min(max(level, 0), tl.rows - 1), col = min(max(tl.type[e], 0), tl.cols - 1);
-    const float* o = tl.origins + 2 * (row * tl.cols + col);
-    return TileOrigin{o[0], o[1]};
-}
-// the env's level as its lead lane sees it (a quad's other lanes take the lead's value: the lead is the one that writes level[])
-template <int LANES>
-WL_DEV int load_level(const WlTerrainLevels& tl, int e) {
-    int lv = tl.level[e];
-    if constexpr (LANES == 4) lv = __builtin_amdgcn_update_dpp(0, lv, 0, 0xF, 0xF, true);   // quad_perm [0, 0, 0, 0]
-    return lv;
-}
-// the level an env moves to when its episode ends: up at the goal, down (not below 0) after a failure, unchanged after a time-out;
-// past the top row: a uniform row
-WL_DEV int next_level(const WlTerrainLevels& tl, int level, bool at_goal, bool failed, uint32_t gid, uint64_t step, uint64_t seed) {
-    int lv = min(max(level, 0), tl.rows - 1);
-    if (at_goal) lv += 1;
-    else if (failed) lv = max(lv - 1, 0);
-    if (lv >= tl.rows) lv = (int)__umulhi(philox_block(gid, step, ES_LEVEL, seed).x, (uint32_t)tl.rows);
-    return lv;
-}
-
-// stands a drawn car at (x, y) on the terrain
-WL_DEV void stand_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, float x, float y) {
-    float zt;
-    V3 n;
-    g.sample(x, y, zt, n);
-    r.pos = v3(x, y, fmaxf(p.reset_z, zt + p.spawn_clearance));
-}
-// isaaclab reset_root_state_uniform with the ranges of :409-419 + UniformPose2dCommand resample (:425-435).  STAND: the car is stood
-// on the terrain where it is drawn; otherwise pos.x / pos.y (and tgt_x / tgt_y) stay OFFSETS from a tile's centre for place_elev_reset
-// (`g` is read only when STAND: the origin-free wrapper passes nullptr)
-template <bool STAND>
-WL_DEV ElevReset draw_elev_reset_at(const WlElevParams& p, const HeightFieldGround* g, uint32_t gid, uint64_t step, uint64_t seed) {
-    const F4 u = philox_uniform4(gid, step, ES_RESET, seed);
-    const F4 c = philox_uniform4(gid, step, ES_CMD_RESET, seed);
-    ElevReset r;
-    const float x = sym(u.x, p.reset_xy), y = sym(u.y, p.reset_xy);
-    if constexpr (STAND) stand_elev_reset(p, *g, r, x, y);
-    else r.pos = v3(x, y, 0.f);
-    float s, cc;
-    sincos_fast(0.5f * sym(u.z, p.reset_yaw), s, cc);
-    r.q = Quat{cc, 0.f, 0.f, s};
-    r.vx = fmaf(u.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
-    r.vy = fmaf(c.w, p.reset_vel[1] - p.reset_vel[0], p.reset_vel[0]);
-    r.tgt_x = sym(c.x, p.cmd_xy);
-    r.tgt_y = sym(c.y, p.cmd_xy);
-    r.tgt_h = sym(c.z, p.cmd_heading);
-    return r;
-}
-// the part of a reset's draw that does not depend on where the env's tile is; place_elev_reset adds the centre and stands the car
-WL_DEV ElevReset draw_elev_reset_local(const WlElevParams& p, uint32_t gid, uint64_t step, uint64_t seed) {
-    return draw_elev_reset_at<false>(p, nullptr, gid, step, seed);
-}
-WL_DEV ElevReset draw_elev_reset(const WlElevParams& p, const HeightFieldGround& g, uint32_t gid, uint64_t step, uint64_t seed) {
-    return draw_elev_reset_at<true>(p, &g, gid, step, seed);
-}
-WL_DEV void place_elev_reset(const WlElevParams& p, const HeightFieldGround& g, ElevReset& r, TileOrigin o) {
-    stand_elev_reset(p, g, r, add_unfused(o.x, r.pos.x), add_unfused(o.y, r.pos.y));
-    r.tgt_x = add_unfused(o.x, r.tgt_x);
-    r.tgt_y = add_unfused(o.y, r.tgt_y);
-}
-
-// what the height scan needs of an env after its step: root position and the cos / sin of its yaw
-struct ScanPose {
-    float px, py, pz, c, s;
-};
-
-// ---- world_height_map (:44-48): the 26 x 26 yaw-aligned height scan -- what every form below evaluates per ray ------------------
-// The rays of one env form a lattice; in GRID units (cells of the heightfield) ray (ix, iy) stands at
-// (u0 + ix ux + iy uy, v0 + ix vx + iy vy).  Round 4: the lattice frame is set up once per env (7 floats, what the fused kernels
-// keep in LDS) and a ray costs ~35 VALU instructions instead of ~62 (the ray's metres -> rotate -> translate -> grid units chain,
-// four float compares for the inside test and 64-bit address arithmetic went; the scan was as much instruction- as gather-bound:
-// 676 rays x 62 / 64 lanes = 655 wavefront-instructions per env against ~1100 clocks per env and CU).  Same definition
-// (oracle/elev_step.py::height_map, heightfield.py::sample with guard=False); fp32 rounding of the ray position differs by a few ulp
-// of the grid coordinate from the metre chain (tests/heightfield_reference.py derives the bound).  The scan has NO far-border guard:
-// the contact samplers clamp u, v to n - 1 - 1e-3 (wl_heightfield.h), the scan samples the ray's own cell -- on a border that slopes
-// the two differ by up to 1e-3 cell x the slope (1e-4 m at 0.1 m cells and a slope of 1), beyond the scan's 2e-5 m, so the scan's
-// definition is the guard-free one (tests/test_gpu_heightfield_geometry.py holds every scan form to it).
-struct ScanFrame {
-    float u0, v0, ux, vx, uy, vy, pz;
-};
-WL_DEV ScanFrame scan_frame(const WlElevParams& p, const HeightFieldGround& g, const ScanPose& sp) {
-    const float g0 = -0.5f * p.scan_size, k = p.scan_res * g.inv_cell;
-    ScanFrame f;
-    // (multiply-adds spelled out: see yaw_cs)
-    f.u0 = ((sp.px + fmaf(sp.c, g0, -(sp.s * g0))) - g.f.x0) * g.inv_cell;
-    f.v0 = ((sp.py + fmaf(sp.s, g0, sp.c * g0)) - g.f.y0) * g.inv_cell;
-    f.ux = sp.c * k, f.vx = sp.s * k;
-    f.uy = -sp.s * k, f.vy = sp.c * k;
-    f.pz = sp.pz;
-    return f;
-}
-// ray index r (< 1024) of the scan -> lattice coordinates, meshgrid "xy": x fastest (r / 26 by multiply-shift: exact, checked)
-WL_DEV void scan_ray_xy(int r, float& fix, float& fiy) {
-    const int iy = (int)(__umul24((unsigned)r, 1261u) >> 15);
-    fix = (float)(r - iy * WL_ELEV_SCAN_N);
-    fiy = (float)iy;
-}
-// the cell a ray falls into: float offset of its lower-left grid point, position inside the cell, inside-the-field flag
-struct ScanCell {
-    int i, j;      // NOT clamped: outside the field when !inside
-    float fu, fv;
-    bool inside;
-};
-WL_DEV ScanCell scan_cell(const ScanFrame& f, const WlHeightField& hf, float fix, float fiy) {
-    const float u = fmaf(fix, f.ux, fmaf(fiy, f.uy, f.u0)), v = fmaf(fix, f.vx, fmaf(fiy, f.vy, f.v0));
-    const float fl_u = floorf(u), fl_v = floorf(v);
-    const int i = (int)fl_u, j = (int)fl_v;      // saturating conversion: far-away rays stay far away
-    ScanCell c;
-    c.fu = u - fl_u;
-    c.fv = v - fl_v;
-    // 0 <= u < nx - 1 as ONE unsigned compare per axis; a NaN pose (converted to cell 0) is caught through its NaN fraction
-    c.inside = (unsigned)i < (unsigned)(hf.nx - 1) && (unsigned)j < (unsigned)(hf.ny - 1) && (c.fu + c.fv >= 0.f);
-    c.i = i, c.j = j;
-    return c;
-}
-// a ray in flight: the gather of its cell's four corner codes, decoded and consumed by scan_value.
-// Round 6: ONE 8-byte gather from the row-pair table (WlHeightField.pair): lo = (c00 | c01 << 16), hi = (c10 | c11 << 16).  The
-// gathers were bound by the texture unit's address rate -- rocprofv3 on the fused launch at 4096 envs: TA busy 16 000 cycles per CU
-// = the whole scan phase, 57 cache accesses per 64-lane gather instruction, L1 hit rate 0.91 -- and a ray cost two of them (rows j
-// and j + 1 of the code field); with the pair table it costs one (measured: fused step 20.5 -> 17.5 us, gather-form scan at 262 144
-// envs 484 -> 319 us).
-struct ScanRay {
-    uint32_t lo, hi;
-    float fu, fv;
-    bool inside;
-};
-struct ScanField {   // the row-pair table through a buffer resource: one 32-bit lane offset per gather
-    __amdgpu_buffer_rsrc_t rsrc;
-    float z_scale;
-};
-WL_DEV ScanField scan_field(const WlHeightField& hf) {
-    return ScanField{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(hf.pair), 0, hf.nx * hf.ny * 4, 0x00020000), hf.z_scale};
-}
-WL_DEV ScanRay scan_request(const ScanFrame& f, const WlHeightField& hf, const ScanField& sf, float fix, float fiy) {
-    typedef unsigned wl_u2 __attribute__((ext_vector_type(2)));
-    const ScanCell c = scan_cell(f, hf, fix, fiy);
-    ScanRay r;
-    r.fu = c.fu, r.fv = c.fv, r.inside = c.inside;
-    // a ray outside the field asks for whatever address its cell index wraps to: inside the buffer it reads a value nobody uses
-    // (the ray is a miss), outside it the resource's bounds check returns 0 -- four clamps per ray saved.  24-bit multiply (full
-    // rate; v_mul_lo_u32 is a quarter-rate instruction): exact for every ray inside the field (heightfield_args_ok: nx, ny < 2^23)
-    const wl_u2 w = __builtin_amdgcn_raw_buffer_load_b64(sf.rsrc, (__mul24(c.j, hf.nx) + c.i) * 4, 0, 0);
-    r.lo = w.x, r.hi = w.y;
-    return r;
-}
-// FOUR consecutive rays per lane, stored as ONE 16-byte word (round 4).  The scan's 676 four-byte stores per env were what bound
-// it, whatever the read side did (gathers or an LDS patch, DESIGN.md section 7: 500 us per launch at 262 144 envs either way): a store
-// instruction costs the memory pipeline per INSTRUCTION far more than per byte (MI355X_MICROARCH.md: narrow stores are issue-bound,
-// a dword store ~6 x a dwordx4 store per byte).  Rays 4 q .. 4 q + 3 of an env (q < 169) are neighbours along x; the scan row has 26
-// = 6.5 quads, so a quad starting at ix = 24 continues at (0, iy + 1): ray pairs (0, 1) and (2, 3) never straddle a row.
-typedef float wl_float4_u __attribute__((ext_vector_type(4), aligned(4)));   // observation rows are only 4-byte aligned
-constexpr int kScanQuads = WL_ELEV_SCAN_N * WL_ELEV_SCAN_N / 4;             // 169
-static_assert(WL_ELEV_SCAN_N % 2 == 0 && (WL_ELEV_SCAN_N * WL_ELEV_SCAN_N) % 4 == 0, "ray pairs stay inside a scan row, whole quads per env");
-// quad slot (env-in-block x 169 + quad, < 2^13) -> env j, quad q (idx / 169 by multiply-shift: exact, checked)
-WL_DEV void scan_quad_slot(int idx, int& j, int& q) {
-    j = (int)(__umul24((unsigned)idx, 6205u) >> 20);
-    q = idx - j * kScanQuads;
-}
-// bilinear height under the ray -> the observation value: -(sensor_z - hit_z - offset) + (root_z - plane_init_value), +inf on a
-// miss, clipped to +- obs_clip
-WL_DEV float scan_value(const WlElevParams& p, const ScanRay& r, float z_scale, float pz) {
-    // the blend runs on the CODES and is scaled once (3 instructions per ray fewer than decoding the four corners first; the large-batch
-    // scan is VALU-bound since round 5).  Exactly the decode-first value when z_scale is a power of two (terrain.py's default: scaling
-    // by 2^k commutes with every rounding); for other scales it differs from it in the last bit -- every scan form shares this function
-    const float c00 = (float)(int)(int16_t)(r.lo & 0xffffu), c01 = (float)((int)r.lo >> 16);
-    const float c10 = (float)(int)(int16_t)(r.hi & 0xffffu), c11 = (float)((int)r.hi >> 16);
-    const float a = fmaf(r.fu, c10 - c00, c00), b = fmaf(r.fu, c11 - c01, c01);
-    float hz;
-    {
-#pragma clang fp contract(off)
-        hz = fmaf(r.fv, b - a, a) * z_scale;      // a multiply of its own: not fused into the subtraction below per inlining site
-    }
-    const float val = r.inside ? (-(pz - hz - p.scan_offset) + (pz - p.elev_z0)) : __builtin_inff();
-    return clampf(val, -p.obs_clip, p.obs_clip);
-}
-// the gathers of the four rays of quad q (4 x 8 B in flight per lane) ...
-WL_DEV void scan_quad_request(const ScanFrame& f, const WlHeightField& hf, const ScanField& sf, int q, ScanRay (&r)[4]) {
-    float fx0, fy0, fx2, fy2;
-    scan_ray_xy(4 * q, fx0, fy0);
-    scan_ray_xy(4 * q + 2, fx2, fy2);
-    r[0] = scan_request(f, hf, sf, fx0, fy0);
-    r[1] = scan_request(f, hf, sf, fx0 + 1.f, fy0);
-    r[2] = scan_request(f, hf, sf, fx2, fy2);
-    r[3] = scan_request(f, hf, sf, fx2 + 1.f, fy2);
-}
-// ... and their four values as one 16-byte word
-WL_DEV wl_float4_u scan_quad_value(const WlElevParams& p, const ScanRay (&r)[4], float z_scale, float pz) {
-    wl_float4_u v;
-    v.x = scan_value(p, r[0], z_scale, pz), v.y = scan_value(p, r[1], z_scale, pz), v.z = scan_value(p, r[2], z_scale, pz);
-    v.w = scan_value(p, r[3], z_scale, pz);
-    return v;
-}
-#ifndef WL_FUSED_SCAN_NT
-#define WL_FUSED_SCAN_NT true     // the fused step + scan launches' map rows as non-temporal stores (round 4, 4096 envs: 25.6 -> 24.7 us per step)
-#endif
-template <bool STREAM>
-WL_DEV void scan_quad_store(float* __restrict__ row_map /* obs row + 13 */, int q, wl_float4_u v) {
-    wl_float4_u* dst = reinterpret_cast<wl_float4_u*>(row_map + 4 * q);
-
-    if constexpr (STREAM) __builtin_nontemporal_store(v, dst);
-    else *dst = v;
-}
-
-// the bookkeeping rows of an env (episode length, goal command, episode sums) + the last action: with VehRows everything a
-// persistent rollout carries in registers from step to step
-struct ElevBook {
-    int ep_len;
-    float cb[2], epsum[WL_ER_NTERMS], tgt[4];   // tgt: target x, y, heading, resample timer
-    float act[2];
-};
-template <int LANES>
-WL_DEV void store_elev_state(const WlElevParams& p, const WlEnvBuffers& b, const Rows& S, int e, int wid, bool lead,
-                             const VehRows<LANES>& r, const ElevBook& k) {
-    store_veh_rows<LANES>(S, e, wid, lead, r, k.act[0], k.act[1], p.log_episode_sums != 0, k.epsum);
-    if (lead) {
-        S.st(WL_S_CMD_BX, e, k.cb[0]);
-        S.st(WL_S_CMD_BY, e, k.cb[1]);
-        S.st(WL_S_TGT_X, e, k.tgt[0]);
-        S.st(WL_S_TGT_Y, e, k.tgt[1]);
-        S.st(WL_S_TGT_H, e, k.tgt[2]);
-        S.st(WL_S_CMD_TIMER, e, k.tgt[3]);
-        b.episode_len[e] = k.ep_len;
-    }
-}
-template <int LANES>
-WL_DEV ElevBook load_elev_book(const WlElevParams& p, const WlEnvBuffers& b, const Rows& S, int e) {
-    ElevBook k;
-    k.ep_len = b.episode_len[e];
-    k.cb[0] = S.ld(WL_S_CMD_BX, e);
-    k.cb[1] = S.ld(WL_S_CMD_BY, e);
-#pragma unroll
-    for (int i = 0; i < WL_ER_NTERMS; ++i) k.epsum[i] = p.log_episode_sums ? S.ld(WL_S_EPSUM0 + i, e) : 0.f;
-    k.tgt[0] = S.ld(WL_S_TGT_X, e);
-    k.tgt[1] = S.ld(WL_S_TGT_Y, e);
-    k.tgt[2] = S.ld(WL_S_TGT_H, e);
-    k.tgt[3] = S.ld(WL_S_CMD_TIMER, e);
-    k.act[0] = k.act[1] = 0.f;
-    return k;
-}
-
-// one env.step() of env `e` (all LANES lanes of the env take part): the body of the step kernels below.
-// PERSIST: the env's rows and bookkeeping live in `rows` / `*carry` across calls (persistent rollout): nothing is loaded
-// from or stored to the state matrix here, both are updated in place.
-// How the fused launch takes the step apart (round 6): `pose(pos, q)` is called with the env's pose as the step leaves it (AFTER a
-// reset, if the env resets) as soon as that pose is known -- before the rewards are weighted, the outputs, the metrics and the state
-// rows are written -- so that the launch can hand the height scan its lattice frames and let the other wavefronts start while this one
-// finishes its bookkeeping.  `reset_src` supplies a resetting env's draw (wl_implicit_task.h): drawn here by default, by the fused
-// launch's helper wavefront there.
-static_assert(sizeof(WlElevParams) % alignof(VehDerived) == 0, "VehDerived follows WlElevParams in the argument block without a gap");
-// What the step kernels take as their first argument: WlElevParams WITHOUT its trailing `levels` member, so that a launch without
-// terrain levels has the argument block -- and, with LEVELS = false, the code -- it had before the member existed.  The member
-// travels as the kernels' LAST argument and is read (scalar loads) only by the LEVELS = true instantiations, at resets.
-constexpr int kElevHeadBytes = (int)offsetof(WlElevParams, log_episode_sums) + 4;
-struct ElevHead {
-    uint32_t w[kElevHeadBytes / 4];
-};
-static_assert(offsetof(WlElevParams, levels) >= (size_t)kElevHeadBytes && alignof(ElevHead) == 4, "levels is the trailing member");
-inline ElevHead elev_head(const WlElevParams* p) {
-    ElevHead h;
-    __builtin_memcpy(&h, p, sizeof(h));
-    return h;
-}
-// the argument read as the parameter struct: every field but `levels` is there
-WL_DEV const WlElevParams& elev_args(const ElevHead& h) { return reinterpret_cast<const WlElevParams&>(h); }
-// the vector copy of the head and of the derived block behind it (kernarg_vector_copy2), as a parameter struct in registers
-WL_DEV void elev_kernarg_copy(WlElevParams& p, VehDerived& vd) {
-    ElevHead h;
-    kernarg_vector_copy2(0, h, vd);
-    __builtin_memcpy(&p, &h, sizeof(h));
-}
-struct NoPose {
-    WL_DEV void operator()(const V3&, const Quat&) const {}
-};
-template <int LANES, bool LEVELS, bool PERSIST = false, class RESET = InlineReset, class POSE = NoPose>
-WL_DEV ScanPose elev_env_step(const WlElevParams& p, const VehDerived& vd, const WlEnvBuffers& b, const HeightFieldGround& ground,
-                              const float2 action, VehRows<LANES>& rows, const WlStepOut& out, const uint64_t seed,
-                              const uint64_t step, const Rows& S, const int e, const int wid, const bool lead, float* blk_metrics,
-                              const WlTerrainLevels& tl /* the kernel's scalar argument: read at resets only, when LEVELS */,
-                              ElevBook* carry = nullptr, float* prop2 = nullptr, const RESET& reset_src = RESET(), const POSE& pose = POSE()) {
-    const WlVehicleParams& vp = p.vehicle;
-    const uint32_t gid = (uint32_t)(b.env_offset + e);
-    float2 a = action;
-    const EnvConst ec = veh_env_const<LANES>(p.action, vp, vd, a, rows, wid);
-    VehState s = veh_state<LANES>(vp, rows);
-    // Bookkeeping rows (episode length, goal command, episode sums): the lane form fetches them after the physics loop --
-    // it runs several wavefronts per SIMD and the registers are worth more than the latency; the quad form is one wavefront
-    // per SIMD with registers to spare, so it requests them BEFORE the loop and finds them landed behind it.
-    int ep_len_in = 0;
-    float cb_in[2] = {0.f, 0.f}, epsum_in[WL_ER_NTERMS], tgt_in[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < WL_ER_NTERMS; ++i) epsum_in[i] = 0.f;
-    auto fetch_bookkeeping = [&]() {
-        if constexpr (PERSIST) {
-            ep_len_in = carry->ep_len;
-            cb_in[0] = carry->cb[0], cb_in[1] = carry->cb[1];
-#pragma unroll
-            for (int i = 0; i < WL_ER_NTERMS; ++i) epsum_in[i] = carry->epsum[i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) tgt_in[i] = carry->tgt[i];
-            return;
-        }
-        ep_len_in = b.episode_len[e];
-        cb_in[0] = S.ld(WL_S_CMD_BX, e);
-        cb_in[1] = S.ld(WL_S_CMD_BY, e);
-        if (p.log_episode_sums) {
-#pragma unroll
-            for (int i = 0; i < WL_ER_NTERMS; ++i) epsum_in[i] = S.ld(WL_S_EPSUM0 + i, e);
-        }
-        tgt_in[0] = S.ld(WL_S_TGT_X, e);
-        tgt_in[1] = S.ld(WL_S_TGT_Y, e);
-        tgt_in[2] = S.ld(WL_S_TGT_H, e);
-        tgt_in[3] = S.ld(WL_S_CMD_TIMER, e);
-    };
-    if constexpr (LANES == 4) {
-        fetch_bookkeeping();
-        WL_TL(1);
-    }
-    veh_integrate<LANES>(vp, vd, ec, s, ground, wid);
-    if constexpr (LANES == 4) WL_TL(2);
-    if constexpr (LANES != 4) {
-        asm volatile("" ::: "memory");
-        fetch_bookkeeping();
-    }
-    VehPost v = veh_post<LANES>(vp, s);
-    int ep_len = ep_len_in + 1;
-    const bool truncated = ep_len >= p.max_episode_length;
-    // terminations / rewards use the command as the PREVIOUS step's command update left it (IsaacLab step order)
-    float cbx = cb_in[0], cby = cb_in[1];
-    const ElevTerms tm = elev_terms(p, v.pos, v.R.r2.z, v.vb, s.v, v.wheel_sum, cbx, cby, truncated);
-    const bool terminated = !v.finite || tm.flag[0] || tm.flag[1] || tm.flag[2] || tm.flag[3];
-    // the pose the step leaves behind first (a reset replaces it): whoever waits for it is served before the bookkeeping.  `pose` is
-    // called exactly once on every path -- unconditionally, with nothing above it that returns -- because the fused launch's holds the
-    // block's one s_barrier: keep it that way.
-    const bool reset_now = terminated || truncated;
-    ElevReset rd{};
-    [[maybe_unused]] int level_now = 0;      // LEVELS and reset_now: the level the env leaves this step on
-    if (reset_now) {
-        if constexpr (LEVELS) {
-            // the curriculum first (IsaacLab _reset_idx: curriculum terms before the reset events), then the spawn on the new tile.
-            // The origin-free draw may come from the helper wavefront; the level needs this step's outcome, so it is decided here.
-            level_now = next_level(tl, load_level<LANES>(tl, e), tm.flag[WL_ET_AT_GOAL], terminated, gid, step, seed);
-            if (lead) tl.level[e] = level_now;
-            rd = reset_src(e, [&] { return draw_elev_reset_local(p, gid, step, seed); });
-            place_elev_reset(p, ground, rd, tile_origin(tl, e, level_now));
-        } else {
-            rd = reset_src(e, [&] { return draw_elev_reset(p, ground, gid, step, seed); });
-        }
-        v.pos = rd.pos;
-    }
-    pose(v.pos, reset_now ? rd.q : s.q);
-    const float step_dt = p.sim_dt * (float)p.decimation;
-    float epsum[WL_ER_NTERMS];
-    const float reward = weigh_rewards(p.weight, tm.t, v.finite, step_dt, p.log_episode_sums != 0, epsum_in, epsum);
-    if (lead) write_step_flags(out, e, reward, terminated, truncated);
-    float a0 = a.x, a1 = a.y;
-    float tgt_x = tgt_in[0], tgt_y = tgt_in[1], tgt_h = tgt_in[2], cmd_timer = tgt_in[3];
-    if (reset_now) {
-        if (lead) episode_end_metrics(blk_metrics, epsum, truncated, v.finite, tm.flag, ep_len);
-        veh_reset(s, v, epsum, rd.pos, rd.q, v3(rd.vx, rd.vy, 0.f));
-        tgt_x = rd.tgt_x;
-        tgt_y = rd.tgt_y;
-        tgt_h = rd.tgt_h;
-        cmd_timer = p.cmd_resample_s;
-        ep_len = 0;
-        a0 = a1 = 0.f;
-    }
-    // command manager: count down, resample expired targets, re-express the target in the yaw-aligned base frame
-    cmd_timer -= step_dt;
-    if (cmd_timer <= 0.f) {
-        const F4 u = philox_uniform4(gid, step, ES_CMD_RESAMPLE, seed);
-        tgt_x = sym(u.x, p.cmd_xy);
-        tgt_y = sym(u.y, p.cmd_xy);
-        if constexpr (LEVELS) {      // the goal square sits on the env's tile
-            const TileOrigin o = tile_origin(tl, e, reset_now ? level_now : load_level<LANES>(tl, e));
-            tgt_x = add_unfused(o.x, tgt_x);
-            tgt_y = add_unfused(o.y, tgt_y);
-        }
-        tgt_h = sym(u.z, p.cmd_heading);
-        cmd_timer = p.cmd_resample_s;
-    }
-    {
-        float c, sn;
-        yaw_cs(s.q, c, sn);
-        const float dx = tgt_x - v.pos.x, dy = tgt_y - v.pos.y;
-        cbx = fmaf(c, dx, sn * dy);
-        cby = fmaf(-sn, dx, c * dy);
-    }
-    {   // the env's new rows: kept (persistent rollout) or written back
-        veh_rows_from(rows, s, v);
-        ElevBook k;
-        k.ep_len = ep_len;
-        k.cb[0] = cbx, k.cb[1] = cby;
-#pragma unroll
-        for (int i = 0; i < WL_ER_NTERMS; ++i) k.epsum[i] = epsum[i];
-        k.tgt[0] = tgt_x, k.tgt[1] = tgt_y, k.tgt[2] = tgt_h, k.tgt[3] = cmd_timer;
-        k.act[0] = a0, k.act[1] = a1;
-        if constexpr (PERSIST) *carry = k;
-        else store_elev_state<LANES>(p, b, S, e, wid, lead, rows, k);
-    }
-    // proprioceptive part of the observation, from the post-reset state (all lanes of a quad take part)
-    const Mat3 R2 = mat_from_quat(s.q);
-    write_elev_prop<LANES>(p, out.obs + (int64_t)e * WL_ELEV_OBS_DIM, v.pos, s.q, mul_t(R2, s.v), mul_t(R2, v.ww), cbx, cby, a0, a1,
-                           wid, lead, prop2);
-    float yc, ys;
-    yaw_cs(s.q, yc, ys);
-    return ScanPose{v.pos.x, v.pos.y, v.pos.z, yc, ys};
-}
 
 // (lane form: 110 VGPRs = 4 wavefronts per SIMD.  Squeezed to 96 / 80 registers for 5 / 6 wavefronts the kernel spills 60 / 128 bytes
 // of scratch per lane and the step at 262 144 envs goes from 650 to 664 / 782 us: round 3.)
 #ifndef WL_ELEV_LANE_WAVES
 #define WL_ELEV_LANE_WAVES 1
 #endif
-template <int LANES, bool LEVELS>
-__global__ void __launch_bounds__(kBlock, LANES == 1 ? WL_ELEV_LANE_WAVES : 1) elev_step_kernel(const ElevHead h_arg, const VehDerived vd_arg, const WlEnvBuffers b,
+// lane = env (the quad form of the step is elev_step_scan_kernel's wavefront 0)
+template <bool LEVELS>
+__global__ void __launch_bounds__(kBlock, WL_ELEV_LANE_WAVES) elev_step_kernel(const ElevHead h_arg, const VehDerived vd_arg, const WlEnvBuffers b,
                                                            const HeightFieldGround ground, const float2* __restrict__ actions,
                                                            const WlStepOut out, const uint64_t seed, const uint64_t step,
                                                            const WlTerrainLevels tl_arg) {
     __shared__ float blk_metrics[WL_M_COUNT];
-    const WlElevParams& p_arg = elev_args(h_arg);
-    WlElevParams p_quad;
-    VehDerived vd = vd_arg;
-    if constexpr (LANES == 4) {   // latency form: one batch of vector loads instead of dependent scalar-load round trips
-        elev_kernarg_copy(p_quad, vd);
-        keep_scalar_common(p_quad, p_arg);
-        vd.n_sub = vd_arg.n_sub;
-    }
-    const WlElevParams& p = LANES == 4 ? p_quad : p_arg;
-    constexpr int kEnvs = kBlock / LANES;
-    const int wid = LANES == 1 ? 0 : (threadIdx.x & 3);
-    const bool lead = LANES == 1 || wid == 0;
-    const int e = blockIdx.x * kEnvs + threadIdx.x / LANES;
+    const WlElevParams& p = elev_args(h_arg);
+    VehDerived vd = vd_arg;   // (a copy, not the argument itself: read in place, one of its scalar loads is issued elsewhere)
+    const int e = blockIdx.x * kBlock + threadIdx.x;
     if (threadIdx.x < WL_M_COUNT) blk_metrics[threadIdx.x] = 0.f;
     const int m_slot = b.metrics_slots > 1 ? (int)(step % (uint64_t)b.metrics_slots) : 0;
     if (b.metrics_slots > 1) clear_metric_slot(b, (m_slot + 1) % b.metrics_slots);
     __syncthreads();
     const Rows S = make_rows(b.state, b.stride);
     if (e < b.n_envs) {
-        VehRows<LANES> rows = load_veh_rows<LANES>(S, e, wid);
-        (void)elev_env_step<LANES, LEVELS>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, wid, lead, blk_metrics, tl_arg);
+        VehRows<1> rows = load_veh_rows<1>(S, e, 0);
+        (void)elev_env_step<1, LEVELS>(p, vd, b, ground, actions[e], rows, out, seed, step, S, e, 0, true, blk_metrics, tl_arg);
     }
     __syncthreads();
     block_metrics_flush(blk_metrics, b, m_slot);   // threads 0..15 = wavefront 0 of the block
@@ -624,7 +112,7 @@ inline void launch_elev_scan(const WlElevParams* p, const WlEnvBuffers* b, const
 }
 
 // env.step() AND the height scan as ONE launch (quad form, n <= 32 768): block = 16 envs, 8 wavefronts.  Wavefront 0
-// steps them (16 quads, as in elev_step_kernel<4>) while wavefront 1 draws their reset poses (ResetHelper), and leaves each
+// steps them (16 quads of lanes: elev_env_step<4>) while wavefront 1 draws their reset poses (ResetHelper), and leaves each
 // env's post-step lattice frame in LDS; then all eight wavefronts cast the 16 x 169 quads of rays (flat index over (env, quad),
 // one quad per lane and batch: the scan phase below).  Against the two-launch form this removes the scan kernel's own start
 // (launch gap, wave ramp, the pose rows' first-touch latency) from the step's dependent chain, and one physics wavefront per CU
@@ -1245,7 +733,7 @@ int wl_elev_rollout(const WlElevParams* p, const WlEnvBuffers* b, const WlHeight
             });
         } else {
             launch_levels(p, [&](auto lv) {
-                elev_step_kernel<1, decltype(lv)::value><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
+                elev_step_kernel<decltype(lv)::value><<<lane_grid, kBlock, 0, (hipStream_t)stream>>>(h, vd, *b, g, a, o, seed, step0 + (uint64_t)k, p->levels);
             });
             launch_elev_scan(p, b, g, o.obs, (hipStream_t)stream);
         }
