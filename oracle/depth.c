@@ -132,7 +132,7 @@ static double cast_ray(const Field* f, double ox, double oy, double oz, double d
 }
 
 /* pos [n][3], quat [n][4] (w, x, y, z) of the ROOT; camera at cam_pos in the body frame, optical axis body +x, image right
- * = body -y, image down = body -z (the kernel's pixel_ray_body); depth [n][img_h][img_w].  Returns 0. */
+ * = body -y, image down = body -z (the kernel's depth_pixel_ray_body); depth [n][img_h][img_w].  Returns 0. */
 int wl_oracle_depth(int n, const float* pos, const float* quat, const float* cam_pos, float fx, float fy, float cx, float cy,
                     int img_h, int img_w, const float* height, int nx, int ny, float x0, float y0, float cell, float outside_z,
                     float max_depth, float* depth) {

@@ -97,7 +97,7 @@ def reset_envs(p, state, episode_len, hf, ids, seed, step, env_offset=0):
 
 def height_map(p, state, hf):
     """E1: 26 x 26 yaw-aligned grid of terrain heights relative to the base plane, clipped (x fastest).  Sampled WITHOUT the contact
-    samplers' far-border guard, as wl_elev.hip::scan_cell does; a ray off the grid misses (+inf, clipped), whatever outside_z is"""
+    samplers' far-border guard, as wl_elev_scan_dev.h::scan_cell does; a ray off the grid misses (+inf, clipped), whatever outside_z is"""
     n = state.shape[1]
     k = np.arange(N_RAYS, dtype=np.float32)
     g = (F(-0.5 * p.scan_size) + k * F(p.scan_res)).astype(F)

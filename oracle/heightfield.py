@@ -58,7 +58,7 @@ def sample(hf, x0, y0, cell, x, y, outside=0.0, guard=True):
     -> z [N], n [N,3], inside [N] bool.  The wheel-contact samplers' definition (wl_heightfield.h): u, v clamped to
     [0, n - 1 - 1e-3] in fp32 (the far-border guard) and the integer cell clamped to n - 2, so that the guard's vanishing on
     fields 32 770 or more points wide (n - 1 - 1e-3 rounds to n - 1 there) still reads inside the grid; `guard=False` is the
-    height scan's (wl_elev.hip::scan_cell): no clamp of u, v -- the cell clamp alone keeps the read on the grid"""
+    height scan's (wl_elev_scan_dev.h::scan_cell): no clamp of u, v -- the cell clamp alone keeps the read on the grid"""
     hf = f32(hf)
     ny, nx = hf.shape
     inv = F(1) / F(cell)

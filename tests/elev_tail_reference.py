@@ -1,6 +1,6 @@
 """The post-physics tail of the elevation step restated in float64 (test infrastructure: never imported by the product).
 
-`elev_env_step` (wheeledlab_amd/csrc/wl_elev.hip) from `veh_post` on, in its own order: the four terminations and the non-finite
+`elev_env_step` (wheeledlab_amd/csrc/wl_elev_env.h) from `veh_post` on, in its own order: the four terminations and the non-finite
 rule, the four reward terms (both read the command the PREVIOUS step left), reward and episode sums, the episode metrics, the
 curriculum's level (decided before the spawn), the reset draw, the command count-down / resample (after the reset: a resetting
 env's resample lands on its new tile), the command re-expressed from the post-reset position and yaw, and the 13 proprioceptive
@@ -18,7 +18,7 @@ Bound.  An element passes when |got - ref| <= n U m + E (tests/drift_tail_refere
 on the element's longest path, m = the first-order magnitude propagated item by item, E = the intrinsics' documented error;
 -ffp-contract=fast: where the source does not spell the fma the UNFUSED path is counted).  Nothing was tuned against GPU output.
 
-Roundings per element (wl_math.h: mat_from_quat, mul_t, atan2_fast; wl_elev.hip: elev_terms, yaw_cs, write_elev_prop;
+Roundings per element (wl_math.h: mat_from_quat, mul_t, atan2_fast; wl_elev_env.h: elev_terms, yaw_cs, write_elev_prop;
 wl_implicit_task.h: veh_post, weigh_rewards):
   element                      n    path
   R entry                      3    diagonal: q.y y2 | 1 - . | fma (off-diagonal: product | fma = 2; the diagonal's count is used)
@@ -77,7 +77,7 @@ FLT_MAX = float(np.finfo(F).max)
 M_SHARDS = 32
 N_TERMS, N_FLAGS = 4, 4
 OBS_DIM = 13 + 26 * 26
-ES_RESET, ES_CMD_RESET, ES_CMD_RESAMPLE = 0, 1, 2          # wl_elev.hip ElevStream (ES_LEVEL = 3: terrain_levels_reference)
+ES_RESET, ES_CMD_RESET, ES_CMD_RESAMPLE = 0, 1, 2          # wl_elev_env.h ElevStream (ES_LEVEL = 3: terrain_levels_reference)
 N_BODY, N_WHEEL, N_R33, N_EULER = 6, 3, 3, 7
 N_CONTRIB, N_REWARD_ADDS, N_EPSUM_ADD = 2, 4, 1
 ORACLE_EXTRA = 4

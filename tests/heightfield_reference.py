@@ -6,7 +6,7 @@ comparison is the kernel's.  Two definitions, written down here because they dif
       u, v are clamped to [0, n - 1 - 1e-3] where the bound is the fp32 value (float)(n - 1) - 1e-3f the device computes, and the
       cell index to n - 2.  On a field 32 770 or more points wide the bound rounds to n - 1 itself: the guard is gone, and only the
       cell clamp (which changes nothing inside the field) keeps the read on the grid.
-  height scan (wl_elev.hip::scan_cell / scan_value, every scan form) -- `guard=False`: no clamp; the ray's own cell and fraction.
+  height scan (wl_elev_scan_dev.h::scan_cell / scan_value, every scan form) -- `guard=False`: no clamp; the ray's own cell and fraction.
 
 Both are `inside` for u in [0, nx - 1) and v in [0, ny - 1); outside, the contact samplers return outside_z and a +z normal, the scan
 a miss (+inf, clipped to obs_clip).  The two agree except within 1e-3 cell of the far border lines, where the guard flattens the

@@ -14,7 +14,7 @@ from oracle.env_step import sym
 from oracle.layout import ACT0, CMD_BX, CMD_TIMER, EPSUM0, PX, QW, TGT_H, TGT_X, TGT_Y, VX
 from oracle.mathlib import F
 
-S_LEVEL = 3     # csrc/wl_elev.hip ES_LEVEL
+S_LEVEL = 3     # csrc/wl_elev_env.h ES_LEVEL
 
 
 def uniform_below(word, n):

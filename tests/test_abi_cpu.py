@@ -207,6 +207,25 @@ def test_layout_of_task_structs_and_misuse_codes(tmp_path):
                     (hf_args(30000, 30000, 1.0, base), -1), (hf_args(8, 8, math.inf, base), -1)):
         assert lib.wl_visual_step_hf(C.byref(vp), C.byref(good), C.byref(tm), C.byref(hfx), base, C.byref(out), 0, 0, None) == rc
         assert lib.wl_visual_reset_hf(C.byref(vp), C.byref(good), C.byref(tm), C.byref(hfx), None, 0, 0, None) == rc
+    # the heightfield forms and the visual-depth step refuse the same maps as the plane's entry points: none, not square, past 24 bits
+    hfg = hf_args(8, 8, 1.0, base)
+    for bad in (None, A.WlTravMap(base, base, 400, 500, 10, 0.5, 0.5), A.WlTravMap(base, base, 500, 400, 10, 0.5, 0.5),
+                A.WlTravMap(base, base, 1 << 23, 1 << 23, 10, 0.5, 0.5), A.WlTravMap(base, base, 50000, 50000, 10, 0.5, 0.5)):
+        mref = None if bad is None else C.byref(bad)
+        assert lib.wl_visual_step_hf(C.byref(vp), C.byref(good), mref, C.byref(hfg), base, C.byref(out), 0, 0, None) == -1
+        assert lib.wl_visual_reset_hf(C.byref(vp), C.byref(good), mref, C.byref(hfg), None, 0, 0, None) == -1
+        assert lib.wl_visual_depth_step(C.byref(vp), C.byref(good), mref, C.byref(hfg), base, 10.0, base, C.byref(out), 0, 0, None) == -1
+    # wl_visual_mdp: no map struct, no map bytes, an empty map (it needs neither the spawn-cell table nor the camera's 24-bit limit)
+    for bad in (None, A.WlTravMap(None, base, 500, 500, 10, 0.5, 0.5), A.WlTravMap(base, base, 0, 0, 10, 0.5, 0.5)):
+        mref = None if bad is None else C.byref(bad)
+        assert lib.wl_visual_mdp(C.byref(vp), mref, 100, 128, base, base, base, base, base, base, None) == -1
+    # wl_visual_rollout: a negative step count, no actions, an output block with a row missing
+    vro = lib.wl_visual_rollout
+    assert vro(C.byref(vp), C.byref(good), C.byref(tm), base, C.byref(out), 100 * A.VIS_OBS_DIM, 100, -1, 0, 0, None) == -1
+    assert vro(C.byref(vp), C.byref(good), C.byref(tm), None, C.byref(out), 100 * A.VIS_OBS_DIM, 100, 2, 0, 0, None) == -1
+    for part in (A.WlStepOut(None, base, base, base, None), A.WlStepOut(base, None, base, base, None),
+                 A.WlStepOut(base, base, None, base, None), A.WlStepOut(base, base, base, None, None)):
+        assert vro(C.byref(vp), C.byref(good), C.byref(tm), base, C.byref(part), 100 * A.VIS_OBS_DIM, 100, 2, 0, 0, None) == -1
     for hfx, rc in ((hf_args(8, 8, 1.0, base + 2), -3), (hf_args(1 << 23, 2, 1.0, base), -1), (hf_args(30000, 30000, 1.0, base), -1)):
         assert lib.wl_elev_step(C.byref(ep), C.byref(good), C.byref(hfx), base, C.byref(out), 0, 0, None) == rc
 

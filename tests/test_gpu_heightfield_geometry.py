@@ -6,7 +6,7 @@ outside_z, passed to ElevBatch / VisualDepthBatch.  Poses are written straight i
   * every scan form (fused step, split launch, persistent rollout, collector) equal to observe() of the state it leaves, on G1 and G5;
   * steps against the oracle on G1 - G3 in both kernel forms, cars spawned over each border; the visual-depth task on G1;
   * settled cars on the exact plane G6 need no excuse; reset heights on G1 against sample64(guard=True).
-Mutation seen caught: x0 and y0 swapped in wl_elev.hip::scan_frame -- test_height_scan_against_float64[G1] (over a million rays off)."""
+Mutation seen caught: x0 and y0 swapped in wl_elev_scan_dev.h::scan_frame -- test_height_scan_against_float64[G1] (over a million rays off)."""
 import numpy as np
 import pytest
 import torch

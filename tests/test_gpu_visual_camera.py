@@ -1,4 +1,4 @@
-"""The visual task's camera (wl_visual.hip::render_image) held pixel by pixel to tests/visual_camera_reference.py: hand-set poses written
+"""The visual task's camera (wl_visual_cam_dev.h::render_image) held pixel by pixel to tests/visual_camera_reference.py: hand-set poses written
 into the state rows (tests/visual_camera_cases.py: level, rolled and pitched, on a side / the roof / the nose, 0.05 - 5 m up and at /
 below the plane, around every map edge and corner, 10 km away; the golden map and an asymmetric one-cell pattern at 500, 101, 64 and 600
 cells; shifted intrinsics; sky 0 / 0.5 / 1).  Stage 1: the kernel's class per pixel, zero unexplained.  Stage 2: every augmentation

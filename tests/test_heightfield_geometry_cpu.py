@@ -97,7 +97,7 @@ def test_oracle_sample_and_height_map_against_float64(name):
 def test_guard_is_what_separates_the_scan_from_the_contacts():
     """G1 rises with a slope of 1 through its far borders: within 1e-3 cell of them the guarded (contact) and guard-free (scan)
     definitions differ by up to 1e-3 cell x 0.1 m x 1 = 1e-4 m, more than the scan's bound there (2e-5 m + the slope times the
-    position error) -- which is why the scan is held to the guard-free definition, the one wl_elev.hip implements"""
+    position error) -- which is why the scan is held to the guard-free definition, the one wl_elev_scan_dev.h implements"""
     f = HC.get("G1")
     v = np.linspace(0.5, f.ny - 1.5, 4001)
     u = np.full_like(v, f.nx - 1 - 1e-6)

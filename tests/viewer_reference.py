@@ -29,7 +29,7 @@ def _camera(p):
 
 
 def trav_albedo(m, row_spacing, col_spacing, x, y, with_bit=False):
-    """the map lookup of wl_visual.hip::map_id in float32 (truncation toward zero, clamp); with_bit: also the traversability bit"""
+    """the map lookup of wl_visual_env.h::map_id in float32 (truncation toward zero, clamp); with_bit: also the traversability bit"""
     rows, cols = m.shape
     rs, cs = F32(row_spacing), F32(col_spacing)
     width, height = F32(rows) * rs, F32(cols) * cs

@@ -1,4 +1,4 @@
-"""The visual task's grey camera (wl_visual.hip::render_image) restated in float64 -- TEST INFRASTRUCTURE, never imported by the product.
+"""The visual task's grey camera (wl_visual_cam_dev.h::render_image) restated in float64 -- TEST INFRASTRUCTURE, never imported by the product.
 Inputs are what the kernel is handed (fp32 pose rows, fp32 intrinsics and augmentation values, the byte map, the fp32 spacing), widened
 to float64; every operation after that is float64, so the only error left in a comparison is the kernel's.  Two stages:
 

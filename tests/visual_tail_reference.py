@@ -1,6 +1,6 @@
 """The post-physics tail of the visual and visual-depth steps restated in float64 (test infrastructure: never imported by the product).
 
-`visual_env_step` (wheeledlab_amd/csrc/wl_visual.hip) from `veh_post` on, in its own order: the time-out, `out_of_map` and the
+`visual_env_step` (wheeledlab_amd/csrc/wl_visual_env.h) from `veh_post` on, in its own order: the time-out, `out_of_map` and the
 non-finite rule, the two reward terms (traversable_reward, forward_vel), reward and episode sums, the episode metrics, the reset
 draw (a random traversable cell, a random yaw, on a heightfield the lift onto the terrain under the cell), the rows the step stores
 and the eight proprioceptive values of the post-reset state with the zeroed last action.  Inputs are the fp32 rows a step stores
@@ -16,7 +16,7 @@ Bound.  An element passes when |got - ref| <= n U m + E (tests/drift_tail_refere
 the element's longest path, m = the first-order magnitude propagated item by item, E = the intrinsics' documented error;
 -ffp-contract=fast: where the source does not spell the fma the UNFUSED path is counted).  Nothing was tuned against GPU output.
 
-Roundings per element (wl_math.h: mat_from_quat, mul_t, sincos_rev; wl_visual.hip: visual_env_step, draw_visual_reset,
+Roundings per element (wl_math.h: mat_from_quat, mul_t, sincos_rev; wl_visual_env.h: visual_env_step, draw_visual_reset,
 visual_reset_pose; wl_implicit_task.h: veh_post, weigh_rewards, episode_end_metrics, veh_reset, store_veh_rows):
   element                      n    path
   truncated                    0    ep_len + 1 >= max_episode_length: integers, EXACT

@@ -423,7 +423,7 @@ WL_DEV PyrHead pyramid_head(const DepthGrid& g, const Pyramid& py, const FieldMe
 }
 
 // camera ray of pixel (row, col) of the FULL 60 x 80 image in the body frame: optical axis = body +x, image right = body -y,
-// image down = body -z (the visual camera's convention, wl_visual.hip).  Body x component 1: the ray parameter IS the
+// image down = body -z (the visual camera's convention, wl_visual_cam_dev.h).  Body x component 1: the ray parameter IS the
 // image-plane distance.
 WL_DEV V3 depth_pixel_ray_body(const WlVisualParams& p, int row, int col) {
     return v3(1.f, -(((float)col + 0.5f - p.cx) / p.fx), -(((float)row + 0.5f - p.cy) / p.fy));

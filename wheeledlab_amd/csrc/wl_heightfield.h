@@ -12,7 +12,7 @@ namespace {
 // 4-byte gather (the address is only 2-byte aligned: gfx950 takes unaligned dword loads from global memory, buffers and LDS --
 // the compiler emits global_load_dword / ds_read_b32 for them), a cell's four corners two of them; decoding is one conversion
 // (SDWA: sign-extended half -> float) and one multiply per corner, the same on every CONTACT and DEPTH path, so that those samplers
-// of a field see exactly the floats the oracle's decoded grid holds.  The one exception is the height SCAN (wl_elev.hip::scan_value,
+// of a field see exactly the floats the oracle's decoded grid holds.  The one exception is the height SCAN (wl_elev_scan_dev.h::scan_value,
 // shared by all four scan forms): it blends the four corner codes and scales once -- identical when z_scale is a power of two
 // (terrain.py's default 2^-13; scaling by 2^k commutes with every rounding), different in the last bit otherwise (IsaacLab's
 // vertical_scale 0.005): the scan's parity bound is 2e-5 m (tests/test_gpu_elev_parity.py), not bit equality with the decoded grid.

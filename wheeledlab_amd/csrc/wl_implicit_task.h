@@ -195,7 +195,7 @@ WL_DEV void veh_rows_from(VehRows<LANES>& r, const VehState& s, const VehPost& o
 // ---- where a resetting env's draw comes from: `src(e, draw)` with `draw()` the task's own draw for env e ----
 // A helper wavefront draws the block's resets while the physics runs (round 6): the draw depends on (seed, env, step) and the terrain
 // only, and with a reset somewhere in nearly every launch the elevation draw's ~0.9 us (two Philox blocks, a terrain sample's round
-// trip, sin / cos) was on the fused launch's critical path (the visual draw: wl_visual.hip visual_env_step).  ResetHelper lives in LDS.
+// trip, sin / cos) was on the fused launch's critical path (the visual draw: wl_visual_env.h visual_env_step).  ResetHelper lives in LDS.
 struct InlineReset {
     template <class F>
     WL_DEV auto operator()(int, F draw) const { return draw(); }

@@ -241,6 +241,12 @@ inline void launch_quad(int n_envs, F&& launch) {
     else if (n_envs <= 8192) launch(std::integral_constant<int, 128>{}, (lanes + 127) / 128);
     else launch(std::integral_constant<int, kBlock>{}, grid_for(lanes));
 }
+// a runtime bool as a template argument of a launch: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+inline void with_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
 // Step kernels come in two forms (wl_vehicle.h): lane-per-env (no redundant work: best when the chip is full) and
 // quad-per-env (one wheel per lane: shorter critical path, 4x the waves: best while the chip is under-filled).
 // 256 CUs x 4 SIMDs = 1024 wave slots at one wave per SIMD; quads pay off up to a few waves per SIMD.

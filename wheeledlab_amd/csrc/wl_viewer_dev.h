@@ -147,7 +147,7 @@ WL_DEV void viewer_car(const WlViewerParams& p, const ViewerGeom& g, const Viewe
     px.n = mul(car.R, nl);
 }
 
-// TraversabilityHashmapUtil.get_map_id (visual/utils/traversability_utils.py:83-88), restated from wl_visual.hip::map_id (not
+// TraversabilityHashmapUtil.get_map_id (visual/utils/traversability_utils.py:83-88), restated from wl_visual_env.h::map_id (not
 // shared: moving it would change the visual task's sources): float32 arithmetic, truncation toward zero, clamp to the map
 WL_DEV bool viewer_traversable(const WlTravMap& m, float x, float y) {
     const float width = (float)m.rows * m.row_spacing, height = (float)m.cols * m.col_spacing;

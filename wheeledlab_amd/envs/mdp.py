@@ -240,7 +240,7 @@ def increase_reward_weight_over_time(env, env_ids, reward_term_name: str, increa
 def terrain_levels_goal(env, env_ids=None, asset_cfg=_ROBOT):
     """IsaacLab's `terrain_levels` curriculum for the goal task: an env that ends its episode at the goal moves a row of tiles up,
     one that fails (below the minimum height, stuck, rolled over, non-finite) a row down, a time-out stays; past the last row it
-    draws a uniform row.  The move itself is made INSIDE the step kernels, where the resets are (csrc/wl_elev.hip next_level;
+    draws a uniform row.  The move itself is made INSIDE the step kernels, where the resets are (csrc/wl_elev_env.h next_level;
     flatten.py switches it on when a CurrTerm names this function); the term's value -- logged as Curriculum/terrain_levels -- is the
     mean level, a 0-dim device tensor."""
     levels = env._batch.levels

@@ -240,7 +240,7 @@ class CameraData:
         """`output["rgb"]` [N, 60, 80, 3] uint8 (mdp_sensors/observations.py:60-62 `camera_data_rgb`): the designed camera's view of the
         black / white traversability plane, all 60 rows, no augmentation -- each pixel one ray against the z = 0 plane with a map lookup
         (white 255 on a traversable cell, black 0 off it or off the map, grey 127 where the ray misses the plane), the model the fused
-        observation kernel evaluates for the lower 40 rows (csrc/wl_visual.hip, oracle/visual_step.py::camera).  Plain torch: this is
+        observation kernel evaluates for the lower 40 rows (csrc/wl_visual_cam_dev.h, oracle/visual_step.py::camera).  Plain torch: this is
         the un-wired debugging / logging path, not env.step()."""
         b = self._b
         if not hasattr(b, "trav_map"):

@@ -1,6 +1,6 @@
 """Terrain curriculum, host side: the tables a generated terrain's levels start from (include/wheeledlab_amd.h WlTerrainLevels)
 and the checks a config must pass.  numpy only and importable without a device; the rule that moves an env between rows lives in
-the step kernels (csrc/wl_elev.hip next_level) and, restated, in tests/terrain_levels_reference.py.
+the step kernels (csrc/wl_elev_env.h next_level) and, restated, in tests/terrain_levels_reference.py.
 
 IsaacLab's names: `terrain_origins` [rows, cols] are the tile centres, `terrain_levels` / `terrain_types` the row / column of
 every env, `env_origins` the centres gathered per env (isaaclab.terrains.TerrainImporter with a curriculum generator)."""
@@ -10,7 +10,7 @@ import numpy as np
 
 from .terrain_gen_cfg import lattice, philox4x32
 
-LEVEL_STREAM = 3       # csrc/wl_elev.hip ES_LEVEL: the Philox stream of the initial levels (step 0) and of the wrap draw (the step)
+LEVEL_STREAM = 3       # csrc/wl_elev_env.h ES_LEVEL: the Philox stream of the initial levels (step 0) and of the wrap draw (the step)
 
 
 def philox_word0(gid, step: int, stream: int, seed: int, rounds: int = 7) -> np.ndarray:
