@@ -391,6 +391,30 @@ OBSHIST_SIGNATURES = {
     "wl_obs_history_push": (C.c_int, [_i32, _i32, _vp, _i64, _P(WlObsHistoryTerm), _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/wheeledlab_amd_obsnoise.h: observation corruption -- a header of its own, outside the drop-in step boundary
+WL_OBSCORRUPT_VERSION = 1
+OBSCORRUPT_MAX_TERMS = 64
+OBSCORRUPT_MAX_DIM = 1 << 20
+OC_STREAM_NOISE, OC_STREAM_BIAS = 16, 17
+OC_NONE, OC_CONSTANT, OC_UNIFORM, OC_GAUSSIAN = 0, 1, 2, 3
+OC_ADD, OC_SCALE, OC_ABS = 0, 1, 2
+
+
+class WlObsCorruptTerm(C.Structure):
+    _fields_ = [("off", C.c_int32), ("width", C.c_int32), ("noise_kind", C.c_int32), ("noise_op", C.c_int32), ("noise_a", C.c_float),
+                ("noise_b", C.c_float), ("bias_kind", C.c_int32), ("bias_per_component", C.c_int32), ("bias_a", C.c_float), ("bias_b", C.c_float),
+                ("bias_off", C.c_int32), ("has_scale", C.c_int32), ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("scale", C.c_float),
+                ("state_row", C.c_int32)]
+
+
+# every symbol include/wheeledlab_amd_obsnoise.h declares
+OBSCORRUPT_SIGNATURES = {
+    "wl_obs_corrupt_version": (C.c_int, []),
+    "wl_obs_corrupt_width": (C.c_int64, [_P(WlObsCorruptTerm), _i32, _i32]),
+    "wl_obs_corrupt_apply": (C.c_int, [_i32, _i32, _vp, _i64, _P(WlObsCorruptTerm), _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _u64, _u64, _u64,
+                                       _i32, _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -413,7 +437,7 @@ def load(path: str | None = None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **OBSNORM_SIGNATURES,
-                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES}.items():
+                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES, **OBSCORRUPT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -434,6 +458,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has ray-caster version {lib.wl_raycast_version()}, python expects {WL_RAYCASTER_VERSION}: rebuild")
     if lib.wl_obs_history_version() != WL_OBSHIST_VERSION:
         raise HipExtensionMissing(f"{path} has observation-history version {lib.wl_obs_history_version()}, python expects {WL_OBSHIST_VERSION}: rebuild")
+    if lib.wl_obs_corrupt_version() != WL_OBSCORRUPT_VERSION:
+        raise HipExtensionMissing(f"{path} has observation-corruption version {lib.wl_obs_corrupt_version()}, python expects {WL_OBSCORRUPT_VERSION}: rebuild")
     _lib = lib
     return lib
 

@@ -11,7 +11,10 @@
 // WL_RS_NOISE1 (normals 8..11 + high-frequency push): layout in wl_drift_env.h.  The other tasks' reset draws use streams 0..2 of their own
 // enums (wl_elev_env.h ES_*, wl_visual_env.h).  Ids 1..3 and 6 are free since the drift draws were packed (round 4).
 enum WlRngStream : uint32_t { WL_RS_DRIFT_EVENTS = 0, WL_RS_NOISE0 = 4, WL_RS_NOISE1 = 5, WL_RS_POLICY = 7, WL_RS_STARTUP = 8,
-                            WL_RS_STARTUP_BUCKET = 9, WL_RS_STARTUP_WHEELS = 10 };
+                            WL_RS_STARTUP_BUCKET = 9, WL_RS_STARTUP_WHEELS = 10,
+                            // observation corruption (wl_obs_corrupt.hip): the low 8 bits of a stream word that carries the column block above them;
+                            // 11 .. 15 are the terrain's (wheeledlab_amd_terrain.h WL_TS_*)
+                            WL_RS_OBS_NOISE = 16, WL_RS_OBS_BIAS = 17 };
 
 struct U4 {
     uint32_t x, y, z, w;

@@ -10,7 +10,7 @@ from dataclasses import dataclass, field
 from .. import _abi as A
 from ..params import MUSHR_CHASSIS_MASS, mushr_vehicle
 from .configclass import fields_of
-from .managers_cfg import AdditiveGaussianNoiseCfg
+from . import corruption
 
 INT_MAX = 2 ** 31 - 1
 
@@ -43,6 +43,7 @@ class FlatDriftCfg:
     obs_dim: int = 14
     task: str = "drift"
     extra: dict = field(default_factory=dict)
+    corruption: bool = False                                # the corruption layer is built (envs/corruption.py): the step writes the clean row
 
 
 def _terms(cfg):
@@ -134,17 +135,13 @@ def flatten_drift_cfg(cfg) -> FlatDriftCfg:
         raise NotImplementedError(f"the policy observation must start with the fused kernel's layout {want} (got {got}); "
                                   "further terms are evaluated with torch and concatenated behind it")
     flat.custom_obs = obs_terms[len(want):]
-    p.enable_corruption = int(bool(pol.enable_corruption))
+    # what the step cannot draw itself (uniform noise, a mean, a noise model, noise on last_action, clip / scale on the
+    # proprioceptive terms) is the corruption layer's (envs/corruption.py): the step then writes the CLEAN row
+    corruption.normalise(obs_terms)
+    flat.corruption = corruption.needed(pol, obs_terms, "drift")
+    p.enable_corruption = 0 if flat.corruption else int(bool(pol.enable_corruption))
     for i, (_, t) in enumerate(obs_terms[:4]):
-        n = t.noise
-        if n is None:
-            p.noise_std[i] = 0.0
-        elif isinstance(n, AdditiveGaussianNoiseCfg) and n.mean == 0.0:
-            p.noise_std[i] = float(n.std)
-        else:
-            raise NotImplementedError("only zero-mean additive Gaussian observation noise is fused")
-        if t.clip is not None or t.scale is not None:
-            raise NotImplementedError("clip / scale on the proprioceptive terms is not fused")
+        p.noise_std[i] = 0.0 if flat.corruption or t.noise is None else float(t.noise.std)
     if tuple(obs_terms[4][1].clip or ()) != (-1.0, 1.0):
         raise NotImplementedError("last_action must be clipped to (-1, 1) (common/observations.py:52)")
 
@@ -238,6 +235,7 @@ class FlatTaskCfg:
     curriculum: list = field(default_factory=list)
     obs_dim: int = 0
     extra: dict = field(default_factory=dict)
+    corruption: bool = False
 
 
 def _common_vehicle(cfg, p, acfg):
@@ -365,8 +363,10 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     want = ["goal_relative_xyz", "root_euler_xyz", "base_lin_vel", "base_ang_vel", "last_action", "world_height_map"]
     obs_terms = _terms(cfg.observations.policy)
     got = [getattr(t.func, "__name__", str(t.func)) for _, t in obs_terms]
-    if got[:len(want)] != want or cfg.observations.policy.enable_corruption:
-        raise NotImplementedError(f"the policy observation must start with the fused kernel's layout {want} (no corruption); got {got}")
+    if got[:len(want)] != want:
+        raise NotImplementedError(f"the policy observation must start with the fused kernel's layout {want}; got {got}")
+    corruption.normalise(obs_terms)
+    flat.corruption = corruption.needed(cfg.observations.policy, obs_terms, "elevation")      # the step itself draws no noise
     flat.custom_obs = obs_terms[len(want):]
     hm = obs_terms[5][1]
     p.scan_offset, p.elev_z0 = float(hm.params.get("offset", 0.084)), float(hm.params.get("plane_init_value", 0.19))
@@ -533,8 +533,10 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     want = ["raycast_depth" if depth_task else "camera_data_rgb_flattened_aug", "base_lin_vel", "base_ang_vel", "last_action"]
     vis_obs = _terms(cfg.observations.policy)
     got = [getattr(t.func, "__name__", str(t.func)) for _, t in vis_obs]
-    if got[:len(want)] != want or cfg.observations.policy.enable_corruption:
-        raise NotImplementedError(f"the policy observation must start with the fused kernel's layout {want} (no corruption); got {got}")
+    if got[:len(want)] != want:
+        raise NotImplementedError(f"the policy observation must start with the fused kernel's layout {want}; got {got}")
+    corruption.normalise(vis_obs)
+    flat.corruption = corruption.needed(cfg.observations.policy, vis_obs, "visual_depth" if depth_task else "visual")
     flat.custom_obs = vis_obs[len(want):]
     cam = cfg.scene.camera
     if (cam.height, cam.width) != (60, 80):

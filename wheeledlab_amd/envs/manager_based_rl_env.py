@@ -21,6 +21,7 @@ from .. import _abi as A
 from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
 from ..field import assemble_terrain
 from .configclass import fields_of
+from .corruption import ObsCorruption, resolve as resolve_corruption
 from .flatten import flatten_cfg
 from .history import ObsHistory, resolve as resolve_history
 from .scene import SceneView
@@ -156,9 +157,9 @@ class ObservationManager:
         env = self._env
         if env._history is not None:
             if not env._history.filled:       # read before the first reset: every frame is the current one
-                env._history.push(env._with_custom_obs(env._batch.observe()), env._batch.terminated, fresh=True)
+                env._history.push(env._current_row(), env._batch.terminated, fresh=True)
             return {"policy": env._history.current()}
-        return {"policy": env._with_custom_obs(env._batch.observe())}
+        return {"policy": env._current_row()}
 
 
 def episode_log_keys(reward_slots, term_names):
@@ -292,6 +293,10 @@ class ManagerBasedRLEnv:
         self._has_custom_rewards = bool(self._custom_rew or self._custom_term or self._custom_obs)
         self._obs_dim = self._batch.OBS_DIM
         self._history = None
+        # observation corruption (envs/corruption.py): with the layer, plugin terms are evaluated by `func` alone and their noise, clip
+        # and scale move into its launch
+        self._corruption = None
+        self._plugins_raw = bool(flat.corruption)
         custom_widths = []
         if self._custom_obs:
             # shape probe on the un-reset state: nothing it renders may be kept (the scene camera caches per step)
@@ -308,6 +313,13 @@ class ManagerBasedRLEnv:
         # observation history (envs/history.py): with any term keeping more than one frame the env owns the stacked rows; without,
         # nothing is built and no path below changes
         obs_terms = [(k, v) for k, v in fields_of(cfg.observations.policy) if hasattr(v, "func")]
+        # the corruption layer: noise models, clip and scale of every term in one launch between the raw row and the history push;
+        # built only for what the fused kernels cannot express, else nothing changes
+        clayout = resolve_corruption(cfg.observations.policy, obs_terms, list(self._batch.OBS_TERM_WIDTHS) + custom_widths, flat.task)
+        assert (clayout is not None) == bool(flat.corruption)
+        if clayout is not None:
+            assert clayout.D == self._obs_dim
+            self._corruption = ObsCorruption(clayout, self._batch)
         layout = resolve_history(cfg.observations.policy, obs_terms, list(self._batch.OBS_TERM_WIDTHS) + custom_widths)
         if layout is not None:
             assert layout.D == self._obs_dim
@@ -368,6 +380,8 @@ class ManagerBasedRLEnv:
         for t in self._custom_epsum.values():
             t.zero_()
         obs = self._with_custom_obs(self._batch.observe())
+        if self._corruption is not None:      # every env draws its episode's bias; the step is the current count
+            obs = self._corruption.corrupt(obs, self._corruption.all)
         if self._history is not None:         # every frame of every env is the reset frame
             obs = self._history.push(obs, self._batch.terminated, fresh=True)
         self.obs_buf = {"policy": obs}
@@ -403,6 +417,8 @@ class ManagerBasedRLEnv:
         self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
+        if self._corruption is not None:      # noise -> clip -> scale, before the history; keyed by the step count after the step
+            obs = self._corruption.corrupt(obs, terminated, truncated)
         if self._history is not None:         # the flags the step returns: an env they name starts over with this frame
             obs = self._history.push(obs, terminated, truncated)
         self._curriculum_at_boundary(lambda: terminated | truncated)
@@ -434,14 +450,22 @@ class ManagerBasedRLEnv:
         self.action_manager.prev_action = a
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()
-        if self._history is None:
+        if self._history is None and self._corruption is None:
             b.rollout(storage.actions[k:k + 1], storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
         else:
-            # the raw row into the batch's own, then ONE launch from stacked row k to stacked row k + 1 of the storage
+            # the raw row into the batch's own; then the corruption, straight into row k + 1 of the storage without history, and with
+            # it into the env's row and from there ONE launch from stacked row k to stacked row k + 1
             b.rollout(storage.actions[k:k + 1], b.obs.unsqueeze(0), storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
-            self._history.push_into(b.obs, storage.observations[k], storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
+            raw = b.obs
+            if self._corruption is not None:
+                if self._history is None:
+                    self._corruption.apply(raw, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
+                else:
+                    raw = self._corruption.corrupt(raw, storage.terminated[k], storage.time_outs[k])
+            if self._history is not None:
+                self._history.push_into(raw, storage.observations[k], storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
@@ -474,7 +498,7 @@ class ManagerBasedRLEnv:
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
         return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._history is None
-                and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
+                and self._corruption is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
 
     def collect_rollout(self, actor_critic, storage):
         """storage.n_steps x { actor -> sample -> env.step } of the runner's collection loop (modified_rsl_rl_runner.py:70-80) in ONE
@@ -484,6 +508,8 @@ class ManagerBasedRLEnv:
         cut at curriculum boundaries exactly as rollout_policy() cuts the drift task's; call finish_collection() after it."""
         if self._history is not None:
             raise ValueError("observation history is pushed between steps; use step() or collect_step()")
+        if self._corruption is not None:
+            raise ValueError("observation corruption runs between steps; use step() or collect_step()")
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
         b = self._batch
@@ -495,6 +521,8 @@ class ManagerBasedRLEnv:
         b, K = self._batch, storage.n_steps if n_steps is None else n_steps
         if self._history is not None:         # (b.obs already holds the last raw row)
             self.obs_buf = {"policy": self._history.adopt(storage.observations[K])}
+        elif self._corruption is not None:    # (likewise; the env's corrupted row catches up)
+            self.obs_buf = {"policy": self._corruption.adopt(storage.observations[K])}
         else:
             b.obs.copy_(storage.observations[K])
             self.obs_buf = {"policy": b.obs}
@@ -513,6 +541,8 @@ class ManagerBasedRLEnv:
             raise ValueError("custom (torch) reward terms run between steps; use step()")
         if self._history is not None:
             raise ValueError("observation history is pushed between steps; use step() or collect_step()")
+        if self._corruption is not None:
+            raise ValueError("observation corruption runs between steps; use step() or collect_step()")
         b, K = self._batch, storage.n_steps
         self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))
@@ -558,6 +588,8 @@ class ManagerBasedRLEnv:
         if v.dim() == 1:
             v = v.unsqueeze(-1)
         v = v.reshape(self.num_envs, -1)
+        if self._plugins_raw:                 # noise, clip and scale are the corruption layer's
+            return v
         n = getattr(term, "noise", None)
         if n is not None and getattr(self.cfg.observations.policy, "enable_corruption", False):
             if hasattr(n, "std"):
@@ -569,6 +601,16 @@ class ManagerBasedRLEnv:
         if getattr(term, "scale", None) is not None:
             v = v * term.scale
         return v
+
+    def _current_row(self) -> torch.Tensor:
+        """the observation row as it stands, before any history: reading draws nothing new -- with corruption it is the row of the
+        last step (before the first reset: the current state's, every reset flag set)"""
+        c = self._corruption
+        if c is None:
+            return self._with_custom_obs(self._batch.observe())
+        if not c.filled:
+            c.corrupt(self._with_custom_obs(self._batch.observe()), c.all)
+        return c.row
 
     def _with_custom_obs(self, obs: torch.Tensor) -> torch.Tensor:
         if not self._custom_obs:

@@ -49,7 +49,13 @@ class EventTermCfg(ManagerTermBaseCfg):
 
 @configclass
 class NoiseCfg:
-    pass
+    """isaaclab.utils.noise.NoiseCfg: how the draw n meets the value x -- "add": x + n, "scale": x * n, "abs": n (envs/corruption.py)"""
+    operation: str = "add"
+
+
+@configclass
+class ConstantNoiseCfg(NoiseCfg):
+    bias: float = 0.0
 
 
 @configclass
@@ -65,6 +71,20 @@ class AdditiveUniformNoiseCfg(NoiseCfg):
 
 
 GaussianNoiseCfg, UniformNoiseCfg = AdditiveGaussianNoiseCfg, AdditiveUniformNoiseCfg
+
+
+@configclass
+class NoiseModelCfg:
+    """isaaclab.utils.noise.NoiseModelCfg: the noise of `noise_cfg`, as a model"""
+    noise_cfg = MISSING
+
+
+@configclass
+class NoiseModelWithAdditiveBiasCfg(NoiseModelCfg):
+    """noise(x) + bias[env]: the bias is drawn from `bias_noise_cfg` applied to zeros when the env resets and held for the episode --
+    one value per component, or with sample_bias_per_component False one per env and term"""
+    bias_noise_cfg = MISSING
+    sample_bias_per_component: bool = True
 
 
 @configclass
