@@ -415,6 +415,31 @@ OBSCORRUPT_SIGNATURES = {
                                        _i32, _vp]),
 }
 
+# include/wheeledlab_amd_events.h: per-episode domain randomisation -- a header of its own, outside the drop-in step boundary
+WL_EVENTRAND_VERSION = 1
+EVENTRAND_MAX_TERMS = 8
+ER_STREAM_VALUE, ER_STREAM_TIMER = 18, 19
+ER_MU, ER_DAMP, ER_MASS_BASE, ER_MASS_WHEELS = 0, 1, 2, 3
+ER_RESET, ER_INTERVAL = 0, 1
+ER_ADD, ER_SCALE, ER_ABS = 0, 1, 2
+ER_UNIFORM, ER_LOG_UNIFORM, ER_GAUSSIAN = 0, 1, 2
+
+
+class WlEventRandTerm(C.Structure):
+    _fields_ = [("target", C.c_int32), ("mode", C.c_int32), ("op", C.c_int32), ("dist", C.c_int32), ("p0", C.c_float), ("p1", C.c_float),
+                ("base", C.c_float), ("interval_lo", C.c_float), ("interval_hi", C.c_float), ("is_global_time", C.c_int32),
+                ("min_step_count_between_reset", C.c_int32), ("mu_s_lo", C.c_float), ("mu_s_hi", C.c_float), ("mu_d_lo", C.c_float),
+                ("mu_d_hi", C.c_float), ("num_buckets", C.c_int32), ("make_consistent", C.c_int32)]
+
+
+# every symbol include/wheeledlab_amd_events.h declares
+EVENTRAND_SIGNATURES = {
+    "wl_event_rand_version": (C.c_int, []),
+    "wl_event_rand_width": (C.c_int64, [_P(WlEventRandTerm), _i32]),
+    "wl_event_rand_apply": (C.c_int, [_i32, _vp, _i64, _P(WlEventRandTerm), _i32, _vp, _vp, _vp, _vp, C.c_uint32, _u64, _u64, C.c_float, _u64,
+                                      _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -437,7 +462,7 @@ def load(path: str | None = None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **OBSNORM_SIGNATURES,
-                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES, **OBSCORRUPT_SIGNATURES}.items():
+                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES, **OBSCORRUPT_SIGNATURES, **EVENTRAND_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -460,6 +485,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has observation-history version {lib.wl_obs_history_version()}, python expects {WL_OBSHIST_VERSION}: rebuild")
     if lib.wl_obs_corrupt_version() != WL_OBSCORRUPT_VERSION:
         raise HipExtensionMissing(f"{path} has observation-corruption version {lib.wl_obs_corrupt_version()}, python expects {WL_OBSCORRUPT_VERSION}: rebuild")
+    if lib.wl_event_rand_version() != WL_EVENTRAND_VERSION:
+        raise HipExtensionMissing(f"{path} has event-randomisation version {lib.wl_event_rand_version()}, python expects {WL_EVENTRAND_VERSION}: rebuild")
     _lib = lib
     return lib
 

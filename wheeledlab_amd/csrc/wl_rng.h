@@ -14,7 +14,9 @@ enum WlRngStream : uint32_t { WL_RS_DRIFT_EVENTS = 0, WL_RS_NOISE0 = 4, WL_RS_NO
                             WL_RS_STARTUP_BUCKET = 9, WL_RS_STARTUP_WHEELS = 10,
                             // observation corruption (wl_obs_corrupt.hip): the low 8 bits of a stream word that carries the column block above them;
                             // 11 .. 15 are the terrain's (wheeledlab_amd_terrain.h WL_TS_*)
-                            WL_RS_OBS_NOISE = 16, WL_RS_OBS_BIAS = 17 };
+                            WL_RS_OBS_NOISE = 16, WL_RS_OBS_BIAS = 17,
+                            // per-episode domain randomisation (wl_event_rand.hip): values and timers, the term index above the low 8 bits
+                            WL_RS_EVENT_VALUE = 18, WL_RS_EVENT_TIMER = 19 };
 
 struct U4 {
     uint32_t x, y, z, w;

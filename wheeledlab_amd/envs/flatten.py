@@ -11,6 +11,7 @@ from .. import _abi as A
 from ..params import MUSHR_CHASSIS_MASS, mushr_vehicle
 from .configclass import fields_of
 from . import corruption
+from . import events as event_rand
 
 INT_MAX = 2 ** 31 - 1
 
@@ -28,6 +29,8 @@ class StartupSpec:
     chassis_mass: float = MUSHR_CHASSIS_MASS
     track_radius: float = 0.8
     track_straight: float = 0.8
+    throttle_damping: float = 30.0      # the asset's throttle DCMotorCfg.damping / stiffness: what a reset / interval gain term applies
+    throttle_stiffness: float = 0.0     # its operation to, and the one stiffness it may name (envs/events.py)
 
 
 @dataclass
@@ -44,6 +47,7 @@ class FlatDriftCfg:
     task: str = "drift"
     extra: dict = field(default_factory=dict)
     corruption: bool = False                                # the corruption layer is built (envs/corruption.py): the step writes the clean row
+    events: object = None                                   # envs/events.EventTable of the reset / interval randomisation terms, or None
 
 
 def _terms(cfg):
@@ -91,6 +95,7 @@ def flatten_drift_cfg(cfg) -> FlatDriftCfg:
     v.half_track = acfg.base_width / 2
     v.wheel_radius = acfg.wheel_radius
     su.damping = (float(thr.damping),) * 2
+    su.throttle_damping, su.throttle_stiffness = float(thr.damping), float(thr.stiffness or 0.0)
 
     # ---- rewards ----
     for i in range(A.WL_MAX_REW_TERMS):
@@ -172,6 +177,8 @@ def flatten_drift_cfg(cfg) -> FlatDriftCfg:
             su.mass_add = tuple(pr["mass_distribution_params"])
         elif ev == "push" and term.mode == "interval":
             pushes.append((name, term))
+        elif event_rand.is_episodic(term):      # friction / gains / mass per episode: the layer between steps (envs/events.py)
+            continue
         else:
             raise NotImplementedError(f"event term '{name}' ({getattr(term.func, '__name__', term.func)}, mode {term.mode}) "
                                       "has no HIP implementation")
@@ -196,6 +203,7 @@ def flatten_drift_cfg(cfg) -> FlatDriftCfg:
         p.enable_pushes = 1
     if p.num_ref_points > 32:
         raise NotImplementedError("at most 32 reference poses")
+    flat.events = event_rand.resolve(cfg.events, su, "drift")
 
     flat.curriculum = _terms(cfg.curriculum)
     p.log_episode_sums = 1
@@ -236,6 +244,7 @@ class FlatTaskCfg:
     obs_dim: int = 0
     extra: dict = field(default_factory=dict)
     corruption: bool = False
+    events: object = None                                   # as FlatDriftCfg.events
 
 
 def _common_vehicle(cfg, p, acfg):
@@ -299,6 +308,8 @@ def _startup_events(cfg, su, allowed_reset):
                 raise NotImplementedError("randomize_rigid_body_mass: operation add / abs")
         elif ev == "actuator_gains" and term.mode == "startup":
             su.damping = tuple(pr["damping_distribution_params"])
+        elif event_rand.is_episodic(term):      # friction / gains / mass per episode: the layer between steps (envs/events.py)
+            continue
         else:
             raise NotImplementedError(f"event term '{name}' ({getattr(term.func, '__name__', term.func)}, mode {term.mode}) "
                                       "has no HIP implementation for this task")
@@ -323,6 +334,7 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
     p.max_episode_length = math.ceil(cfg.episode_length_s / (float(cfg.sim.dt) * int(cfg.decimation)))
     acfg = _action(cfg, p)
     su.damping = (_common_vehicle(cfg, p, acfg),) * 2
+    su.throttle_damping, su.throttle_stiffness = su.damping[0], float(cfg.scene.robot.actuators["throttle_joints"].stiffness or 0.0)
     for i in range(A.WL_MAX_REW_TERMS):
         p.weight[i] = 0.0
     for name, term in _terms(cfg.rewards):
@@ -384,6 +396,7 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
                 raise ValueError(f"events.{name}.func = '{term.func}': not an event term of wheeledlab_amd.envs.mdp")
             term.func = getattr(mdp, term.func)
     rt = _startup_events(cfg, su, ("reset_uniform", "reset_from_terrain"))
+    flat.events = event_rand.resolve(cfg.events, su, "elevation")
     from_terrain = rt is not None and getattr(rt.func, "wl_event", None) == "reset_from_terrain"
     if rt is not None:
         pr, vr = rt.params["pose_range"], rt.params["velocity_range"]
@@ -504,6 +517,7 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     p.max_episode_length = math.ceil(cfg.episode_length_s / (float(cfg.sim.dt) * int(cfg.decimation)))
     acfg = _action(cfg, p)
     su.damping = (_common_vehicle(cfg, p, acfg),) * 2
+    su.throttle_damping, su.throttle_stiffness = su.damping[0], float(cfg.scene.robot.actuators["throttle_joints"].stiffness or 0.0)
     for i in range(A.WL_MAX_REW_TERMS):
         p.weight[i] = 0.0
     for name, term in _terms(cfg.rewards):
@@ -546,6 +560,7 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     p.cx, p.cy = cam.width / 2, cam.height / 2
     p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] = cam.body_pos
     _startup_events(cfg, su, ("reset_traversable",))
+    flat.events = event_rand.resolve(cfg.events, su, flat.task)
     flat.curriculum = _terms(cfg.curriculum)
     t = cfg.scene.terrain
     flat.extra.update(map=t.traversability_hashmap, map_size=(t.num_rows, t.num_cols), env_size=(t.env_num_rows, t.env_num_cols),

@@ -22,6 +22,7 @@ from ..core import DriftBatch, ElevBatch, VisualBatch, VisualDepthBatch
 from ..field import assemble_terrain
 from .configclass import fields_of
 from .corruption import ObsCorruption, resolve as resolve_corruption
+from .events import EventRandomizer
 from .flatten import flatten_cfg
 from .history import ObsHistory, resolve as resolve_history
 from .scene import SceneView
@@ -327,6 +328,12 @@ class ManagerBasedRLEnv:
             self.observation_manager.group_obs_dim["policy"] = layout.shape
             self.single_observation_space = {"policy": Box(-math.inf, math.inf, layout.shape)}
             self.observation_space = {"policy": Box(-math.inf, math.inf, (self.num_envs, *layout.shape))}
+        # per-episode domain randomisation (envs/events.py): friction, gain and mass events in mode reset / interval, one launch between
+        # steps; built only when the config holds such a term, else nothing changes.  (_event_direct: the mdp functions called directly)
+        self._event_rand = None
+        self._event_direct = None
+        if flat.events is not None:
+            self._event_rand = EventRandomizer(flat.events, self._batch, flat.startup, self.step_dt)
         self._has_curriculum = bool(flat.curriculum)
         self._clip_actions = False
         self._sim_step_counter = 0
@@ -376,6 +383,8 @@ class ManagerBasedRLEnv:
         if seed is not None:
             self.seed(seed)
         self._batch.reset()
+        if self._event_rand is not None:      # IsaacLab's initial reset: the reset-mode terms on every env, per-env timers drawn again
+            self._event_rand.reset_all()
         self.extras = {}
         for t in self._custom_epsum.values():
             t.zero_()
@@ -417,6 +426,8 @@ class ManagerBasedRLEnv:
         self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
+        if self._event_rand is not None:      # the envs the step reset start their episode with fresh constants; interval timers run
+            self._event_rand.apply(terminated, truncated)
         if self._corruption is not None:      # noise -> clip -> scale, before the history; keyed by the step count after the step
             obs = self._corruption.corrupt(obs, terminated, truncated)
         if self._history is not None:         # the flags the step returns: an env they name starts over with this frame
@@ -453,12 +464,16 @@ class ManagerBasedRLEnv:
         if self._history is None and self._corruption is None:
             b.rollout(storage.actions[k:k + 1], storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
+            if self._event_rand is not None:
+                self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
         else:
             # the raw row into the batch's own; then the corruption, straight into row k + 1 of the storage without history, and with
             # it into the env's row and from there ONE launch from stacked row k to stacked row k + 1
             b.rollout(storage.actions[k:k + 1], b.obs.unsqueeze(0), storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
             raw = b.obs
+            if self._event_rand is not None:      # (as in step(): after the step, before the corruption)
+                self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
             if self._corruption is not None:
                 if self._history is None:
                     self._corruption.apply(raw, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
@@ -498,7 +513,7 @@ class ManagerBasedRLEnv:
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
         return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._history is None
-                and self._corruption is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
+                and self._corruption is None and self._event_rand is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
 
     def collect_rollout(self, actor_critic, storage):
         """storage.n_steps x { actor -> sample -> env.step } of the runner's collection loop (modified_rsl_rl_runner.py:70-80) in ONE
@@ -510,6 +525,8 @@ class ManagerBasedRLEnv:
             raise ValueError("observation history is pushed between steps; use step() or collect_step()")
         if self._corruption is not None:
             raise ValueError("observation corruption runs between steps; use step() or collect_step()")
+        if self._event_rand is not None:
+            raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
         b = self._batch
@@ -543,6 +560,8 @@ class ManagerBasedRLEnv:
             raise ValueError("observation history is pushed between steps; use step() or collect_step()")
         if self._corruption is not None:
             raise ValueError("observation corruption runs between steps; use step() or collect_step()")
+        if self._event_rand is not None:
+            raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
         b, K = self._batch, storage.n_steps
         self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))

@@ -189,22 +189,41 @@ class reset_root_state_along_track(ManagerTermBase):
         env._batch.reset(mask)
 
 
+def _randomize_now(env, func, env_ids, params):
+    """a randomisation event called directly (user code): the term applied to `env_ids` now by the env's event layer
+    (envs/events.py EventRandomizer.apply_ids; the draws are keyed by env id and by how often this term was applied to the env).
+    In a config the three functions are markers: mode "startup" is the constructor's, "reset" / "interval" the layer's launch."""
+    from types import SimpleNamespace
+    from .events import EventRandomizer, term_row
+    term = SimpleNamespace(func=func, mode="reset", params=params, interval_range_s=None, is_global_time=False, min_step_count_between_reset=0)
+    row = term_row(func.__name__, term, env._flat.startup)
+    layer = env._event_rand or env._event_direct
+    if layer is None:
+        layer = env._event_direct = EventRandomizer(None, env._batch, env._flat.startup, env.step_dt)
+    layer.apply_ids(row, env_ids)
+
+
 @_event("wheel_friction")
 def randomize_rigid_body_material(env, env_ids, static_friction_range, dynamic_friction_range, restitution_range,
                                   num_buckets, asset_cfg=None, make_consistent=False):
-    raise RuntimeError("startup event: applied by the env constructor (flatten.py), not callable per step")
+    _randomize_now(env, randomize_rigid_body_material, env_ids,
+                   dict(static_friction_range=static_friction_range, dynamic_friction_range=dynamic_friction_range, restitution_range=restitution_range,
+                        num_buckets=num_buckets, asset_cfg=asset_cfg, make_consistent=make_consistent))
 
 
 @_event("actuator_gains")
 def randomize_actuator_gains(env, env_ids, asset_cfg=None, stiffness_distribution_params=None,
                              damping_distribution_params=None, operation="abs", distribution="uniform"):
-    raise RuntimeError("startup event: applied by the env constructor (flatten.py), not callable per step")
+    _randomize_now(env, randomize_actuator_gains, env_ids,
+                   dict(asset_cfg=asset_cfg, stiffness_distribution_params=stiffness_distribution_params,
+                        damping_distribution_params=damping_distribution_params, operation=operation, distribution=distribution))
 
 
 @_event("base_mass")
 def randomize_rigid_body_mass(env, env_ids, asset_cfg=None, mass_distribution_params=None, operation="add",
                               distribution="uniform", recompute_inertia=True):
-    raise RuntimeError("startup event: applied by the env constructor (flatten.py), not callable per step")
+    _randomize_now(env, randomize_rigid_body_mass, env_ids,
+                   dict(asset_cfg=asset_cfg, mass_distribution_params=mass_distribution_params, operation=operation, distribution=distribution))
 
 
 @_event("push")
