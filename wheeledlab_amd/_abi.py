@@ -440,6 +440,20 @@ EVENTRAND_SIGNATURES = {
                                       _vp]),
 }
 
+# include/wheeledlab_amd_latency.h: action latency -- a header of its own, outside the drop-in step boundary
+WL_ACTLAT_VERSION = 1
+ACTLAT_MAX_DELAY = 16
+ACTLAT_HEAD_ROWS = 5
+AL_STREAM = 20
+
+# every symbol include/wheeledlab_amd_latency.h declares
+ACTLAT_SIGNATURES = {
+    "wl_action_latency_version": (C.c_int, []),
+    "wl_action_latency_width": (C.c_int64, [_i32]),
+    "wl_action_latency_push": (C.c_int, [_i32, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "wl_action_latency_finish": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _vp]),
+}
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwheeledlab_amd.so")
 _lib = None
 
@@ -462,7 +476,8 @@ def load(path: str | None = None):
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipExtensionMissing(f"cannot load {path}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **VIEWER_SIGNATURES, **TERRAIN_SIGNATURES, **OBSNORM_SIGNATURES,
-                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES, **OBSCORRUPT_SIGNATURES, **EVENTRAND_SIGNATURES}.items():
+                               **RAYCASTER_SIGNATURES, **OBSHIST_SIGNATURES, **OBSCORRUPT_SIGNATURES, **EVENTRAND_SIGNATURES,
+                               **ACTLAT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -487,6 +502,8 @@ def load(path: str | None = None):
         raise HipExtensionMissing(f"{path} has observation-corruption version {lib.wl_obs_corrupt_version()}, python expects {WL_OBSCORRUPT_VERSION}: rebuild")
     if lib.wl_event_rand_version() != WL_EVENTRAND_VERSION:
         raise HipExtensionMissing(f"{path} has event-randomisation version {lib.wl_event_rand_version()}, python expects {WL_EVENTRAND_VERSION}: rebuild")
+    if lib.wl_action_latency_version() != WL_ACTLAT_VERSION:
+        raise HipExtensionMissing(f"{path} has action-latency version {lib.wl_action_latency_version()}, python expects {WL_ACTLAT_VERSION}: rebuild")
     _lib = lib
     return lib
 

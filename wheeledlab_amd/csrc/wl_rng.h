@@ -16,7 +16,9 @@ enum WlRngStream : uint32_t { WL_RS_DRIFT_EVENTS = 0, WL_RS_NOISE0 = 4, WL_RS_NO
                             // 11 .. 15 are the terrain's (wheeledlab_amd_terrain.h WL_TS_*)
                             WL_RS_OBS_NOISE = 16, WL_RS_OBS_BIAS = 17,
                             // per-episode domain randomisation (wl_event_rand.hip): values and timers, the term index above the low 8 bits
-                            WL_RS_EVENT_VALUE = 18, WL_RS_EVENT_TIMER = 19 };
+                            WL_RS_EVENT_VALUE = 18, WL_RS_EVENT_TIMER = 19,
+                            // action latency (wl_action_latency.hip): the per-episode lags, id 20 (wl_action_latency_dev.h asserts it)
+                            WL_RS_ACT_LAG = WL_RS_EVENT_TIMER + 1 };
 
 struct U4 {
     uint32_t x, y, z, w;

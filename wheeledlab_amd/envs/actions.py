@@ -80,6 +80,16 @@ class RCCar4WDAction(AckermannAction):
 
 
 @configclass
+class ActionLatencyCfg:
+    """Control latency of an action term (envs/latency.py): every env applies the policy's action a number of
+    control steps (env.step() calls) late, drawn per episode from min_delay .. max_delay; per_component: steering and throttle draw lags
+    of their own.  (0, 0) is no latency and builds nothing."""
+    min_delay: int = 0
+    max_delay: int = 0
+    per_component: bool = False
+
+
+@configclass
 class AckermannActionCfg(ActionTermCfg):
     class_type = AckermannAction
     wheel_joint_names: list = MISSING
@@ -91,6 +101,7 @@ class AckermannActionCfg(ActionTermCfg):
     base_width: float = 1.0
     wheel_radius: float = 1.0
     no_reverse: bool = False
+    latency: object = None         # ActionLatencyCfg, or a dict of its fields (a command-line override); None: the action is applied at once
 
 
 @configclass

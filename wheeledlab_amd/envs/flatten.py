@@ -12,6 +12,7 @@ from ..params import MUSHR_CHASSIS_MASS, mushr_vehicle
 from .configclass import fields_of
 from . import corruption
 from . import events as event_rand
+from . import latency as action_latency
 
 INT_MAX = 2 ** 31 - 1
 
@@ -48,6 +49,7 @@ class FlatDriftCfg:
     extra: dict = field(default_factory=dict)
     corruption: bool = False                                # the corruption layer is built (envs/corruption.py): the step writes the clean row
     events: object = None                                   # envs/events.EventTable of the reset / interval randomisation terms, or None
+    latency: object = None                                  # envs/latency.LatencySpec of the action term's latency, or None
 
 
 def _terms(cfg):
@@ -204,6 +206,7 @@ def flatten_drift_cfg(cfg) -> FlatDriftCfg:
     if p.num_ref_points > 32:
         raise NotImplementedError("at most 32 reference poses")
     flat.events = event_rand.resolve(cfg.events, su, "drift")
+    flat.latency = action_latency.resolve(cfg.actions)
 
     flat.curriculum = _terms(cfg.curriculum)
     p.log_episode_sums = 1
@@ -245,6 +248,7 @@ class FlatTaskCfg:
     extra: dict = field(default_factory=dict)
     corruption: bool = False
     events: object = None                                   # as FlatDriftCfg.events
+    latency: object = None                                  # as FlatDriftCfg.latency
 
 
 def _common_vehicle(cfg, p, acfg):
@@ -397,6 +401,7 @@ def flatten_elev_cfg(cfg) -> FlatTaskCfg:
             term.func = getattr(mdp, term.func)
     rt = _startup_events(cfg, su, ("reset_uniform", "reset_from_terrain"))
     flat.events = event_rand.resolve(cfg.events, su, "elevation")
+    flat.latency = action_latency.resolve(cfg.actions)
     from_terrain = rt is not None and getattr(rt.func, "wl_event", None) == "reset_from_terrain"
     if rt is not None:
         pr, vr = rt.params["pose_range"], rt.params["velocity_range"]
@@ -561,6 +566,7 @@ def flatten_visual_cfg(cfg) -> FlatTaskCfg:
     p.cam_pos[0], p.cam_pos[1], p.cam_pos[2] = cam.body_pos
     _startup_events(cfg, su, ("reset_traversable",))
     flat.events = event_rand.resolve(cfg.events, su, flat.task)
+    flat.latency = action_latency.resolve(cfg.actions)
     flat.curriculum = _terms(cfg.curriculum)
     t = cfg.scene.terrain
     flat.extra.update(map=t.traversability_hashmap, map_size=(t.num_rows, t.num_cols), env_size=(t.env_num_rows, t.env_num_cols),

@@ -25,6 +25,7 @@ from .corruption import ObsCorruption, resolve as resolve_corruption
 from .events import EventRandomizer
 from .flatten import flatten_cfg
 from .history import ObsHistory, resolve as resolve_history
+from .latency import ActionLatency
 from .scene import SceneView
 
 
@@ -334,6 +335,11 @@ class ManagerBasedRLEnv:
         self._event_direct = None
         if flat.events is not None:
             self._event_rand = EventRandomizer(flat.events, self._batch, flat.startup, self.step_dt)
+        # action latency (envs/latency.py): per-env delayed actions, one launch before the step and one after; built only when the action
+        # term asks for it, else nothing changes.  action_manager.action stays the policy's action
+        self.action_latency = None
+        if flat.latency is not None:
+            self.action_latency = ActionLatency(flat.latency, self._batch, task=flat.task)
         self._has_curriculum = bool(flat.curriculum)
         self._clip_actions = False
         self._sim_step_counter = 0
@@ -385,6 +391,8 @@ class ManagerBasedRLEnv:
         self._batch.reset()
         if self._event_rand is not None:      # IsaacLab's initial reset: the reset-mode terms on every env, per-env timers drawn again
             self._event_rand.reset_all()
+        if self.action_latency is not None:   # every env forgets its ring and draws its episode's lags
+            self.action_latency.reset_all()
         self.extras = {}
         for t in self._custom_epsum.values():
             t.zero_()
@@ -420,7 +428,8 @@ class ManagerBasedRLEnv:
         slot = b.step_count % b.metrics_slots if b.metrics_slots > 1 else None   # this step's slot of the metric ring
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()       # one ColorJitter / GaussianBlur draw per call, as torchvision does for a batch
-        obs, rew, terminated, truncated = b.step(action)
+        # (with latency the step runs on the delayed action; `action`, the policy's, is what finish() puts back below)
+        obs, rew, terminated, truncated = b.step(action if self.action_latency is None else self.action_latency.push(action))
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
@@ -428,6 +437,8 @@ class ManagerBasedRLEnv:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
         if self._event_rand is not None:      # the envs the step reset start their episode with fresh constants; interval timers run
             self._event_rand.apply(terminated, truncated)
+        if self.action_latency is not None:   # last_action is the policy's action: before the corruption layer, which reads it from the state
+            self.action_latency.finish(action, obs, terminated, truncated)
         if self._corruption is not None:      # noise -> clip -> scale, before the history; keyed by the step count after the step
             obs = self._corruption.corrupt(obs, terminated, truncated)
         if self._history is not None:         # the flags the step returns: an env they name starts over with this frame
@@ -461,19 +472,25 @@ class ManagerBasedRLEnv:
         self.action_manager.prev_action = a
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()
+        # (with latency the step runs on the delayed action; storage.actions[k] stays what the log-prob was computed for)
+        acts = storage.actions[k:k + 1] if self.action_latency is None else self.action_latency.push(a).unsqueeze(0)
         if self._history is None and self._corruption is None:
-            b.rollout(storage.actions[k:k + 1], storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
+            b.rollout(acts, storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
             if self._event_rand is not None:
                 self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
+            if self.action_latency is not None:
+                self.action_latency.finish(a, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
         else:
             # the raw row into the batch's own; then the corruption, straight into row k + 1 of the storage without history, and with
             # it into the env's row and from there ONE launch from stacked row k to stacked row k + 1
-            b.rollout(storage.actions[k:k + 1], b.obs.unsqueeze(0), storage.rewards[k:k + 1],
+            b.rollout(acts, b.obs.unsqueeze(0), storage.rewards[k:k + 1],
                       storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
             raw = b.obs
             if self._event_rand is not None:      # (as in step(): after the step, before the corruption)
                 self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
+            if self.action_latency is not None:
+                self.action_latency.finish(a, raw, storage.terminated[k], storage.time_outs[k])
             if self._corruption is not None:
                 if self._history is None:
                     self._corruption.apply(raw, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
@@ -513,7 +530,7 @@ class ManagerBasedRLEnv:
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
         return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._history is None
-                and self._corruption is None and self._event_rand is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
+                and self._corruption is None and self._event_rand is None and self.action_latency is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
 
     def collect_rollout(self, actor_critic, storage):
         """storage.n_steps x { actor -> sample -> env.step } of the runner's collection loop (modified_rsl_rl_runner.py:70-80) in ONE
@@ -527,6 +544,8 @@ class ManagerBasedRLEnv:
             raise ValueError("observation corruption runs between steps; use step() or collect_step()")
         if self._event_rand is not None:
             raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
+        if self.action_latency is not None:
+            raise ValueError("action latency delays actions between steps; use step() or collect_step()")
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
         b = self._batch
@@ -562,6 +581,8 @@ class ManagerBasedRLEnv:
             raise ValueError("observation corruption runs between steps; use step() or collect_step()")
         if self._event_rand is not None:
             raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
+        if self.action_latency is not None:
+            raise ValueError("action latency delays actions between steps; use step() or collect_step()")
         b, K = self._batch, storage.n_steps
         self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))

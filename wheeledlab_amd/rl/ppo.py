@@ -341,11 +341,13 @@ class OnPolicyRunner:
         base = env.unwrapped
         can_fuse = (getattr(base, "_task", None) == "drift" and self.actor_critic.fusable()
                     and not getattr(base, "_has_custom_rewards", False) and getattr(base, "_history", None) is None
-                    and getattr(base, "_corruption", None) is None and getattr(base, "_event_rand", None) is None)
+                    and getattr(base, "_corruption", None) is None and getattr(base, "_event_rand", None) is None
+                    and getattr(base, "action_latency", None) is None)
         if fused and not can_fuse:
             raise ValueError("fused collection needs the drift task, [64, 64] elu/relu MLPs, only built-in reward terms, no "
                              "observation history and no observation corruption layer (noise models, uniform or biased noise, clip / "
-                             "scale: envs/corruption.py), and no friction, gain or mass event in mode reset or interval (envs/events.py)")
+                             "scale: envs/corruption.py), no friction, gain or mass event in mode reset or interval (envs/events.py), and no action "
+                             "latency (envs/latency.py)")
         self.fused = can_fuse if fused is None else bool(fused)
         # per-step collection (every task, any observation width): the policy step as one launch (wl_actor_critic_act)
         can_act = self.device.type == "cuda" and self.actor_critic.act_fusable() and hasattr(base, "_batch")
