@@ -118,6 +118,36 @@ def test_storage_rows_k_and_k_plus_1_are_accepted_and_a_row_onto_itself_is_refus
     assert np.array_equal(got[0], rows_w[0]) and np.array_equal(got[1], R.push_closed(tab, obs_w, rows_w[0], np.zeros(n, bool)))
 
 
+@pytest.mark.parametrize("which", ["reset_a", "reset_b"])
+@pytest.mark.parametrize("where", ["first bytes", "last bytes"])
+def test_reset_flags_inside_next_are_refused_and_nothing_is_launched(which, where):
+    """what the launch stores may touch nothing it reads: flag bytes that lie on `next` are WL_EINVAL, and `next` keeps every word"""
+    A, lib = _lib()
+    tab, D, Dh = R.table(*R.TABLES["elevation"])
+    ct = _ctable(A, tab)
+    n = 3
+    rng = np.random.default_rng(1)
+    obs, prev = _dev(R.special_words(rng, (n, D))), _dev(R.special_words(rng, (n, Dh)))
+    nxt = torch.full((n * Dh,), GUARD, dtype=torch.int32, device=DEV)
+    inside = nxt.view(torch.uint8)                                           # n * Dh * 4 bytes
+    lying = inside[:n] if where == "first bytes" else inside[n * Dh * 4 - 1:]      # (the last: one byte of the n overlaps)
+    good = torch.zeros(n, dtype=torch.bool, device=DEV)
+    ra, rb = (lying, good) if which == "reset_a" else (good, lying)
+    s = A.stream(torch.device(DEV))
+    rc = lib.wl_obs_history_push(n, D, obs.data_ptr(), D, ct, len(tab), prev.data_ptr(), nxt.data_ptr(), ra.data_ptr(), rb.data_ptr(), s)
+    assert rc == -1                                                          # WL_EINVAL
+    torch.cuda.synchronize()
+    assert (_host(nxt) == GUARD).all()
+    # flags that end where `next` begins, or begin where it ends, touch nothing of it: accepted
+    buf = torch.full((n * Dh + 8,), 0, dtype=torch.int32, device=DEV)
+    nxt2 = buf[4:4 + n * Dh]
+    before, after = buf[:4].view(torch.uint8)[16 - n:], buf[4 + n * Dh:].view(torch.uint8)[:n]
+    assert before.data_ptr() + n == nxt2.data_ptr() and after.data_ptr() == nxt2.data_ptr() + n * Dh * 4
+    assert lib.wl_obs_history_push(n, D, obs.data_ptr(), D, ct, len(tab), prev.data_ptr(), nxt2.data_ptr(), before.data_ptr(), after.data_ptr(), s) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(_host(nxt2).reshape(n, Dh), R.push_closed(tab, _host(obs).reshape(n, D), _host(prev).reshape(n, Dh), np.zeros(n, bool)))
+
+
 # ---- the env ---------------------------------------------------------------------------------------------------------
 
 def _env(task, n, seed=11, steps_per_episode=4, edit=None):

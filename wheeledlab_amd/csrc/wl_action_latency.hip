@@ -27,24 +27,6 @@ __global__ void __launch_bounds__(kBlock) action_latency_finish_kernel(const Act
     actlat_finish_env(e, a);
 }
 
-inline bool overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
-struct Span {
-    const void* p;
-    int64_t bytes;
-};
-// one of the first `stored` (non-NULL) spans, which the launch writes, on any other span
-template <int N>
-bool any_overlap(const Span (&v)[N], int stored) {
-    for (int i = 0; i < stored; ++i)
-        for (int j = i + 1; j < N; ++j)
-            if (v[i].p && v[j].p && overlap(v[i].p, v[i].bytes, v[j].p, v[j].bytes)) return true;
-    return false;
-}
-
 }  // namespace
 
 extern "C" {

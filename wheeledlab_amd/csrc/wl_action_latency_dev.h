@@ -11,19 +11,18 @@
 #include <cstdint>
 
 #include "../../include/wheeledlab_amd_latency.h"
+#include "wl_layer_common.h"
 #include "wl_rng.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define WL_AL_HD __host__ __device__ __forceinline__   // what the host entry points call too
-
 static_assert(WL_RS_ACT_LAG == WL_AL_STREAM && WL_AL_STREAM == 20, "the lag draw's stream id is 20");
 constexpr int AL_LAG = 0, AL_PUSHES = 2, AL_HEAD = 3, AL_DRAWN = 4, AL_RING = WL_ACTLAT_HEAD_ROWS;
 
 // the rows of the layer block, or -1
-WL_AL_HD int64_t actlat_width(int max_delay) {
+WL_HD int64_t actlat_width(int max_delay) {
     return max_delay < 0 || max_delay > WL_ACTLAT_MAX_DELAY ? -1 : (int64_t)AL_RING + 2 * ((int64_t)max_delay + 1);
 }
 
@@ -89,7 +88,7 @@ WL_DEV uint32_t actlat_lag(uint32_t w, int min_delay, int span) {
 WL_DEV void actlat_finish_env(int e, const ActLatFinishArgs& a) {
     const int64_t s = a.stride;
     uint32_t* B = a.block + e;
-    const bool reset = (a.reset_a[e] | (a.reset_b ? a.reset_b[e] : (uint8_t)0)) != 0;
+    const bool reset = WL_LAYER_RESET(a, e);
     if (reset) {
         const uint32_t drawn = B[AL_DRAWN * s];
         const U4 w = philox_block(a.env0 + (uint32_t)e, (uint64_t)drawn, (uint32_t)WL_RS_ACT_LAG, a.seed);

@@ -21,16 +21,10 @@ struct EventRandTable {
 
 __global__ void __launch_bounds__(kBlock) event_rand_kernel(const EventRandArgs a, const EventRandTable tab) {
     __shared__ EventRandDevTerm t[WL_EVENTRAND_MAX_TERMS];
-    if ((int)threadIdx.x < a.n_terms) t[threadIdx.x] = tab.t[threadIdx.x];
-    __syncthreads();
+    layer_table_to_lds(t, tab, a.n_terms);
     const int e = blockIdx.x * kBlock + threadIdx.x;
     if (e >= a.n) return;
     eventrand_env(e, a, t);
-}
-
-inline bool overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
 }
 
 }  // namespace
@@ -52,16 +46,15 @@ int wl_event_rand_apply(int32_t n, float* state, int64_t stride, const WlEventRa
     if (rows < 0) return WL_EINVAL;
     if (stride * 4 * WL_S_COUNT > 0x7fffffffLL) return WL_EINVAL;
     if (n_terms < 32 && (mask_terms >> n_terms) != 0u) return WL_EINVAL;
-    if (!(step_dt >= 0.f) || !er_finite(step_dt)) return WL_EINVAL;
+    if (!(step_dt >= 0.f) || !layer_finite(step_dt)) return WL_EINVAL;
     // what the launch stores (the four constant rows, the block) may touch nothing else it reads or stores
     static_assert(WL_S_MU_D == WL_S_MU_S + 1 && WL_S_DAMP == WL_S_MU_S + 2 && WL_S_MASS == WL_S_MU_S + 3, "the constant rows are adjacent");
-    const float* consts = state + (int64_t)WL_S_MU_S * stride;
-    const int64_t consts_bytes = (3 * stride + n) * 4, block_bytes = ((rows - 1) * stride + n) * 4;
-    if (overlap(consts, consts_bytes, block, block_bytes)) return WL_EINVAL;
-    const auto stored = [&](const void* p, int64_t bytes) {
-        return p && (overlap(consts, consts_bytes, p, bytes) || overlap(block, block_bytes, p, bytes));
-    };
-    if (stored(reset_a, n) || stored(reset_b, n) || stored(mask, n)) return WL_EINVAL;
+    const Span spans[] = {{state + (int64_t)WL_S_MU_S * stride, (3 * stride + n) * 4},
+                          {block, ((rows - 1) * stride + n) * 4},
+                          {reset_a, n},
+                          {reset_b, n},
+                          {mask, n}};
+    if (any_overlap(spans, 2)) return WL_EINVAL;
     if (stride % 64 != 0 || !aligned(state, 4) || !aligned(block, 4)) return WL_EALIGN;
     EventRandArgs a{};
     a.state = state;

@@ -13,13 +13,12 @@
 #include <cstdint>
 
 #include "../../include/wheeledlab_amd_events.h"
+#include "wl_layer_common.h"
 #include "wl_rng.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define WL_ER_HD __host__ __device__ __forceinline__   // integer / table code the host entry points call too
 
 // a term as the kernel carries it: 48 bytes.  code: bits 0-1 target, 2 mode, 3-4 operation, 5-6 distribution, 7 global time, 8 consistent
 struct EventRandDevTerm {
@@ -31,24 +30,22 @@ struct EventRandDevTerm {
     int32_t nb;
 };
 constexpr uint32_t ER_GLOBAL = 1u << 7, ER_CONSISTENT = 1u << 8;
-WL_ER_HD int er_target(uint32_t code) { return (int)(code & 3u); }
-WL_ER_HD int er_mode(uint32_t code) { return (int)((code >> 2) & 1u); }
-WL_ER_HD int er_op(uint32_t code) { return (int)((code >> 3) & 3u); }
-WL_ER_HD int er_dist(uint32_t code) { return (int)((code >> 5) & 3u); }
+WL_HD int er_target(uint32_t code) { return (int)(code & 3u); }
+WL_HD int er_mode(uint32_t code) { return (int)((code >> 2) & 1u); }
+WL_HD int er_op(uint32_t code) { return (int)((code >> 3) & 3u); }
+WL_HD int er_dist(uint32_t code) { return (int)((code >> 5) & 3u); }
 
 constexpr int ER_ROWS_HEAD = 2, ER_ROWS_PER_TERM = 4;   // part_base, part_wheels; then time_left, applied, last_step / drawn (two words)
 
-WL_ER_HD bool er_finite(float x) { return x - x == 0.f; }
-
 // the validated table -> the rows of the layer block, or -1
-WL_ER_HD int64_t eventrand_width(const WlEventRandTerm* t, int n_terms) {
+WL_HD int64_t eventrand_width(const WlEventRandTerm* t, int n_terms) {
     if (!t || n_terms < 1 || n_terms > WL_EVENTRAND_MAX_TERMS) return -1;
     for (int k = 0; k < n_terms; ++k) {
         const WlEventRandTerm& q = t[k];
         if (q.target < WL_ER_MU || q.target > WL_ER_MASS_WHEELS || q.mode < WL_ER_RESET || q.mode > WL_ER_INTERVAL) return -1;
         if (q.op < WL_ER_ADD || q.op > WL_ER_ABS || q.dist < WL_ER_UNIFORM || q.dist > WL_ER_GAUSSIAN) return -1;
-        if (!er_finite(q.p0) || !er_finite(q.p1) || !er_finite(q.base) || !er_finite(q.interval_lo) || !er_finite(q.interval_hi)) return -1;
-        if (!er_finite(q.mu_s_lo) || !er_finite(q.mu_s_hi) || !er_finite(q.mu_d_lo) || !er_finite(q.mu_d_hi)) return -1;
+        if (!layer_finite(q.p0) || !layer_finite(q.p1) || !layer_finite(q.base) || !layer_finite(q.interval_lo) || !layer_finite(q.interval_hi)) return -1;
+        if (!layer_finite(q.mu_s_lo) || !layer_finite(q.mu_s_hi) || !layer_finite(q.mu_d_lo) || !layer_finite(q.mu_d_hi)) return -1;
         if (q.dist == WL_ER_GAUSSIAN ? q.p1 < 0.f : q.p0 > q.p1) return -1;
         if (q.dist == WL_ER_LOG_UNIFORM && !(q.p0 > 0.f)) return -1;
         if (q.target == WL_ER_MASS_WHEELS && q.op != WL_ER_ABS) return -1;
@@ -132,7 +129,7 @@ WL_DEV float eventrand_timer(uint32_t id, uint32_t drawn, int k, const EventRand
 // stored at the end, so that of two terms on one target the later one is what the rows hold.
 WL_DEV void eventrand_env(int e, const EventRandArgs& a, const EventRandDevTerm* t) {
     const uint32_t env = a.env0 + (uint32_t)e;
-    const bool reset = (a.reset_a[e] | (a.reset_b ? a.reset_b[e] : (uint8_t)0)) != 0;
+    const bool reset = WL_LAYER_RESET(a, e);
     const bool masked = a.mask != nullptr && a.mask[e] != 0;
     const int64_t s = a.stride;
     float mu_s = 0.f, mu_d = 0.f, damp = 0.f, part_base = 0.f, part_wheels = 0.f;

@@ -30,8 +30,7 @@ typedef uint32_t oc_u32x2 __attribute__((ext_vector_type(2)));
 
 __global__ void __launch_bounds__(kBlock) obs_corrupt_kernel(const ObsCorruptArgs a, uint32_t* out, const int64_t out_stride, const ObsCorruptTable tab) {
     __shared__ ObsCorruptDevTerm t[WL_OBSCORRUPT_MAX_TERMS];
-    if ((int)threadIdx.x < a.n_terms) t[threadIdx.x] = tab.t[threadIdx.x];
-    __syncthreads();
+    layer_table_to_lds(t, tab, a.n_terms);
     const unsigned gid = blockIdx.x * kBlock + threadIdx.x;        // (unsigned: the last block may reach past 2^31)
     if (gid >= (unsigned)a.lanes) return;
     const int lane = (int)gid;
@@ -78,11 +77,6 @@ __global__ void __launch_bounds__(kBlock) obs_corrupt_kernel(const ObsCorruptArg
     }
 }
 
-inline bool overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -108,20 +102,20 @@ int wl_obs_corrupt_apply(int32_t n, int32_t D, const float* obs, int64_t obs_str
     const int64_t limit = ((int64_t)1 << 31) - 16;
     if ((int64_t)n * obs_stride >= limit || (int64_t)n * out_stride >= limit || (int64_t)n * (Db > 0 ? Db : 1) >= limit) return WL_EINVAL;
     const int64_t obs_bytes = ((int64_t)(n - 1) * obs_stride + D) * 4, out_bytes = ((int64_t)(n - 1) * out_stride + D) * 4;
+    // what the launch stores (`out`, the bias block) may touch nothing else it reads: the raw rows -- unless they ARE `out`, in place
+    // with equal strides, where every lane reads its own words before it writes them --, the flags and the state rows of the table
     const bool in_place = (const float*)out == obs && out_stride == obs_stride;
-    if (!in_place && overlap(out, out_bytes, obs, obs_bytes)) return WL_EINVAL;
-    const int64_t bias_bytes = (int64_t)n * Db * 4;
-    if (Db > 0 && (overlap(out, out_bytes, bias, bias_bytes) || overlap(obs, obs_bytes, bias, bias_bytes))) return WL_EINVAL;
-    // what the launch stores (`out`, the bias block) may touch nothing else it reads: the flags and the state rows of the table
-    const auto stored = [&](const void* p, int64_t bytes) {
-        return p && (overlap(out, out_bytes, p, bytes) || (Db > 0 && overlap(bias, bias_bytes, p, bytes)));
-    };
-    if (stored(reset_a, n) || stored(reset_b, n)) return WL_EINVAL;
+    Span spans[5 + WL_OBSCORRUPT_MAX_TERMS] = {{out, out_bytes},
+                                               {Db > 0 ? bias : nullptr, (int64_t)n * Db * 4},
+                                               {in_place ? nullptr : obs, obs_bytes},
+                                               {reset_a, n},
+                                               {reset_b, n}};      // then one per term: NULL without a state row
     for (int k = 0; k < n_terms; ++k) {
         if (terms[k].state_row < 0) continue;
         const int64_t words = (int64_t)(terms[k].width - 1) * state_stride + n;      // rows state_row .. state_row + width - 1, n of each
-        if (stored(state + (int64_t)terms[k].state_row * state_stride, words * 4)) return WL_EINVAL;
+        spans[5 + k] = Span{state + (int64_t)terms[k].state_row * state_stride, words * 4};
     }
+    if (any_overlap(spans, 2)) return WL_EINVAL;
     if (!aligned(obs, 4) || !aligned(out, 4) || !aligned(state, 4) || !aligned(bias, 4)) return WL_EALIGN;
     ObsCorruptArgs a{};
     a.obs = (const uint32_t*)obs;

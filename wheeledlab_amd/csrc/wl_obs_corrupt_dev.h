@@ -13,13 +13,12 @@
 #include <cstdint>
 
 #include "../../include/wheeledlab_amd_obsnoise.h"
+#include "wl_layer_common.h"
 #include "wl_rng.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-#define WL_OC_HD __host__ __device__ __forceinline__   // integer / table code the host entry points call too
 
 constexpr int OBSCORRUPT_SLOT = 4;   // columns per lane: the four words of one Philox block
 
@@ -34,18 +33,17 @@ struct ObsCorruptDevTerm {
     int32_t state_row;
 };
 constexpr uint32_t OC_PER_COMPONENT = 1u << 6, OC_SCALE = 1u << 7, OC_CLIP = 1u << 8;
-WL_OC_HD int oc_noise_kind(uint32_t code) { return (int)(code & 3u); }
-WL_OC_HD int oc_op(uint32_t code) { return (int)((code >> 2) & 3u); }
-WL_OC_HD int oc_bias_kind(uint32_t code) { return (int)((code >> 4) & 3u); }
+WL_HD int oc_noise_kind(uint32_t code) { return (int)(code & 3u); }
+WL_HD int oc_op(uint32_t code) { return (int)((code >> 2) & 3u); }
+WL_HD int oc_bias_kind(uint32_t code) { return (int)((code >> 4) & 3u); }
 
-WL_OC_HD bool oc_finite(float x) { return x - x == 0.f; }
-WL_OC_HD bool oc_kind_ok(int32_t kind, float a, float b) {
+WL_HD bool oc_kind_ok(int32_t kind, float a, float b) {
     if (kind < WL_OC_NONE || kind > WL_OC_GAUSSIAN) return false;
-    return kind == WL_OC_NONE || (oc_finite(a) && (kind == WL_OC_CONSTANT || oc_finite(b)));
+    return kind == WL_OC_NONE || (layer_finite(a) && (kind == WL_OC_CONSTANT || layer_finite(b)));
 }
 
 // the validated table -> Db, the floats of bias per env, or -1
-WL_OC_HD int64_t obscorrupt_width(const WlObsCorruptTerm* t, int n_terms, int D) {
+WL_HD int64_t obscorrupt_width(const WlObsCorruptTerm* t, int n_terms, int D) {
     if (!t || n_terms < 1 || n_terms > WL_OBSCORRUPT_MAX_TERMS || D < 1 || D > WL_OBSCORRUPT_MAX_DIM) return -1;
     int64_t off = 0, bias = 0;
     for (int k = 0; k < n_terms; ++k) {
@@ -57,14 +55,14 @@ WL_OC_HD int64_t obscorrupt_width(const WlObsCorruptTerm* t, int n_terms, int D)
         if (q.bias_per_component != 0 && q.bias_per_component != 1) return -1;
         if (q.bias_off != bias) return -1;
         if (!(q.clip_lo <= q.clip_hi)) return -1;                       // (a NaN bound fails the comparison)
-        if (!oc_finite(q.scale) || (q.has_scale != 0 && q.has_scale != 1) || (!q.has_scale && q.scale != 1.f)) return -1;
+        if (!layer_finite(q.scale) || (q.has_scale != 0 && q.has_scale != 1) || (!q.has_scale && q.scale != 1.f)) return -1;
         off += q.width;
         if (q.bias_kind != WL_OC_NONE) bias += q.bias_per_component ? q.width : 1;
     }
     return off == D ? bias : -1;
 }
 
-WL_OC_HD ObsCorruptDevTerm obscorrupt_pack(const WlObsCorruptTerm& q) {
+WL_HD ObsCorruptDevTerm obscorrupt_pack(const WlObsCorruptTerm& q) {
     ObsCorruptDevTerm d;
     d.off = q.off;
     d.width = q.width;
@@ -137,7 +135,7 @@ WL_DEV void obscorrupt_lane(int e, int c0, int count, const ObsCorruptArgs& a, c
                             uint32_t (&v)[OBSCORRUPT_SLOT]) {
     const uint32_t env = a.env0 + (uint32_t)e;
     const uint32_t blk = (uint32_t)c0 >> 2;
-    const bool reset = (a.reset_a[e] | (a.reset_b ? a.reset_b[e] : (uint8_t)0)) != 0;
+    const bool reset = WL_LAYER_RESET(a, e);
     int k = obscorrupt_seek(c0, t, a.n_terms);
     U4 wn{}, wb{};
     bool have_n = false;

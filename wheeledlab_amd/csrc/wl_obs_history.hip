@@ -27,8 +27,7 @@ typedef uint32_t obshist_u32x4 __attribute__((ext_vector_type(4)));
 // slower at the elevation and visual shapes
 __global__ void __launch_bounds__(kBlock) obshist_push_kernel(const ObsHistArgs a, uint32_t* __restrict__ next, const ObsHistTable tab) {
     __shared__ WlObsHistoryTerm t[WL_OBSHIST_MAX_TERMS];
-    if ((int)threadIdx.x < a.n_terms) t[threadIdx.x] = tab.t[threadIdx.x];
-    __syncthreads();
+    layer_table_to_lds(t, tab, a.n_terms);
     const int slot = (int)(blockIdx.x * kBlock + threadIdx.x);
     if (slot >= a.slots) return;
     uint32_t v[OBSHIST_SLOT];
@@ -40,11 +39,6 @@ __global__ void __launch_bounds__(kBlock) obshist_push_kernel(const ObsHistArgs 
     } else {
         for (int i = 0; i < count; ++i) next[j0 + i] = v[i];
     }
-}
-
-inline bool overlap(const void* p, int64_t p_bytes, const void* q, int64_t q_bytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)q_bytes && b < a + (uintptr_t)p_bytes;
 }
 
 }  // namespace
@@ -65,8 +59,10 @@ int wl_obs_history_push(int32_t n, int32_t D, const float* obs, int64_t obs_stri
     if (Dh < 0 || obs_stride < D) return WL_EINVAL;
     const int64_t limit = ((int64_t)1 << 31) - 16;
     if ((int64_t)n * Dh >= limit || (int64_t)n * obs_stride >= limit) return WL_EINVAL;
+    // what the launch stores (`next`) may touch nothing it reads: the raw rows, the previous stacked rows, the flags
     const int64_t row_bytes = (int64_t)n * Dh * 4;
-    if (overlap(next, row_bytes, obs, (int64_t)n * obs_stride * 4) || (prev && overlap(next, row_bytes, prev, row_bytes))) return WL_EINVAL;
+    const Span spans[] = {{next, row_bytes}, {obs, (int64_t)n * obs_stride * 4}, {prev, row_bytes}, {reset_a, n}, {reset_b, n}};
+    if (any_overlap(spans, 1)) return WL_EINVAL;
     if (!aligned(obs, 4) || !aligned(prev, 4) || !aligned(next, 4)) return WL_EALIGN;
     ObsHistArgs a{};
     a.obs = (const uint32_t*)obs;

@@ -8,10 +8,9 @@
 #include <cstdint>
 
 #include "../../include/wheeledlab_amd_history.h"
+#include "wl_layer_common.h"
 
 namespace {
-
-#define WL_OH __host__ __device__ __forceinline__
 
 constexpr int OBSHIST_SLOT = 4;   // outputs per lane: one 16-byte store
 
@@ -29,7 +28,7 @@ struct ObsHistArgs {
 };
 
 // the validated table: term k covers columns [dst_off, dst_off + width * frames) of the stacked row, in order, without gaps
-WL_OH int64_t obshist_width(const WlObsHistoryTerm* t, int n_terms, int D) {
+WL_HD int64_t obshist_width(const WlObsHistoryTerm* t, int n_terms, int D) {
     if (!t || n_terms < 1 || n_terms > WL_OBSHIST_MAX_TERMS || D < 1 || D > WL_OBSHIST_MAX_DIM) return -1;
     int64_t src = 0, dst = 0;
     for (int k = 0; k < n_terms; ++k) {
@@ -47,14 +46,14 @@ struct ObsHistCursor {
     int32_t src_off, w, span;   // of term k; span = w * frames
 };
 
-WL_OH void obshist_load_term(ObsHistCursor& q, const WlObsHistoryTerm* t) {
+WL_HD void obshist_load_term(ObsHistCursor& q, const WlObsHistoryTerm* t) {
     q.src_off = t[q.k].src_off;
     q.w = t[q.k].width;
     q.span = t[q.k].width * t[q.k].frames;
 }
 
 // the term of column c: the last k with dst_off_k <= c, six halvings over at most 64 entries
-WL_OH ObsHistCursor obshist_seek(int c, const WlObsHistoryTerm* t, int n_terms) {
+WL_HD ObsHistCursor obshist_seek(int c, const WlObsHistoryTerm* t, int n_terms) {
     int k = 0;
 #pragma unroll
     for (int step = WL_OBSHIST_MAX_TERMS / 2; step > 0; step >>= 1) {
@@ -69,7 +68,7 @@ WL_OH ObsHistCursor obshist_seek(int c, const WlObsHistoryTerm* t, int n_terms) 
 }
 
 // to the next column of the row; true: that was the row's last column and the cursor stands on column 0 of the next row
-WL_OH bool obshist_step(ObsHistCursor& q, const WlObsHistoryTerm* t, int n_terms) {
+WL_HD bool obshist_step(ObsHistCursor& q, const WlObsHistoryTerm* t, int n_terms) {
     if (++q.r < q.span) return false;
     const bool wrapped = q.k + 1 == n_terms;
     q.k = wrapped ? 0 : q.k + 1;
@@ -85,21 +84,20 @@ struct ObsHistSrc {
     int32_t col;
     bool from_obs;
 };
-WL_OH ObsHistSrc obshist_source(const ObsHistCursor& q, int c, bool fresh) {
+WL_HD ObsHistSrc obshist_source(const ObsHistCursor& q, int c, bool fresh) {
     const int newest = q.span - q.w;
     if (q.r >= newest) return ObsHistSrc{q.src_off + (q.r - newest), true};
     if (fresh) return ObsHistSrc{q.src_off + (int)((unsigned)q.r % (unsigned)q.w), true};
     return ObsHistSrc{c + q.w, false};
 }
 
-WL_OH bool obshist_fresh(const ObsHistArgs& a, int e) {
-    if (!a.prev) return true;
-    return (a.reset_a[e] | (a.reset_b ? a.reset_b[e] : (uint8_t)0)) != 0;
+WL_HD bool obshist_fresh(const ObsHistArgs& a, int e) {
+    return !a.prev || WL_LAYER_RESET(a, e);
 }
 
 // the outputs of slot s: v[0 .. count) are outputs j0 .. j0 + count - 1 of the flat [n][Dh] block; count == 4 exactly when the slot
 // is a whole 16-byte line of `next`
-WL_OH int obshist_gather(int slot, const ObsHistArgs& a, const WlObsHistoryTerm* t, uint32_t (&v)[OBSHIST_SLOT], int& j0) {
+WL_HD int obshist_gather(int slot, const ObsHistArgs& a, const WlObsHistoryTerm* t, uint32_t (&v)[OBSHIST_SLOT], int& j0) {
     const int v0 = slot * OBSHIST_SLOT - a.shift;
     j0 = v0 < 0 ? 0 : v0;
     const int j1 = v0 + OBSHIST_SLOT < a.total ? v0 + OBSHIST_SLOT : a.total;

@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _abi as A
+from .layers import BatchLayer
 from .managers_cfg import (AdditiveGaussianNoiseCfg, AdditiveUniformNoiseCfg, ConstantNoiseCfg, NoiseCfg, NoiseModelCfg,
                            NoiseModelWithAdditiveBiasCfg)
 
@@ -175,18 +176,17 @@ def resolve(group, terms, widths, fused_layout) -> CorruptionLayout | None:
     return CorruptionLayout(tuple(rows), tuple(n for n, _ in terms), off, boff, bool(getattr(group, "enable_corruption", False)))
 
 
-class ObsCorruption:
+class ObsCorruption(BatchLayer):
     """the layer of one env batch: the table, the bias block [n, Db] and the launch"""
 
     def __init__(self, layout: CorruptionLayout, batch):
         import torch
-        self.layout, self.batch, self.n, self.device = layout, batch, int(batch.n), batch.state.device
-        self.lib = A.load()
+        super().__init__(batch)                                                     # (self.all: env.reset())
+        self.layout = layout
         self.table = (A.WlObsCorruptTerm * len(layout.terms))(*[A.WlObsCorruptTerm(*t) for t in layout.terms])
         if self.lib.wl_obs_corrupt_width(self.table, len(layout.terms), layout.D) != layout.Db:
             raise ValueError(f"observation corruption: the term table {layout.terms} is not one of rows of {layout.D}")
         self.bias = torch.zeros(self.n, max(layout.Db, 1), dtype=torch.float32, device=self.device)
-        self.all = torch.ones(self.n, dtype=torch.uint8, device=self.device)      # every reset flag set: env.reset()
         self.row = torch.zeros(self.n, layout.D, dtype=torch.float32, device=self.device)   # the env's own corrupted row
         self.filled = False
 

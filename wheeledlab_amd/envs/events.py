@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _abi as A
+from .layers import BatchLayer
 
 KINDS = ("wheel_friction", "actuator_gains", "base_mass")          # the wl_event markers of the three mdp functions
 MODES = {"reset": A.ER_RESET, "interval": A.ER_INTERVAL}
@@ -155,22 +156,20 @@ def resolve(events, startup_spec, task: str = "drift") -> EventTable | None:
     return EventTable(tuple(rows), tuple(names))
 
 
-class EventRandomizer:
+class EventRandomizer(BatchLayer):
     """the layer of one env batch: the table, the block [2 + 4 K, stride] and the launch.  An empty table (K = 0) launches nothing; it
     serves direct calls of the mdp functions (apply_ids), which bring their own one-term table."""
 
     def __init__(self, table: EventTable | None, batch, startup_spec, step_dt: float):
         import torch
+        super().__init__(batch)                                                     # (self.all: env.reset(), apply_all())
         self.table = table if table is not None else EventTable((), ())
-        self.batch, self.startup, self.step_dt = batch, startup_spec, float(np.float32(step_dt))
-        self.n, self.stride, self.device = int(batch.n), int(batch.stride), batch.state.device
-        self.lib = A.load()
+        self.startup, self.step_dt = startup_spec, float(np.float32(step_dt))
         self.K = len(self.table.terms)
         self.ctable = self._ctable(self.table.terms)
         if self.K and self.lib.wl_event_rand_width(self.ctable, self.K) != 2 + 4 * self.K:
             raise ValueError(f"event randomisation: the term table {self.table.terms} is refused")
         self.block = torch.zeros(2 + 4 * self.K, self.stride, dtype=torch.float32, device=self.device)
-        self.all = torch.ones(self.n, dtype=torch.uint8, device=self.device)       # every flag set: env.reset(), apply_all()
         self.none = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
         self._mask = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
         self._direct = {}           # a direct call's row -> its own block (its counters go on from call to call)

@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _abi as A
+from .layers import BatchLayer
 
 FIELDS = ("min_delay", "max_delay", "per_component")
 LAST_ACTION_TERM = {"drift": 4, "elevation": 4, "visual": 3, "visual_depth": 3}     # the term's place in the batch's OBS_TERM_WIDTHS
@@ -73,15 +74,14 @@ def resolve(actions) -> LatencySpec | None:
     return specs[0] if specs else None
 
 
-class ActionLatency:
+class ActionLatency(BatchLayer):
     """the layer of one env batch: the block [5 + 2 (max_delay + 1), stride], the delayed actions `applied` [n, 2] and the two launches.
     push(action) before the step -> `applied`, what the step is launched on; finish(action, row, flags) after it."""
 
     def __init__(self, spec: LatencySpec, batch, last_action_col: int | None = None, task: str | None = None):
         import torch
-        self.spec, self.batch = spec, batch
-        self.n, self.stride, self.device = int(batch.n), int(batch.stride), batch.state.device
-        self.lib = A.load()
+        super().__init__(batch)
+        self.spec = spec
         self.rows = int(self.lib.wl_action_latency_width(spec.max_delay))
         if self.rows < 0 or not 0 <= spec.min_delay <= spec.max_delay:
             raise ValueError(f"action latency: delays ({spec.min_delay}, {spec.max_delay}) are refused (at most {A.ACTLAT_MAX_DELAY} control steps)")
@@ -90,7 +90,6 @@ class ActionLatency:
         self.col = int(last_action_col)
         self.block = torch.zeros(self.rows, self.stride, dtype=torch.float32, device=self.device)       # (words: counters and action bits)
         self.applied = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)
-        self.all = torch.ones(self.n, dtype=torch.uint8, device=self.device)                            # every flag set: env.reset()
         self._zero = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)
 
     def push(self, action):

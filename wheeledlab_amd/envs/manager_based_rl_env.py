@@ -26,6 +26,7 @@ from .events import EventRandomizer
 from .flatten import flatten_cfg
 from .history import ObsHistory, resolve as resolve_history
 from .latency import ActionLatency
+from .layers import StepLayers
 from .scene import SceneView
 
 
@@ -157,11 +158,7 @@ class ObservationManager:
         """the current observation.  With observation history: the stacked rows as they stand -- reading pushes nothing, and
         `update_history` (IsaacLab's argument) is accepted and changes nothing: only step() / collect_step() advance the history"""
         env = self._env
-        if env._history is not None:
-            if not env._history.filled:       # read before the first reset: every frame is the current one
-                env._history.push(env._current_row(), env._batch.terminated, fresh=True)
-            return {"policy": env._history.current()}
-        return {"policy": env._current_row()}
+        return {"policy": env._raw_row() if env._layers is None else env._layers.current(env._raw_row, env._batch.terminated)}
 
 
 def episode_log_keys(reward_slots, term_names):
@@ -294,11 +291,11 @@ class ManagerBasedRLEnv:
         # into the runner's storage) are off whenever any kind of custom term is registered
         self._has_custom_rewards = bool(self._custom_rew or self._custom_term or self._custom_obs)
         self._obs_dim = self._batch.OBS_DIM
-        self._history = None
-        # observation corruption (envs/corruption.py): with the layer, plugin terms are evaluated by `func` alone and their noise, clip
-        # and scale move into its launch
-        self._corruption = None
-        self._plugins_raw = bool(flat.corruption)
+        # The layers between steps (envs/layers.py states their order): observation history, observation corruption, per-episode event
+        # randomisation, action latency.  Each is built only for what its module says the fused kernels cannot express; with none,
+        # self._layers is None and no path below runs a launch more than the step's own.
+        history = corruption = events = latency = None
+        self._plugins_raw = bool(flat.corruption)     # with the corruption layer a plugin term's noise, clip and scale move into its launch
         custom_widths = []
         if self._custom_obs:
             # shape probe on the un-reset state: nothing it renders may be kept (the scene camera caches per step)
@@ -312,37 +309,45 @@ class ManagerBasedRLEnv:
             self.observation_manager.group_obs_dim["policy"] = (self._obs_dim,)
             self.single_observation_space = {"policy": Box(-math.inf, math.inf, (self._obs_dim,))}
             self.observation_space = {"policy": Box(-math.inf, math.inf, (self.num_envs, self._obs_dim))}
-        # observation history (envs/history.py): with any term keeping more than one frame the env owns the stacked rows; without,
-        # nothing is built and no path below changes
         obs_terms = [(k, v) for k, v in fields_of(cfg.observations.policy) if hasattr(v, "func")]
-        # the corruption layer: noise models, clip and scale of every term in one launch between the raw row and the history push;
-        # built only for what the fused kernels cannot express, else nothing changes
         clayout = resolve_corruption(cfg.observations.policy, obs_terms, list(self._batch.OBS_TERM_WIDTHS) + custom_widths, flat.task)
         assert (clayout is not None) == bool(flat.corruption)
         if clayout is not None:
             assert clayout.D == self._obs_dim
-            self._corruption = ObsCorruption(clayout, self._batch)
+            corruption = ObsCorruption(clayout, self._batch)
         layout = resolve_history(cfg.observations.policy, obs_terms, list(self._batch.OBS_TERM_WIDTHS) + custom_widths)
         if layout is not None:
             assert layout.D == self._obs_dim
-            self._history = ObsHistory(layout, self.num_envs, self.device)
+            history = ObsHistory(layout, self.num_envs, self.device)
             self.observation_manager.group_obs_dim["policy"] = layout.shape
             self.single_observation_space = {"policy": Box(-math.inf, math.inf, layout.shape)}
             self.observation_space = {"policy": Box(-math.inf, math.inf, (self.num_envs, *layout.shape))}
-        # per-episode domain randomisation (envs/events.py): friction, gain and mass events in mode reset / interval, one launch between
-        # steps; built only when the config holds such a term, else nothing changes.  (_event_direct: the mdp functions called directly)
-        self._event_rand = None
-        self._event_direct = None
+        self._event_direct = None                     # (the mdp event functions called directly: no launch between steps, no layer)
         if flat.events is not None:
-            self._event_rand = EventRandomizer(flat.events, self._batch, flat.startup, self.step_dt)
-        # action latency (envs/latency.py): per-env delayed actions, one launch before the step and one after; built only when the action
-        # term asks for it, else nothing changes.  action_manager.action stays the policy's action
-        self.action_latency = None
+            events = EventRandomizer(flat.events, self._batch, flat.startup, self.step_dt)
         if flat.latency is not None:
-            self.action_latency = ActionLatency(flat.latency, self._batch, task=flat.task)
+            latency = ActionLatency(flat.latency, self._batch, task=flat.task)
+        self._set_layers(events, latency, corruption, history)
         self._has_curriculum = bool(flat.curriculum)
         self._clip_actions = False
         self._sim_step_counter = 0
+
+    def _set_layers(self, events, latency, corruption, history):
+        """self._layers is what step(), collect_step(), reset() and the collectors go through (None without any layer); _event_rand,
+        action_latency, _corruption and _history are read-only mirrors of its layers for whoever reads one -- assigning one of the
+        three private names leaves _layers as it was.  (action_latency alone has a setter: tests/test_gpu_env_action_latency.py forces
+        a zero-lag layer onto a built env.)"""
+        self._event_rand, self._action_latency, self._corruption, self._history = layers = (events, latency, corruption, history)
+        self._layers = StepLayers(*layers) if any(x is not None for x in layers) else None
+
+    @property
+    def action_latency(self):
+        """the action-latency layer (envs/latency.py ActionLatency) or None; assignable"""
+        return self._action_latency
+
+    @action_latency.setter
+    def action_latency(self, layer):
+        self._set_layers(self._event_rand, layer, self._corruption, self._history)
 
     # ---- gym.Env surface --------------------------------------------------------------------------------------
     @property
@@ -389,18 +394,10 @@ class ManagerBasedRLEnv:
         if seed is not None:
             self.seed(seed)
         self._batch.reset()
-        if self._event_rand is not None:      # IsaacLab's initial reset: the reset-mode terms on every env, per-env timers drawn again
-            self._event_rand.reset_all()
-        if self.action_latency is not None:   # every env forgets its ring and draws its episode's lags
-            self.action_latency.reset_all()
         self.extras = {}
         for t in self._custom_epsum.values():
             t.zero_()
-        obs = self._with_custom_obs(self._batch.observe())
-        if self._corruption is not None:      # every env draws its episode's bias; the step is the current count
-            obs = self._corruption.corrupt(obs, self._corruption.all)
-        if self._history is not None:         # every frame of every env is the reset frame
-            obs = self._history.push(obs, self._batch.terminated, fresh=True)
+        obs = self._raw_row() if self._layers is None else self._layers.reset(self._raw_row, self._batch.terminated)
         self.obs_buf = {"policy": obs}
         return self.obs_buf, self.extras
 
@@ -428,21 +425,15 @@ class ManagerBasedRLEnv:
         slot = b.step_count % b.metrics_slots if b.metrics_slots > 1 else None   # this step's slot of the metric ring
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()       # one ColorJitter / GaussianBlur draw per call, as torchvision does for a batch
-        # (with latency the step runs on the delayed action; `action`, the policy's, is what finish() puts back below)
-        obs, rew, terminated, truncated = b.step(action if self.action_latency is None else self.action_latency.push(action))
+        L = self._layers      # (envs/layers.py: with latency the step runs on the delayed action; `action`, the policy's, goes to after())
+        obs, rew, terminated, truncated = b.step(action if L is None else L.delayed(action))
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
         if self._has_custom_rewards:
             obs, rew, terminated, truncated = self._apply_custom_terms(obs, rew, terminated, truncated, slot)
-        if self._event_rand is not None:      # the envs the step reset start their episode with fresh constants; interval timers run
-            self._event_rand.apply(terminated, truncated)
-        if self.action_latency is not None:   # last_action is the policy's action: before the corruption layer, which reads it from the state
-            self.action_latency.finish(action, obs, terminated, truncated)
-        if self._corruption is not None:      # noise -> clip -> scale, before the history; keyed by the step count after the step
-            obs = self._corruption.corrupt(obs, terminated, truncated)
-        if self._history is not None:         # the flags the step returns: an env they name starts over with this frame
-            obs = self._history.push(obs, terminated, truncated)
+        if L is not None:
+            obs = L.after(action, obs, terminated, truncated)
         self._curriculum_at_boundary(lambda: terminated | truncated)
         if self.cfg.sync_episode_log:
             if bool((terminated | truncated).any()):
@@ -472,32 +463,17 @@ class ManagerBasedRLEnv:
         self.action_manager.prev_action = a
         if self._task == "visual" and self._flat.extra.get("augment"):
             b.sample_augmentation()
-        # (with latency the step runs on the delayed action; storage.actions[k] stays what the log-prob was computed for)
-        acts = storage.actions[k:k + 1] if self.action_latency is None else self.action_latency.push(a).unsqueeze(0)
-        if self._history is None and self._corruption is None:
-            b.rollout(acts, storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
-                      storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
-            if self._event_rand is not None:
-                self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
-            if self.action_latency is not None:
-                self.action_latency.finish(a, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
-        else:
-            # the raw row into the batch's own; then the corruption, straight into row k + 1 of the storage without history, and with
-            # it into the env's row and from there ONE launch from stacked row k to stacked row k + 1
-            b.rollout(acts, b.obs.unsqueeze(0), storage.rewards[k:k + 1],
-                      storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
-            raw = b.obs
-            if self._event_rand is not None:      # (as in step(): after the step, before the corruption)
-                self._event_rand.apply(storage.terminated[k], storage.time_outs[k])
-            if self.action_latency is not None:
-                self.action_latency.finish(a, raw, storage.terminated[k], storage.time_outs[k])
-            if self._corruption is not None:
-                if self._history is None:
-                    self._corruption.apply(raw, storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
-                else:
-                    raw = self._corruption.corrupt(raw, storage.terminated[k], storage.time_outs[k])
-            if self._history is not None:
-                self._history.push_into(raw, storage.observations[k], storage.observations[k + 1], storage.terminated[k], storage.time_outs[k])
+        # The step's row lands straight in row k + 1 of the storage unless a layer rewrites it (corruption, history): then in the
+        # batch's own, and the last such layer writes row k + 1 -- the history in ONE launch from stacked row k to stacked row k + 1.
+        # (With latency the step runs on the delayed action; storage.actions[k] stays what the log-prob was computed for.)
+        L = self._layers
+        via_batch = L is not None and L.rewrites_obs
+        b.rollout(storage.actions[k:k + 1] if L is None else L.delayed(a).unsqueeze(0),
+                  b.obs.unsqueeze(0) if via_batch else storage.observations[k + 1:k + 2], storage.rewards[k:k + 1],
+                  storage.terminated[k:k + 1], storage.time_outs[k:k + 1], dones_out=storage.dones[k:k + 1])
+        if L is not None:
+            L.after(a, b.obs if via_batch else storage.observations[k + 1], storage.terminated[k], storage.time_outs[k],
+                    prev=storage.observations[k], out=storage.observations[k + 1])
         self.common_step_counter += 1
         self._sim_step_counter += self.cfg.decimation
         self._run_frame_hooks()
@@ -529,8 +505,11 @@ class ManagerBasedRLEnv:
 
     def can_collect_rollout(self) -> bool:
         """the whole collection loop as one launch per curriculum segment (collect_rollout): elevation task, quad form"""
-        return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._history is None
-                and self._corruption is None and self._event_rand is None and self.action_latency is None and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
+        return (self._task == "elevation" and self._batch.n <= 32768 and not self._has_custom_rewards and self._fused_refusal() is None
+                and os.environ.get("WL_ELEV_PERSISTENT_COLLECT", "1") != "0")
+
+    def _fused_refusal(self):      # why a collector of several env steps per launch cannot run on this env's layers, or None
+        return None if self._layers is None else self._layers.fused_refusal()
 
     def collect_rollout(self, actor_critic, storage):
         """storage.n_steps x { actor -> sample -> env.step } of the runner's collection loop (modified_rsl_rl_runner.py:70-80) in ONE
@@ -538,14 +517,9 @@ class ManagerBasedRLEnv:
         observation rows in LDS); observation row 0 of the storage must hold the current observation.  The critic's values
         are NOT filled in (not needed to step): evaluate storage.observations in one batched pass afterwards.  The rollout is
         cut at curriculum boundaries exactly as rollout_policy() cuts the drift task's; call finish_collection() after it."""
-        if self._history is not None:
-            raise ValueError("observation history is pushed between steps; use step() or collect_step()")
-        if self._corruption is not None:
-            raise ValueError("observation corruption runs between steps; use step() or collect_step()")
-        if self._event_rand is not None:
-            raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
-        if self.action_latency is not None:
-            raise ValueError("action latency delays actions between steps; use step() or collect_step()")
+        refusal = self._fused_refusal()
+        if refusal is not None:
+            raise ValueError(refusal)
         if not self.can_collect_rollout():
             raise NotImplementedError("the persistent collector exists for the elevation task (quad form, built-in reward terms)")
         b = self._batch
@@ -555,13 +529,12 @@ class ManagerBasedRLEnv:
     def finish_collection(self, storage, n_steps: int | None = None):
         """after the last collect_step(): the env's own observation buffer and episode log catch up with the storage"""
         b, K = self._batch, storage.n_steps if n_steps is None else n_steps
-        if self._history is not None:         # (b.obs already holds the last raw row)
-            self.obs_buf = {"policy": self._history.adopt(storage.observations[K])}
-        elif self._corruption is not None:    # (likewise; the env's corrupted row catches up)
-            self.obs_buf = {"policy": self._corruption.adopt(storage.observations[K])}
-        else:
+        # (with a layer that keeps the env's row, b.obs already holds the last raw row and the layer's own catches up)
+        row = None if self._layers is None else self._layers.adopt(storage.observations[K])
+        if row is None:
             b.obs.copy_(storage.observations[K])
-            self.obs_buf = {"policy": b.obs}
+            row = b.obs
+        self.obs_buf = {"policy": row}
         self.extras["log"] = self._episode_log(None) if b.metrics_slots == 1 else EpisodeLog(
             self.episode_metrics(window=K, reduce_ranks=False), None, self._log_keys, self.max_episode_length_s)
 
@@ -575,14 +548,9 @@ class ManagerBasedRLEnv:
             raise NotImplementedError("fused policy rollouts exist for the drift task (14-dim observation)")
         if self._has_custom_rewards:
             raise ValueError("custom (torch) reward terms run between steps; use step()")
-        if self._history is not None:
-            raise ValueError("observation history is pushed between steps; use step() or collect_step()")
-        if self._corruption is not None:
-            raise ValueError("observation corruption runs between steps; use step() or collect_step()")
-        if self._event_rand is not None:
-            raise ValueError("reset / interval event randomisation runs between steps; use step() or collect_step()")
-        if self.action_latency is not None:
-            raise ValueError("action latency delays actions between steps; use step() or collect_step()")
+        refusal = self._fused_refusal()
+        if refusal is not None:
+            raise ValueError(refusal)
         b, K = self._batch, storage.n_steps
         self._in_curriculum_segments(storage, lambda k, n: b.rollout_policy(actor_critic, storage, evaluate_critic=False, start=k, count=n))
         storage.values.copy_(actor_critic.critic(storage.observations).squeeze(-1))
@@ -642,15 +610,8 @@ class ManagerBasedRLEnv:
             v = v * term.scale
         return v
 
-    def _current_row(self) -> torch.Tensor:
-        """the observation row as it stands, before any history: reading draws nothing new -- with corruption it is the row of the
-        last step (before the first reset: the current state's, every reset flag set)"""
-        c = self._corruption
-        if c is None:
-            return self._with_custom_obs(self._batch.observe())
-        if not c.filled:
-            c.corrupt(self._with_custom_obs(self._batch.observe()), c.all)
-        return c.row
+    def _raw_row(self) -> torch.Tensor:      # the observation row of the current state, before any layer
+        return self._with_custom_obs(self._batch.observe())
 
     def _with_custom_obs(self, obs: torch.Tensor) -> torch.Tensor:
         if not self._custom_obs:

@@ -339,15 +339,14 @@ class OnPolicyRunner:
         self.actor_critic = ActorCritic(env.num_obs, env.num_obs, env.num_actions, **pol).to(self.device)
         self.alg = PPO(self.actor_critic, **alg)
         base = env.unwrapped
+        layers = getattr(base, "_layers", None)      # (envs/layers.py: what runs between steps, and why a fused launch cannot hold it)
+        refusal = None if layers is None else layers.fused_refusal()
         can_fuse = (getattr(base, "_task", None) == "drift" and self.actor_critic.fusable()
-                    and not getattr(base, "_has_custom_rewards", False) and getattr(base, "_history", None) is None
-                    and getattr(base, "_corruption", None) is None and getattr(base, "_event_rand", None) is None
-                    and getattr(base, "action_latency", None) is None)
+                    and not getattr(base, "_has_custom_rewards", False) and refusal is None)
         if fused and not can_fuse:
-            raise ValueError("fused collection needs the drift task, [64, 64] elu/relu MLPs, only built-in reward terms, no "
-                             "observation history and no observation corruption layer (noise models, uniform or biased noise, clip / "
-                             "scale: envs/corruption.py), no friction, gain or mass event in mode reset or interval (envs/events.py), and no action "
-                             "latency (envs/latency.py)")
+            from ..envs.layers import REFUSALS
+            raise ValueError("fused collection needs the drift task, [64, 64] elu/relu MLPs, only built-in reward terms and no layer between "
+                             "steps (" + "; ".join(why for _, why in REFUSALS) + ")" + (f" -- here: {refusal}" if refusal else ""))
         self.fused = can_fuse if fused is None else bool(fused)
         # per-step collection (every task, any observation width): the policy step as one launch (wl_actor_critic_act)
         can_act = self.device.type == "cuda" and self.actor_critic.act_fusable() and hasattr(base, "_batch")
